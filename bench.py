@@ -6,14 +6,18 @@ Generator -> fir/clamp/rms -> Detector on [watermarked; clean] -> {l1, mel, loud
 -> Adam update, fp32, inputs resident in HBM.  N=1 workload = BASELINE.json configs[2] (B=256 train step);
 N>1 = configs[3]: the same per-GPU batch on every rank (weak scaling) + the gradient all-reduce over RCCL
 (distributed.GradSync: Detector span from post-accumulate hooks while backward still runs, the rest after).
-Prints ONE JSON line on rank 0.  With no flags at N=1 the line also carries `other_configs`: short measurements
-of BASELINE configs[1] (B=64 eval-mode forward) and configs[4] (main14b_2, hidden 256, B=128 train step), taken
-after the headline region.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, `loss`) -- nothing else.  --full adds what the headline does not need: the `roofline` objects (HIP events
+around the dominant kernels' launches inside the timed region), the CPU-oracle `cpu_baseline` and, at N=1 on the default
+workload, `other_configs`: short measurements of BASELINE configs[1] (B=64 eval-mode forward) and configs[4] (main14b_2,
+hidden 256, B=128 train step), taken after the headline region.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs below); the inputs and weights are seeded, so two builds compare array for array.
 
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
   python bench.py --gpus N ...            (starts its own N ranks)   or
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
-  python bench.py --model main14b_2       (configs[4] as the headline line, with its own roofline / cpu_baseline)
+  python bench.py --model main14b_2 --full   (configs[4] as the headline line, with its own roofline / cpu_baseline)
 """
 from __future__ import annotations
 
@@ -205,8 +209,9 @@ def cpu_baseline_main14b2(G, D, sample_batch=16, budget_s=24.0):
                       + "; ".join(f"{r['threads']} threads {r['s_per_step']} s/step x {r['timed_steps']}" for r in runs)}
 
 
-def build_workload(model, mode, batch, rank, world, dev, torch_adam=False, force_sync=False):
-    """modules + optimizer + step closure + the dominant-kernel timer of one workload"""
+def build_workload(model, mode, batch, rank, world, dev, torch_adam=False, force_sync=False, kernel_timing=True):
+    """modules + optimizer + step closure + the dominant-kernel timers of one workload (none when not `kernel_timing`: the
+    launchers stay unwrapped)"""
     import awm_amd
     from awm_amd import distributed as wmd
     from awm_amd import ops as _ops
@@ -241,7 +246,8 @@ def build_workload(model, mode, batch, rank, world, dev, torch_adam=False, force
             return step_fn(G, D, opt, s, msg, grad_sync=sync)
 
     bf_mode = _ops.conv_bf16x6()
-    return G, D, step, kernel_timers(awm_amd.lib, model, mode, bf_mode, batch), bf_mode
+    timers = kernel_timers(awm_amd.lib, model, mode, bf_mode, batch) if kernel_timing else []
+    return G, D, step, timers, bf_mode
 
 
 BF16X6_PEAK = PEAK_BF16_MFMA_TFLOPS / 6.0
@@ -359,8 +365,8 @@ def roofline_of(entry):
     return head
 
 
-def run_workload(model, mode, batch, steps, warmup, rank, world, dev, dist, torch_adam=False, force_sync=False):
-    G, D, step, timers, bf_mode = build_workload(model, mode, batch, rank, world, dev, torch_adam, force_sync)
+def run_workload(model, mode, batch, steps, warmup, rank, world, dev, dist, torch_adam=False, force_sync=False, kernel_timing=True):
+    G, D, step, timers, bf_mode = build_workload(model, mode, batch, rank, world, dev, torch_adam, force_sync, kernel_timing)
     for _ in range(warmup):
         step()
 
@@ -397,8 +403,43 @@ def run_workload(model, mode, batch, steps, warmup, rank, world, dev, dist, torc
     assert total_loss == total_loss, "NaN"
     roofs = [r for r in (roofline_of(e) for e in timers) if r is not None]
     res = {"ms_per_step": 1e3 * dt / steps, "value": batch * world * steps / dt, "loss": total_loss,
-           "roofline": roofs[0] if roofs else None, "roofline_other_kernels": roofs[1:], "bf_mode": bf_mode, "modules": (G, D)}
+           "roofline": roofs[0] if roofs else None, "roofline_other_kernels": roofs[1:], "bf_mode": bf_mode, "modules": (G, D),
+           "outputs": out}
     return res
+
+
+DUMP_MAX_ELEMS = 1 << 20        # per array; a larger output is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20       # all arrays together
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(out, modules, mode, dirname):
+    """What the last timed step handed its caller, as <dirname>/<name>.npy: every tensor of the step's output dict (train:
+    delta_raw / delta / s_w / logits and the loss terms; fwd: delta / logits / probabilities / bit accuracy / delta RMS) and, after a
+    train step, the updated state of both modules (`generator_state`, `detector_state`: every floating-point state_dict entry --
+    parameters and BatchNorm running statistics -- flattened and concatenated in state_dict order).  float64 stays float64, every
+    other dtype is written as float32.  An array of more than DUMP_MAX_ELEMS elements is written as the elements at
+    sort(randint(0, numel, DUMP_MAX_ELEMS)) of its flattened form, drawn from a CPU generator seeded with DUMP_SAMPLE_SEED, so the
+    sample depends on the shape alone.  Returns {name: [shape of the full output, elements written]}."""
+    import numpy as np
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    if mode == "train":
+        for name, m in zip(("generator_state", "detector_state"), modules):
+            arrays[name] = torch.cat([v.detach().reshape(-1).float() for v in m.state_dict().values() if v.is_floating_point()])
+    os.makedirs(dirname, exist_ok=True)
+    written, index = 0, {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        written += a.nbytes
+        assert written <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs"
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        index[name] = [list(t.shape), int(a.size)]
+    return index
 
 
 def workload_name(model, mode, batch, world):
@@ -425,10 +466,17 @@ def main():
     ap.add_argument("--mode", choices=["train", "fwd"], default="train",
                     help="train: fwd+bwd+Adam (the BASELINE metric, default); fwd: eval-mode forward only "
                          "(BASELINE configs[1]) -- reported with its own metric name")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short configs[1] / configs[4] measurements of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline objects of the dominant kernels (HIP events around "
+                         "their launches in the timed region), the CPU-oracle baseline and, on the default workload, configs[1] / [4]")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the short configs[1] / configs[4] measurements")
     ap.add_argument("--torch-adam", action="store_true", help="use torch.optim.Adam instead of the fused flat Adam")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = 64 if args.mode == "fwd" else (128 if args.model == "main14b_2" else 256)
     if args.mode == "fwd" and args.model != "main16":
@@ -473,8 +521,11 @@ def main():
     import awm_amd
     awm_amd.lib.load()                                  # fail loudly if the HIP library is missing
 
-    r = run_workload(args.model, args.mode, args.batch, args.steps, args.warmup, rank, world, dev, dist, args.torch_adam, force_sync)
+    r = run_workload(args.model, args.mode, args.batch, args.steps, args.warmup, rank, world, dev, dist, args.torch_adam, force_sync,
+                     kernel_timing=args.full)
     if rank == 0:
+        dumped = dump_outputs(r["outputs"], r["modules"], args.mode, args.dump_outputs) if args.dump_outputs else None
+        r["outputs"] = None
         bf_mode = r["bf_mode"]
         line = {"metric": "1-s@16kHz clips/sec (gen+det+loss fwd-bwd)" if args.mode == "train" else
                           "1-s@16kHz clips/sec (gen+det forward only, eval mode)",
@@ -491,16 +542,20 @@ def main():
                                                "split on bf16 MFMA")
                            if (args.model == "main16" and bf_mode) else "native fp32 MFMA",
                            "parallelism": f"dp{world}" if world > 1 else "single"},
-                "loss": round(r["loss"], 6), "roofline": r["roofline"]}
-        if r["roofline_other_kernels"]:
-            line["roofline_other_kernels"] = r["roofline_other_kernels"]
-        if world == 1 and not args.no_cpu_baseline and args.mode == "train":
+                "loss": round(r["loss"], 6)}
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if args.full:
+            line["roofline"] = r["roofline"]
+            if r["roofline_other_kernels"]:
+                line["roofline_other_kernels"] = r["roofline_other_kernels"]
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "train":
             line["cpu_baseline"] = cpu_baseline_main16() if args.model == "main16" else cpu_baseline_main14b2(*r["modules"])
-        default_run = (args.model == "main16" and args.mode == "train" and args.batch == 256 and world == 1 and not args.no_extra
-                       and not args.torch_adam)
+        default_run = (args.full and args.model == "main16" and args.mode == "train" and args.batch == 256 and world == 1
+                       and not args.no_extra and not args.torch_adam)
         del r
-        torch.cuda.empty_cache()
         if default_run:
+            torch.cuda.empty_cache()
             # the other single-GPU BASELINE configs, measured after the headline region (5 timed steps each): parity-test
             # cases, reported for completeness -- `value` above is configs[2] alone
             extra = {}

@@ -146,12 +146,12 @@ def test_bench_launches_its_own_ranks(tmp_path, model, batch):
 
 @pytest.mark.timeout(900)
 def test_bench_line_contract():
-    """`python bench.py` on one GPU prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel (timed
-    with HIP events inside the run) and the CPU-oracle baseline (small batch here: the contract, not the number)."""
+    """`python bench.py --full` on one GPU prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel
+    (timed with HIP events inside the run) and the CPU-oracle baseline (small batch here: the contract, not the number)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--no-extra", "--full"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -170,3 +170,40 @@ def test_bench_line_contract():
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
     assert abs(line["value"] - 8 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """a plain `python bench.py` (no --full) prints the headline keys and nothing that needs runs of its own; --dump-outputs writes
+    the last timed step's outputs (float32, at most 64 MB, large arrays as a seeded sample) and the updated module state"""
+    import numpy as np
+    import bench
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(out)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "loss"):
+        assert k in line, k
+    for k in ("roofline", "roofline_other_kernels", "cpu_baseline", "other_configs"):
+        assert k not in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1
+    assert abs(line["value"] - 8 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    files = sorted(p.name for p in out.iterdir())
+    assert files == sorted(f"{k}.npy" for k in line["dumped_outputs"]), files
+    for k in ("delta", "s_w", "logits", "total", "generator_state", "detector_state"):
+        assert k in line["dumped_outputs"], k
+    total_bytes = 0
+    for name, (shape, n) in line["dumped_outputs"].items():
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size == n == min(int(np.prod(shape)), bench.DUMP_MAX_ELEMS), name
+        assert np.isfinite(a).all(), name
+        total_bytes += a.nbytes
+    assert total_bytes <= 64 << 20
+    assert line["dumped_outputs"]["logits"][0] == [16, 16000, 17]
+    assert abs(float(np.load(out / "total.npy")[0]) - line["loss"]) <= 1e-5 * max(1.0, abs(line["loss"]))
