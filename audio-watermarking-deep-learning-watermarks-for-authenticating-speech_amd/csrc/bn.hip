@@ -319,6 +319,26 @@ __global__ __launch_bounds__(256) void gscale_from_max_kernel(const float* __res
     }
 }
 
+// max |x| per row of x [rows][row_len] (row_len % 4 == 0): grid (G, rows), one atomic max per workgroup into out[row] (non-negative
+// floats compare as ints; out zeroed by the caller) -- the per-clip input scale of wm_gconv_h for activations
+__global__ __launch_bounds__(256) void absmax_rows_kernel(const float4* __restrict__ x, size_t row4, float* __restrict__ out) {
+    __shared__ float red[4];
+    const float4* r = x + (size_t)blockIdx.y * row4;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < row4; i += (size_t)gridDim.x * 256) {
+        const float4 v = stream_load(r + i);
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (m == m) atomicMax(reinterpret_cast<int*>(out) + blockIdx.y, __float_as_int(m));
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -414,6 +434,17 @@ int wm_gscale_absmax(const float* x, long long n, float* scratch, float log2_tar
     const size_t want = (n4 + 2047) / 2048;
     const int grid = (int)(want < 1 ? 1 : (want < 1024 ? want : 1024));
     hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), n4, scratch, log2_target, gscale);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// out[r] = max |x[r][:]| for x [rows][row_len] (row_len % 4 == 0, out zeroed by the caller; a NaN row leaves its entry as it was)
+int wm_absmax_rows(const float* x, int rows, long long row_len, float* out, hipStream_t stream) {
+    if (!x || !out || rows <= 0 || rows > 65535 || row_len <= 0 || (row_len & 3)) return (int)hipErrorInvalidValue;
+    const size_t row4 = (size_t)row_len / 4;
+    const size_t want = (row4 + 2047) / 2048;                         // >= eight float4 per thread
+    const int G = (int)(want < 1 ? 1 : (want < 64 ? want : 64));
+    hipLaunchKernelGGL(absmax_rows_kernel, dim3(G, rows), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), row4, out);
     WM_CHECK_LAUNCH();
     return 0;
 }

@@ -344,8 +344,8 @@ int launch_gconv2(GConvArgs a, hipStream_t stream) {
 //     coalesced over the wave's 32 rows: the weights never pass through LDS (L2 / L1 serve the re-use between tiles and waves).
 //   * input: a chunk's [16][XW] window is staged global -> registers -> LDS as a channel-minor image [position][16 channels] x {hi, lo}
 //     (pitch 24 halves), one chunk ahead of the matrix phase; a B fragment (one output position, 8 consecutive channels at one tap) is
-//     one aligned ds_read_b128 at row position * S + tap.  gscale (data gradients): the input is multiplied by gs before the split
-//     and clamped to the f16 range; the accumulators leave times 1 / (ws gs).
+//     one aligned ds_read_b128 at row position * S + tap.  gscale: the input is multiplied by gs before the split and clamped to the
+//     f16 range; the accumulators leave times 1 / (ws gs).  One gs for the launch (gradients) or one per clip (per_clip: activations).
 // Epilogue as gconv2_kernel's.
 // ---------------------------------------------------------------------------------------------------------------
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
@@ -357,6 +357,7 @@ struct GConvHArgs {
     const unsigned short* wph;      // [2 pieces][Cin / 16][K][Mtot][16] f16, then {ws, 1 / ws}
     const float* gscale;            // {gs, 1 / gs} or null
     float* ymax;                    // optional: max |y| over everything the launch stores (atomic max of non-negative floats as ints; zeroed by the caller)
+    int per_clip;                   // 1: gscale holds max |x| per clip ([NB]; gs derived here) and ymax receives one maximum per clip ([NB])
 };
 
 template <int MW, int WM, int WN, int XRH>   // XRH: staged window elements (channel pairs) per thread, 8 XW <= 256 XRH
@@ -374,8 +375,16 @@ __global__ __launch_bounds__(256) void gconvh_kernel(GConvHArgs ha) {
     const int nchunks = a.Cin >> 4;
     const size_t piece = (size_t)nchunks * K * a.Mtot * 16;                 // halves per weight piece
     const float* tail = reinterpret_cast<const float*>(ha.wph + 2 * piece);
-    const float gs = ha.gscale ? ha.gscale[0] : 1.f;
-    const float dinv = tail[1] * (ha.gscale ? ha.gscale[1] : 1.f);
+    float gs = 1.f, gsinv = 1.f;
+    if (ha.gscale && ha.per_clip) {                                        // the power of two that puts this clip's max |x| into (2^11, 2^12]
+        const float m = ha.gscale[nb];
+        if (m > 0.f && m < 3.0e38f) gs = fminf(fmaxf(exp2f(floorf(12.f - log2f(m))), 1.0e-30f), 1.0e30f);
+        gsinv = 1.f / gs;
+    } else if (ha.gscale) {
+        gs = ha.gscale[0];
+        gsinv = ha.gscale[1];
+    }
+    const float dinv = tail[1] * gsinv;
 
     // ---- staging map: element i of a thread = (channel pair cp, window position j): idx = tid + 256 i = cp * XW + j
     const int nx = (8 * XW + 255) >> 8;
@@ -578,7 +587,7 @@ __global__ __launch_bounds__(256) void gconvh_kernel(GConvHArgs ha) {
     if (ha.ymax) {                                   // the next consumer's gradient scale without a pass over y
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        if (lane == 0 && vmax == vmax && vmax < 3.0e38f) atomicMax(reinterpret_cast<int*>(ha.ymax), __float_as_int(vmax));
+        if (lane == 0 && vmax == vmax && vmax < 3.0e38f) atomicMax(reinterpret_cast<int*>(ha.ymax) + (ha.per_clip ? nb : 0), __float_as_int(vmax));
     }
 }
 
@@ -1251,11 +1260,12 @@ int wm_gconv(const float* x, const float* wp, const float* bias, const float* ve
 }
 
 // wm_gconv on the f16 two-piece split: wph = wm_gconv_pack_h's image of the SAME wp; Cin % 16 == 0 (and Cin1 % 16 == 0 with two sources);
-// gscale = {gs, 1 / gs} for a gradient input (wm_gscale_absmax), NULL for activations.  hipErrorInvalidValue when the shape is outside
-// the kernel's window limits (the caller then uses wm_gconv).
+// gscale = {gs, 1 / gs} for the input (wm_gscale_absmax), or max |x| per clip with per_clip (a producer's ymax, wm_absmax_rows), NULL:
+// split unscaled.
+// hipErrorInvalidValue when the shape is outside the kernel's window limits (the caller then uses wm_gconv).
 int wm_gconv_h(const float* x, const void* wph, const float* bias, const float* vec, const float* res, float* y, int NB,
                int Cin, int Lin, int K, int S, int P, int Mtot, int Nout, int st, int shp, int Cout, int Lout, int act,
-               const float* x2, int Cin1, int nph, const float* gscale, float* ymax, hipStream_t stream) {
+               const float* x2, int Cin1, int nph, const float* gscale, float* ymax, int per_clip, hipStream_t stream) {
     if (NB <= 0 || Cin <= 0 || (Cin & 15) || K <= 0 || K > 16 || S <= 0 || S > 8 || Mtot <= 0 || Nout <= 0 || st < 1 || st > 8 || Lin <= 0 ||
         Lin >= (1 << 24) || NB > 65535 || Mtot >= 8192 || !wph)
         return (int)hipErrorInvalidValue;
@@ -1263,7 +1273,7 @@ int wm_gconv_h(const float* x, const void* wph, const float* bias, const float* 
     if (nph > st || (x2 && (Cin1 <= 0 || Cin1 >= Cin || (Cin1 & 15)))) return (int)hipErrorInvalidValue;
     GConvHArgs ha{GConvArgs{x, nullptr, bias, vec, res, y, NB, Cin, Lin, K, S, P, Mtot, Nout, st, shp, Cout, Lout, act, 0, 0, x2,
                             x2 ? Cin1 : Cin, nph},
-                  reinterpret_cast<const unsigned short*>(wph), gscale, ymax};
+                  reinterpret_cast<const unsigned short*>(wph), gscale, ymax, per_clip ? 1 : 0};
     int rc;
     if (Nout <= 64) rc = Mtot > 64 ? launch_gconvh<2, 2, 1>(ha, stream) : launch_gconvh<2, 1, 1>(ha, stream);
     else if (Mtot > 64) rc = launch_gconvh<2, 2, 2>(ha, stream);

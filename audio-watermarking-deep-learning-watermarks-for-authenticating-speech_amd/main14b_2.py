@@ -32,7 +32,8 @@ _GCONV = {"f16x3": _os0.environ.get("WM_GCONV_F16X3", "1") == "1"}
 
 def set_gconv_f16x3(on: bool):
     """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
-    two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled from max |w|, a gradient input from max |g|), 0 native fp32
+    two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
+    per clip), 0 native fp32
     MFMA.  WM_GCONV_F16X3=0/1 sets the default."""
     _GCONV["f16x3"] = bool(on)
 
@@ -51,26 +52,29 @@ def _pack_h_conv(w, mode):
 
 
 def _gconv_raw(x, wp, bias, K, S, P, Mtot, Nout, st, shp, Cout, Lout, act=0, res=None, vec=None, x2=None, nph=0, out=None, grad_in=False,
-               wph=None):
+               wph=None, allow_h=True):
     NB, Cin, Lin = x.shape
     y = _f32(NB, Cout, Lout, device=x.device) if out is None else out
     Cin_tot = Cin + (x2.shape[1] if x2 is not None else 0)
-    if wph is not None or (_GCONV["f16x3"] and Cin % 16 == 0 and Cin_tot % 16 == 0 and ops.conv_bf16x6()):
+    if wph is not None or (allow_h and _GCONV["f16x3"] and Cin % 16 == 0 and Cin_tot % 16 == 0 and ops.conv_bf16x6()):
         if wph is None:
             wph = torch.empty(2 * Cin_tot * K * Mtot + 4, dtype=torch.int16, device=x.device)
             lib.wm_gconv_pack_h(_p(wp), _p(wph), None, Cin_tot, K, Mtot, _stream())   # fixed scale 2^8: one launch per weight image
-        gsc = ymax = None
         if grad_in:
+            per_clip = 0
             gsc = ops.gscale_of(x)                   # the producer's maximum when it left one (below), else one pass over x
             if x2 is not None:                       # one scale for both gradient sources: the smaller of the two
                 g2 = ops.gscale_of(x2)
                 gsc = torch.stack([torch.minimum(gsc[0], g2[0]), torch.maximum(gsc[1], g2[1])])
-            if out is None:                          # y is a gradient too: leave max |y| for its consumer (a fresh y: every element is stored)
-                ymax = torch.zeros(1, dtype=torch.float32, device=x.device)
+        else:                                        # activations: a power-of-two scale per clip from max |x| (no normalisation layer bounds them)
+            per_clip = 1
+            gsc = ops.amax_per_clip(x)
+        # a fresh y (every element is stored): leave max |y| (per clip for activations) for its consumer
+        ymax = ops.zeroed_slots(NB if per_clip else 1, x.device) if out is None else None
         lib.wm_gconv_h(_p(x), _p(wph), _p(bias), _p(vec), _p(res), _p(y), NB, Cin_tot, Lin, K, S, P, Mtot, Nout, st, shp, Cout, Lout, act,
-                       _p(x2), Cin if x2 is not None else 0, nph, _p(gsc), _p(ymax), _stream())
+                       _p(x2), Cin if x2 is not None else 0, nph, _p(gsc), _p(ymax), per_clip, _stream())
         if ymax is not None:
-            ops._note_gmax(y, ymax)
+            ops._note_gmax(y, ymax, per_clip=bool(per_clip))
         return y
     lib.wm_gconv(_p(x), _p(wp), _p(bias), _p(vec), _p(res), _p(y), NB, Cin_tot, Lin, K, S, P, Mtot, Nout, st, shp, Cout, Lout, act,
                  _p(x2), Cin if x2 is not None else 0, nph, _stream())
@@ -312,6 +316,13 @@ class RowsGatherFn(torch.autograd.Function):
         return dt, None
 
 
+def _lstm_proj(seq, w_ih, bias):
+    """input projection of an LSTM layer over all steps, [T][H][B] -> [T][4H][B]: native fp32 MFMA -- on the f16 split the clips of
+    the launch would be time steps, and a per-step input scale would make a clip's result depend on the rest of the batch"""
+    T, H, B = seq.shape
+    return _gconv_raw(seq, w_ih.t().contiguous(), bias, 1, 1, 0, 4 * H, B, 1, 0, 4 * H, B, allow_h=False)
+
+
 class LSTMLayerFn(ops.GradAwareFunction):
     """one layer of nn.LSTM(H, H) on a time-major sequence [T][H][B] (zero initial state): the input projection of all steps
     is one GEMM, the recurrence a chain of T per-step launches issued by the C launcher (wm_lstm_seq_fwd / _bwd)"""
@@ -322,7 +333,7 @@ class LSTMLayerFn(ops.GradAwareFunction):
         T, H, B = seq.shape
         dev, st = seq.device, _stream()
         bias = (b_ih + b_hh).contiguous()
-        xp = _gconv_raw(seq, w_ih.t().contiguous(), bias, 1, 1, 0, 4 * H, B, 1, 0, 4 * H, B)     # [T][4H][B]
+        xp = _lstm_proj(seq, w_ih, bias)                                                     # [T][4H][B]
         need = ops.wants_grad(ctx)
         hs = _f32(T + 1, H, B, device=dev)           # hs[t+1] = h_t, hs[0] = 0 (so hs[:T] is the h_{t-1} sequence)
         cs = _f32(T + 1, H, B, device=dev)

@@ -244,25 +244,59 @@ def pack_w64_h7(w: torch.Tensor, mode: int) -> torch.Tensor:
 
 
 # max |g| per producer workgroup of gradient tensors whose producer formed it anyway, keyed by the tensor OBJECT (a weak reference
-# guards against a recycled id): a hit saves the consumer's streaming pass over g, a miss is merely slower
+# guards against a recycled id) and its version counter: a hit saves the consumer's streaming pass over g, a miss is merely slower.
+# The version matters: autograd sums the gradients of a tensor with several consumers IN PLACE into the first one that arrived, after
+# its producer noted the maximum -- a bumped version means the noted maximum no longer describes the tensor.
 _GMAX = {}
 
 
-def _note_gmax(t: torch.Tensor, maxes: torch.Tensor):
+def _note_gmax(t: torch.Tensor, maxes: torch.Tensor, per_clip: bool = False):
+    """maxes: max |t| of everything the producer stored, as one or more partial maxima (per_clip: one per clip, t.shape[0] of them)"""
     import weakref
-    if len(_GMAX) > 64:
+    if len(_GMAX) > 256:
         _GMAX.clear()
-    _GMAX[id(t)] = (weakref.ref(t), maxes)
+    _GMAX[id(t)] = (weakref.ref(t), t._version, maxes, per_clip)
+
+
+def _noted(t: torch.Tensor, pop: bool):
+    e = _GMAX.pop(id(t), None) if pop else _GMAX.get(id(t))
+    return e if e is not None and e[0]() is t and e[1] == t._version else None
 
 
 def gscale_of(g: torch.Tensor, log2_target: float = 12.0) -> torch.Tensor:
-    """{gs, 1 / gs} for gradient g: from its producer's per-workgroup maxima when it left them (no pass over g), else wm_gscale_absmax"""
-    e = _GMAX.pop(id(g), None)
-    if e is not None and e[0]() is g:
+    """{gs, 1 / gs} for gradient g: from its producer's maxima when it left them (no pass over g), else wm_gscale_absmax"""
+    e = _noted(g, pop=True)
+    if e is not None:
         gsc = _f32(2, device=g.device)
-        lib.wm_gscale_from_max(_p(e[1]), e[1].numel(), float(log2_target), _p(gsc), _stream())
+        lib.wm_gscale_from_max(_p(e[2]), e[2].numel(), float(log2_target), _p(gsc), _stream())
         return gsc
     return gscale_absmax(g, log2_target)
+
+
+_ZPOOL = {"buf": None, "used": 0}
+
+
+def zeroed_slots(n: int, device) -> torch.Tensor:
+    """n zero floats for a launch's atomic-max output: slices of a pool zeroed once and never handed out twice (no fill launch per layer)"""
+    p = _ZPOOL
+    if p["buf"] is None or p["buf"].device != torch.device(device) or p["used"] + n > p["buf"].numel():
+        p["buf"], p["used"] = torch.zeros(max(1 << 16, n), dtype=torch.float32, device=device), 0
+    s = p["buf"][p["used"]:p["used"] + n]
+    p["used"] += n
+    return s
+
+
+def amax_per_clip(x: torch.Tensor) -> torch.Tensor:
+    """max |x| per clip of activation x [NB][...] -- the per-clip input scale of wm_gconv_h (per_clip = 1): the maxima its producer left
+    (the producing wm_gconv_h's ymax), else one pass over x.  Per clip, so that a clip's result never depends on the rest of the batch."""
+    e = _noted(x, pop=False)
+    if e is not None and e[3]:
+        return e[2]
+    NB = x.shape[0]
+    m = zeroed_slots(NB, x.device)
+    lib.wm_absmax_rows(_p(x), NB, x.numel() // NB, _p(m), _stream())
+    _note_gmax(x, m, per_clip=True)              # kept for the next consumer of the same x (a block's conv1 and skip conv)
+    return m
 
 
 def gscale_absmax(g: torch.Tensor, log2_target: float = 12.0) -> torch.Tensor:

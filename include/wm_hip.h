@@ -122,6 +122,9 @@ int wm_pack_w64_h7(const float* w, void* wph, int mode, wm_stream_t stream);    
 int wm_gscale_absmax(const float* x, long long n, float* scratch, float log2_target, float* gscale, wm_stream_t stream);
 /* the same from per-workgroup maxima a producer already wrote (wm_dwgrad64_bf's dzmax, epi 1 / 2 / 8): no pass over the tensor */
 int wm_gscale_from_max(const float* maxes, int n, float log2_target, float* gscale, wm_stream_t stream);
+/* out[r] = max |x[r][:]| for x [rows][row_len] (row_len % 4 == 0; out zeroed by the caller, atomic max): the per-clip input maxima of
+ * wm_gconv_h (per_clip = 1) for an activation whose producer left none */
+int wm_absmax_rows(const float* x, int rows, long long row_len, float* out, wm_stream_t stream);
 
 /* weight gradient of that ConvTranspose1d (= wm_wgrad64 with KW 7, gpro 0, layout 1): dw [in][out][7], dbias [64];
  * xpro 0 | 2 (x + vec[b*64+c]); partial: >= 256 * (7*4096 + 64) floats. */
@@ -260,13 +263,16 @@ int wm_gconv(const float* x, const float* wp, const float* bias, const float* ve
              const float* x2, int Cin1, int nph, wm_stream_t stream);
 /* wm_gconv on the f16 two-piece split (three f16 piece products per product on v_mfma_f32_32x32x16_f16, fp32 accumulate, fp32-grade):
  * same arguments with wph = wm_gconv_pack_h's image of the SAME wp instead of wp; needs Cin % 16 == 0 (and Cin1 % 16 == 0 with a second
- * source).  gscale = {gs, 1 / gs} (wm_gscale_absmax) when x is a gradient -- it is multiplied by gs before the split and clamped to
- * +-6e4 --, NULL for activations (split unscaled). */
+ * source).  gscale = {gs, 1 / gs} (wm_gscale_absmax) -- x is multiplied by gs before the split and clamped to +-6e4 --, NULL: split
+ * unscaled. */
 int wm_gconv_h(const float* x, const void* wph, const float* bias, const float* vec, const float* res, float* y, int NB,
                int Cin, int Lin, int K, int S, int P, int Mtot, int Nout, int st, int shp, int Cout, int Lout, int act,
-               const float* x2, int Cin1, int nph, const float* gscale, float* ymax, wm_stream_t stream);
+               const float* x2, int Cin1, int nph, const float* gscale, float* ymax, int per_clip, wm_stream_t stream);
 /* ymax (optional, ONE float zeroed by the caller): receives max |y| over everything the launch stores (atomic max) -- the gradient scale
- * of whatever consumes y next comes from wm_gscale_from_max(ymax, 1, ...) instead of a pass over y */
+ * of whatever consumes y next comes from wm_gscale_from_max(ymax, 1, ...) instead of a pass over y.
+ * per_clip = 1: gscale holds max |x| per clip ([NB]: a producer's ymax, or wm_absmax_rows) and the kernel splits clip nb times the power
+ * of two that puts it into (2^11, 2^12]; ymax receives one maximum per clip ([NB] floats zeroed by the caller) -- activations: an
+ * unscaled split loses the lo piece below |x| ~ 2^-3 (f16 subnormals) and saturates above 6e4 */
 /* wph: 2 * Cin * K * Mtot f16 ([piece][Cin / 16][K][Mtot][16]: w * ws) followed by {ws, 1 / ws} as two floats.  scratch (>= 1024 floats):
  * ws = the power of two with max |w| ws in (2^9, 2^10] (a pass over wp); scratch NULL: ws = 2^8 fixed, one launch -- what the host mirror
  * uses: the scale only has to keep the two pieces inside the f16 range, which 2^8 does for max |w| between 4e-6 and 250 */
