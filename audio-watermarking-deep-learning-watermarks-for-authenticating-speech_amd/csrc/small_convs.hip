@@ -1,7 +1,7 @@
 // The thin ends of the two networks (py/main16.py):
 //   stem   Conv1d(1,64,7,padding=3)   Generator.encoder[0] :134 / Detector.model[0] :177
 //   head1  Conv1d(64,1,1)             Generator.decoder[2] :146
-//   head17 Conv1d(64,1+bits,1)        Detector.model[3]    :180, written directly in the
+//   headN  Conv1d(64,1+bits,1)        Detector.model[3]    :180, bits 0..63, written directly in the
 //                                     (B,T,1+bits) layout Detector.forward returns (:186)
 // These are HBM-bound (one 64-channel frame in or out per sample, a handful of FLOPs per
 // byte) so they are plain VALU kernels with 16-B coalesced frame accesses; only the tiny
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void head1_bwd_kernel(const float* __restrict_
         partial[(size_t)blockIdx.x * 65 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// ------------------------------------------------------------------------------------ head17
+// ------------------------------------------------------------------------------------ headN
 // logits[b,t,o] = bias[o] + sum_c w[o][c] x[b,c,t]     NO = 1 + message_bits (<= 17)
 template <int NO>
 __global__ __launch_bounds__(256) void headN_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -310,30 +310,77 @@ __global__ __launch_bounds__(256) void headN_fwd_kernel(const float* __restrict_
     for (int i = threadIdx.x; i < nvalid; i += 256) yb[i] = os[i];
 }
 
+// i / d for 0 <= i <= 2^14 and 2 <= d <= 64, with magic = ceil(2^32 / d): the error i * (magic - 2^32/d) / 2^32 < 2^-18 stays
+// below the 1/d gap between i/d and the next integer
+__device__ __forceinline__ int div_small(int i, unsigned magic) { return (int)__umulhi((unsigned)i, magic); }
+
+// The same computation at a run-time width 2 <= no <= 64 (1 and 17 take the exact-width instantiations above).  The loop over
+// outputs is not unrolled or software-pipelined: either keeps more weights live than there are scalar registers and spills.  The
+// staging rows get the odd stride no | 1: a row stride of 32 or 64 floats would put every lane's store on one bank.
+__global__ __launch_bounds__(256) void headN_fwd_any_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, float* __restrict__ y, int T,
+                                                            int no, unsigned magic) {
+    extern __shared__ float os[];                                // [256][no | 1]
+    const int OS = no | 1;
+    const int tilesPerClip = (T + 255) / 256;
+    const int b = blockIdx.x / tilesPerClip, t0 = (blockIdx.x % tilesPerClip) * 256;
+    const int t = min(t0 + (int)threadIdx.x, T - 1);
+    const float* xb = x + (size_t)b * 64 * T + t;
+    float v[64];
+#pragma unroll
+    for (int c = 0; c < 64; ++c) v[c] = xb[(size_t)c * T];
+#pragma unroll 1
+    for (int o = 0; o < no; ++o) {
+        const float* wo = w + o * 64;                            // uniform address: scalar loads
+        __builtin_amdgcn_sched_barrier(0);                      // keep the next output's 64 weights from being hoisted
+        float a0 = bias[o], a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 64; c += 4) {
+            a0 = fmaf(wo[c], v[c], a0); a1 = fmaf(wo[c + 1], v[c + 1], a1);
+            a2 = fmaf(wo[c + 2], v[c + 2], a2); a3 = fmaf(wo[c + 3], v[c + 3], a3);
+        }
+        os[threadIdx.x * OS + o] = (a0 + a1) + (a2 + a3);
+    }
+    __syncthreads();
+    const int nvalid = min(256, T - t0) * no;
+    float* yb = y + ((size_t)b * T + t0) * no;
+    for (int i = threadIdx.x; i < nvalid; i += 256) {
+        const int r = div_small(i, magic);
+        yb[i] = os[r * OS + (i - r * no)];
+    }
+}
+
 // g [B,T,NO] -> dx[b,c,t] = sum_o w[o][c] g[b,t,o];  dw[o][c] = sum g[b,t,o] x[b,c,t];  db[o] = sum g
 // Both products run on the fp32 matrix cores (the VALU/LDS version spent 11.5 ms per step at B=256):
-//   dx: M = channel (2 tiles), N = time (the wave's 64 steps), K = output index padded to 18
-//   dw: M = output index padded to 32, N = channel (2 tiles), K = time; accumulators persist over tiles
+//   dx: M = channel (2 tiles), N = time (the wave's 64 steps), K = output index padded to even
+//   dw: M = output index padded to 32*NT (NT tiles), N = channel (2 tiles), K = time; accumulators persist over tiles
+// NOC > 0: the width is a compile-time constant (1 and 17: the 0- and 16-bit models, NT = 1).  NOC == 0: any width
+// 2 <= no <= 32*NT, given at run time with magic = ceil(2^32 / no) for the tile scatter.
 // partial[block][NO*64 + NO]
-template <int NO>
+template <int NOC, int NT>
 __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                         const float* __restrict__ w, float* __restrict__ dx,
-                                                        float* __restrict__ partial, int B, int T) {
-    constexpr int XS = 257, GS = 33, KS = (NO + 1) / 2;
+                                                        float* __restrict__ partial, int B, int T, int no, unsigned magic) {
+    constexpr int XS = 257, OB = 32 * NT, GS = OB + 1;
+    constexpr int NOMAX = NOC > 0 ? NOC : OB;
+    const int NO = NOC > 0 ? NOC : no;
+    const int KS = (NO + 1) / 2;                 // k-steps of the dx product
     extern __shared__ __align__(16) float smem[];
     float* xs = smem;                  // [64][XS]
     float* gsm = xs + 64 * XS;         // [256][GS], columns >= NO are zero
-    float* ws = gsm + 256 * GS;        // [32][64],  rows >= NO are zero
+    float* ws = gsm + 256 * GS;        // [OB][64],  rows >= NO are zero
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    for (int i = tid; i < 32 * 64; i += 256) ws[i] = (i < NO * 64) ? w[i] : 0.f;
+    for (int i = tid; i < OB * 64; i += 256) ws[i] = (i < NO * 64) ? w[i] : 0.f;
     for (int i = tid; i < 256 * GS; i += 256) gsm[i] = 0.f;
     const int tilesPerClip = (T + 255) / 256, ntiles = B * tilesPerClip;
-    f32x16 accw[2];
+    f32x16 accw[NT][2];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { accw[0][r] = 0.f; accw[1][r] = 0.f; }
+    for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { accw[mt][0][r] = 0.f; accw[mt][1][r] = 0.f; }
     float accb = 0.f;
     // next tile is fetched into registers (16-B loads, clamped addresses, no branches) while this one is processed
-    constexpr int NG4 = (256 * NO + 3) / 4, NGV = (NG4 + 255) / 256;
+    constexpr int NG4 = (256 * NOMAX + 3) / 4, NGV = (NG4 + 255) / 256;
     float4 sx[16], sgv[NGV];
     // piece p of the staging: 0..15 x rows, 16.. the g tile.  The main loop issues one piece per k-step of the dw product
     // (an 81-KB burst would block the wave at issue, see conv64bf3_kernel)
@@ -372,7 +419,11 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int i = 4 * f + j;
-                    if (i < 256 * NO) gsm[(i / NO) * GS + (i % NO)] = (i < nt * NO) ? e[j] : 0.f;
+                    if (i < 256 * NO) {
+                        const float val = (i < nt * NO) ? e[j] : 0.f;
+                        if constexpr (NOC > 0) gsm[(i / NO) * GS + (i % NO)] = val;
+                        else { const int r = div_small(i, magic); gsm[r * GS + (i - r * NO)] = val; }
+                    }
                 }
             }
         }
@@ -396,11 +447,13 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[mt][n2][r] = 0.f;
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const float a0 = ws[(2 * s + half) * 64 + l31], a1 = ws[(2 * s + half) * 64 + 32 + l31];
-                const float b0 = gsm[(wave * 64 + l31) * GS + 2 * s + half], b1 = gsm[(wave * 64 + 32 + l31) * GS + 2 * s + half];
-                acc[0][0] = mfma32(a0, b0, acc[0][0]); acc[0][1] = mfma32(a0, b1, acc[0][1]);
-                acc[1][0] = mfma32(a1, b0, acc[1][0]); acc[1][1] = mfma32(a1, b1, acc[1][1]);
+            for (int s = 0; s < (NOMAX + 1) / 2; ++s) {
+                if (s < KS) {                      // always true at a compile-time width
+                    const float a0 = ws[(2 * s + half) * 64 + l31], a1 = ws[(2 * s + half) * 64 + 32 + l31];
+                    const float b0 = gsm[(wave * 64 + l31) * GS + 2 * s + half], b1 = gsm[(wave * 64 + 32 + l31) * GS + 2 * s + half];
+                    acc[0][0] = mfma32(a0, b0, acc[0][0]); acc[0][1] = mfma32(a0, b1, acc[0][1]);
+                    acc[1][0] = mfma32(a1, b0, acc[1][0]); acc[1][1] = mfma32(a1, b1, acc[1][1]);
+                }
             }
             float* dxb = dx + (size_t)b * 64 * T + t0;
 #pragma unroll
@@ -420,15 +473,18 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
 #pragma unroll
             for (int s = 0; s < 32; ++s) {
                 if (s < 16 + NGV) load_piece(nextc, s);
-                const float a = ap[2 * s * GS];
-                accw[0] = mfma32(a, bp[2 * s], accw[0]);
-                accw[1] = mfma32(a, bp[32 * XS + 2 * s], accw[1]);
+#pragma unroll
+                for (int mt = 0; mt < NT; ++mt) {
+                    const float a = ap[2 * s * GS + mt * 32];
+                    accw[mt][0] = mfma32(a, bp[2 * s], accw[mt][0]);
+                    accw[mt][1] = mfma32(a, bp[32 * XS + 2 * s], accw[mt][1]);
+                }
             }
         }
-        if (tid < 8 * 32 && (tid & 31) < NO) {          // bias sums: output tid & 31, 32-step segment tid >> 5 (8 short loops, not one long one)
-            const float* gp = gsm + (tid >> 5) * 32 * GS + (tid & 31);
+        if ((tid & (OB - 1)) < NO) {       // bias sums: output tid % OB, OB-step segment tid / OB (short loops, not one long one)
+            const float* gp = gsm + (tid / OB) * OB * GS + (tid & (OB - 1));
 #pragma unroll 8
-            for (int tt = 0; tt < 32; ++tt) accb += gp[tt * GS];
+            for (int tt = 0; tt < OB; ++tt) accb += gp[tt * GS];
         }
         __syncthreads();
         if (next < ntiles) write_tile(next);
@@ -437,27 +493,33 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
     }
     // fixed-order reduction of the four waves' dw tiles through LDS
     __syncthreads();
-    float* red = xs;     // [32][64]
+    float* red = xs;     // [OB][64]
     for (int wv = 0; wv < 4; ++wv) {
         if (wave == wv) {
 #pragma unroll
-            for (int n2 = 0; n2 < 2; ++n2)
+            for (int mt = 0; mt < NT; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int o = mfma_row(r, half), c = n2 * 32 + l31;
-                    red[o * 64 + c] = (wv == 0) ? accw[n2][r] : red[o * 64 + c] + accw[n2][r];
-                }
+                for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int o = mt * 32 + mfma_row(r, half), c = n2 * 32 + l31;
+                        red[o * 64 + c] = (wv == 0) ? accw[mt][n2][r] : red[o * 64 + c] + accw[mt][n2][r];
+                    }
         }
         __syncthreads();
     }
     float* out = partial + (size_t)blockIdx.x * (NO * 64 + NO);
     for (int i = tid; i < NO * 64; i += 256) out[i] = red[i];
     __syncthreads();
-    red[tid] = ((tid & 31) < NO) ? accb : 0.f;          // [8 segments][32]
+    red[tid] = ((tid & (OB - 1)) < NO) ? accb : 0.f;          // [256 / OB segments][OB]
     __syncthreads();
-    if (tid < NO)
-        out[NO * 64 + tid] = ((red[tid] + red[32 + tid]) + (red[64 + tid] + red[96 + tid])) +
-                             ((red[128 + tid] + red[160 + tid]) + (red[192 + tid] + red[224 + tid]));
+    if (tid < NO) {
+        if constexpr (NT == 1)
+            out[NO * 64 + tid] = ((red[tid] + red[32 + tid]) + (red[64 + tid] + red[96 + tid])) +
+                                 ((red[128 + tid] + red[160 + tid]) + (red[192 + tid] + red[224 + tid]));
+        else
+            out[NO * 64 + tid] = (red[tid] + red[64 + tid]) + (red[128 + tid] + red[192 + tid]);
+    }
 }
 
 }  // namespace
@@ -519,31 +581,60 @@ int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, floa
     return 0;
 }
 
+// NO = 1 + message_bits, 1 <= NO <= 64 (message ids are int64: at most 63 bits).  1 and 17 run exact-width instantiations.
 int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, hipStream_t stream) {
+    if (NO < 1 || NO > 64) return (int)hipErrorInvalidValue;
     const int grid = B * ((T + 255) / 256);
     if (NO == 17) hipLaunchKernelGGL(headN_fwd_kernel<17>, dim3(grid), dim3(256), 0, stream, x, w, bias, y, T);
     else if (NO == 1) hipLaunchKernelGGL(headN_fwd_kernel<1>, dim3(grid), dim3(256), 0, stream, x, w, bias, y, T);
-    else return (int)hipErrorInvalidValue;
+    else {
+        const size_t lds = (size_t)256 * (NO | 1) * sizeof(float);
+        static wm::DevOnce done;
+        if (!wm::dev_done(done)) {
+            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_fwd_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 65 * (int)sizeof(float)));
+            wm::dev_mark(done);
+        }
+        const unsigned magic = (unsigned)((0x100000000ull + NO - 1) / NO);
+        hipLaunchKernelGGL(headN_fwd_any_kernel, dim3(grid), dim3(256), lds, stream, x, w, bias, y, T, NO, magic);
+    }
     WM_CHECK_LAUNCH();
     return 0;
 }
 
-// partial: >= 256*(NO*64+NO) floats
+}  // extern "C"
+
+namespace {
+// NOC, NT: see headN_bwd_kernel.  LDS: x tile [64][257], g tile [256][32*NT+1], weights [32*NT][64] -- 145.25 KB at NT = 2
+template <int NOC, int NT>
+int launch_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, int grid, int B, int T, int NO,
+                     hipStream_t stream) {
+    constexpr size_t lds = (size_t)(64 * 257 + 256 * (32 * NT + 1) + 32 * NT * 64) * sizeof(float);
+    static wm::DevOnce done;
+    if (!wm::dev_done(done)) {
+        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<NOC, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        wm::dev_mark(done);
+    }
+    const unsigned magic = NO > 1 ? (unsigned)((0x100000000ull + NO - 1) / NO) : 0u;
+    hipLaunchKernelGGL((headN_bwd_kernel<NOC, NT>), dim3(grid), dim3(256), lds, stream, g, x, w, dx, partial, B, T, NO, magic);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// partial: >= 256*(NO*64+NO) floats (one row per workgroup, at most one workgroup per CU)
 int wm_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int NO, int accumulate, hipStream_t stream) {
+    if (NO < 1 || NO > 64) return (int)hipErrorInvalidValue;
     const int ntiles = B * ((T + 255) / 256);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    const size_t lds = (size_t)(64 * 257 + 256 * 33 + 32 * 64) * sizeof(float);
-    if (NO == 17) {
-        static wm::DevOnce done;
-        if (!wm::dev_done(done)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<17>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); wm::dev_mark(done); }
-        hipLaunchKernelGGL(headN_bwd_kernel<17>, dim3(grid), dim3(256), lds, stream, g, x, w, dx, partial, B, T);
-    } else if (NO == 1) {
-        static wm::DevOnce done;
-        if (!wm::dev_done(done)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); wm::dev_mark(done); }
-        hipLaunchKernelGGL(headN_bwd_kernel<1>, dim3(grid), dim3(256), lds, stream, g, x, w, dx, partial, B, T);
-    } else return (int)hipErrorInvalidValue;
-    WM_CHECK_LAUNCH();
+    int rc;
+    if (NO == 17) rc = launch_headN_bwd<17, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
+    else if (NO == 1) rc = launch_headN_bwd<1, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
+    else if (NO <= 32) rc = launch_headN_bwd<0, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
+    else rc = launch_headN_bwd<0, 2>(g, x, w, dx, partial, grid, B, T, NO, stream);
+    if (rc) return rc;
     const int n = NO * 64 + NO;
     // partial rows are [NO*64 weights | NO biases]; reduce the two pieces with matching row stride
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((NO * 64 + 63) / 64), dim3(256), 0, stream, (const float*)partial, grid, n, NO * 64, dw, accumulate);

@@ -603,8 +603,9 @@ class HeadNFn(torch.autograd.Function):
         x = _frames(x, "head input", 64)
         B, _, T = x.shape
         NO = w.shape[0]
-        if NO not in (1, 17):
-            raise ValueError(f"Detector head: 1+message_bits must be 1 or 17, got {NO}")
+        if not 1 <= NO <= 64:
+            raise ValueError(f"Detector head: 1+message_bits must be in 1..64 (message ids are int64, so a message "
+                             f"carries at most 63 bits), got {NO}")
         y = _f32(B, T, NO, device=x.device)
         lib.wm_headN_fwd(_p(x), _p(w), _p(b), _p(y), B, T, NO, _stream())
         ctx.save_for_backward(x, w)

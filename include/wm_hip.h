@@ -178,7 +178,8 @@ int wm_stem_bwd(const float* g, const float* s, const float* w, float* ds, float
 int wm_head1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, wm_stream_t stream);
 int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int accumulate, wm_stream_t stream);
-/* logits written as (B,T,NO) contiguous -- the layout Detector.forward's permuted view exposes */
+/* logits written as (B,T,NO) contiguous -- the layout Detector.forward's permuted view exposes.  NO = 1 + message_bits,
+ * 1 <= NO <= 64 (message ids are int64, so at most 63 bits); T % 4 == 0.  headN_bwd: partial >= 256*(NO*64+NO) floats. */
 int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, wm_stream_t stream);
 int wm_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int NO, int accumulate, wm_stream_t stream);
