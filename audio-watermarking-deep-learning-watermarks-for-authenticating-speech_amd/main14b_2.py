@@ -19,25 +19,14 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import lib
-from .ops import _f32, _p, _stream
+from .ops import _GCONV, _f32, _p, _stream, set_gconv_f16x3      # this module's two switches are rows of ops.SWITCHES too
+from .step import _train_step
 
 CHANNELS, HIDDEN_DIM, NUM_BITS, OUTPUT_CH = 32, 32, 16, 128     # py/main14b_2.py:43-46
 STRIDES = [2, 4, 5, 8]                                          # :47
 
 
 # ------------------------------------------------------------------------------------------ raw launches
-import os as _os0
-_GCONV = {"f16x3": _os0.environ.get("WM_GCONV_F16X3", "1") == "1"}
-
-
-def set_gconv_f16x3(on: bool):
-    """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
-    two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
-    per clip), 0 native fp32
-    MFMA.  WM_GCONV_F16X3=0/1 sets the default."""
-    _GCONV["f16x3"] = bool(on)
-
-
 def _h_ok(cin):
     """the f16 two-piece build of the generic convolution takes this layer (GEMM channel count a multiple of 16)"""
     return _GCONV["f16x3"] and cin % 16 == 0 and ops.conv_bf16x6()
@@ -147,8 +136,7 @@ def _strided_block_dgrad(gz1, w1, gz2, ws, stride, Lin):
     return _gconv_raw(gz1, wp, None, 1, 1, 0, Cin * K, Lo, stride, 1, Cin, Lin, 0, None, None, gz2, K, dx, grad_in=True)
 
 
-import os as _os
-_FUSED_STRIDED_DGRAD = _os.environ.get("WM_FUSED_STRIDED_DGRAD", "1") == "1"      # A/B knob
+ops.bind_store("main14b_2", globals())          # _FUSED_STRIDED_DGRAD (WM_FUSED_STRIDED_DGRAD=0/1, an A/B knob): a global of this module
 _PLAN = {}
 
 
@@ -301,7 +289,7 @@ class RowsGatherFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, idx):
-        if ops._CHECK_INDEX["mode"] != "off":                  # nn.Embedding raises IndexError (py/main14b_2.py:160)
+        if ops.index_check() != "off":               # nn.Embedding raises IndexError (py/main14b_2.py:160)
             ops._note_index_error(((idx < 0) | (idx >= table.shape[0])).any().to(torch.int32).reshape(1), table.shape[0])
             idx = idx.clamp(0, table.shape[0] - 1)              # keep the gather in range whatever the mode reports later
         ctx.save_for_backward(idx)
@@ -560,20 +548,4 @@ def forward_losses(generator, detector, s, message):
 
 
 def train_step(generator, detector, optimizer, s, message, grad_sync=None):
-    optimizer.zero_grad(set_to_none=not hasattr(optimizer, "flat"))
-    if hasattr(grad_sync, "begin_step"):
-        grad_sync.begin_step()
-    try:
-        with ops.index_check_mode("deferred" if ops._CHECK_INDEX["mode"] == "sync" else ops._CHECK_INDEX["mode"]):
-            total, out = forward_losses(generator, detector, s, message)   # no mid-step sync (it would drain the launch queue)
-        total.backward()
-        if hasattr(optimizer, "finish_backward"):
-            optimizer.finish_backward()
-        if grad_sync is not None:
-            grad_sync()
-        ops.check_message_ids(wait=True, what="this train_step's batch")    # a bad id raises before the update (step.train_step)
-    except BaseException:
-        ops.drop_pending_message_checks()        # a step that died half-way must not report its flag inside a later, valid step
-        raise
-    optimizer.step()
-    return out
+    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync)

@@ -31,10 +31,7 @@ class ResBlock(nn.Module):
         self.relu = nn.ReLU()
 
     def forward(self, x):
-        c1, n1, _, c2, n2 = self.block
-        return ops.ResBlockFn.apply(x, c1.weight, c1.bias, n1.weight, n1.bias, c2.weight, c2.bias, n2.weight, n2.bias,
-                                    n1.running_mean, n1.running_var, n1.num_batches_tracked,
-                                    n2.running_mean, n2.running_var, n2.num_batches_tracked, self.training)
+        return ops.ResBlockFn.apply(x, *_rb_args(self), self.training)
 
 
 def _rb_args(m):
@@ -47,10 +44,8 @@ def resblock_pair(m1, m2, x):
     """m2(m1(x)) for two ResBlocks in a row (py/main16.py:135-136, :178-179).  In a training step on the fused path the pair is
     ONE tape node (ops.ResBlockPairFn: the second block's backward also does the first block's ReLU backward and BatchNorm sums);
     otherwise -- inference, no gradients wanted, odd clip lengths, any of the knobs off, forward hooks on the blocks -- two calls."""
-    c = ops._CONV
-    if (m1.training and m2.training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 3 and x.shape[-1] % 64 == 0
-            and c["bf16x6"] and c["fused_bwd"] and c["mask_on_load"] and c["pair_fold"] and not ops._ASYNC["on"]
-            and not m1._forward_hooks and not m2._forward_hooks and not m1._forward_pre_hooks and not m2._forward_pre_hooks):
+    hooked = m1._forward_hooks or m2._forward_hooks or m1._forward_pre_hooks or m2._forward_pre_hooks
+    if m1.training and m2.training and not hooked and ops.pair_node_applies(x):
         return ops.ResBlockPairFn.apply(x, *_rb_args(m1), *_rb_args(m2), True)
     return m2(m1(x))
 

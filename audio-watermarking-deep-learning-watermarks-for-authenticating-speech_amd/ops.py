@@ -6,6 +6,9 @@ block of the reference graph (py/main16.py:112-186, :53-81, :192-217).
 """
 from __future__ import annotations
 
+import contextlib
+import os
+
 import torch
 
 from ._lib import lib
@@ -125,80 +128,138 @@ def join_side_stream():
 
 def _gdst(*params):
     """gradient destinations registered on the parameters (None when the async path is off)"""
-    if not _ASYNC["on"]:
-        return tuple(None for _ in params)
-    return tuple(getattr(p, "_wm_grad", None) for p in params)
+    return tuple(getattr(p, "_wm_grad", None) if _ASYNC["on"] else None for p in params)
 
 
 def _on_side(inputs, fn, defer=True):
     """queue fn() (kernel launches) for the side stream.  defer=True: held back until release_deferred_wgrads() -- launched
     at once they would only take turns with the main stream's convolutions (both want whole CUs); released at the start of
     the LSTM BPTT they fill the CUs' idle matrix cores instead."""
-    if defer:
-        _ASYNC["deferred"].append((inputs, fn))
-        return
     _ASYNC["deferred"].append((inputs, fn))
-    release_deferred_wgrads()
+    if not defer:
+        release_deferred_wgrads()
 
 
-# ---------------------------------------------------------------------------------------------- conv arithmetic mode
-# k3 convolutions (forward + data gradient): native fp32 MFMA, or the bf16x6 split build (fp32-grade error on the
-# bf16 matrix cores, see csrc/conv64.hip).  WM_CONV_BF16X6=0/1 in the environment overrides the default.
-import os as _os
-_CONV = {"bf16x6": _os.environ.get("WM_CONV_BF16X6", "1") == "1", "schedule": 2,
-         "one_launch_eval": _os.environ.get("WM_RESBLOCK_ONE_LAUNCH", "1") == "1",
-         "fused_bwd": _os.environ.get("WM_FUSED_BWD", "1") == "1",
-         "mask_on_load": _os.environ.get("WM_MASK_ON_LOAD", "1") == "1",
-         "pair_fold": _os.environ.get("WM_PAIR_FOLD", "1") == "1",
-         "bwd_f16x3": _os.environ.get("WM_BWD_F16X3", "1") == "1",
-         "fwd_f16x3": _os.environ.get("WM_FWD_F16X3", "1") == "1",
-         "conv7_f16x3": _os.environ.get("WM_CONV7_F16X3", "1") == "1",
-         "eval_f16x3": _os.environ.get("WM_EVAL_F16X3", "1") == "1"}
+def _wgrad_dst(gdst, device, *shapes):
+    """(tensors for the weight-gradient kernel, accumulate, launch): with destinations registered (gdst, views of the flat gradient bucket) the
+    kernel ACCUMULATES into them, queued for the side stream by launch(inputs it reads, fn); else it fills fresh `shapes`, launched in line"""
+    if all(g is not None for g in gdst):
+        return gdst, True, _on_side
+    return tuple(_f32(*shape, device=device) for shape in shapes), False, lambda inputs, fn: fn()
+
+
+# ---------------------------------------------------------------------------------------------- path switches
+# Every path switch, by the name switches() / set_switch() take: (store, key, environment variable, default, library entry point | None,
+# what on | off selects).  store[key] holds the live value: plain dicts (_CONV, _LSTM, main14b_2's _GCONV and its module globals) read
+# directly on the hot path and by bench.py.  The variable: "1" = on, else off (schedule: an integer).  A library entry point: the value
+# also lives in libwm_hip.so and set_switch() calls it -- at import ONLY when the variable is present (importing needs no built library).
+SWITCHES = {
+    "bf16x6": ("conv", "bf16x6", "WM_CONV_BF16X6", True, None, "64->64 convolutions on the bf16x6 / f16 split builds | native fp32 MFMA"),
+    "schedule": ("conv", "schedule", "WM_CONV_BF_SCHEDULE", 2, "wm_set_conv_bf_schedule", "an integer: 2 register-resident weights + interleaved split | 0 phase-serial"),
+    "one_launch_eval": ("conv", "one_launch_eval", "WM_RESBLOCK_ONE_LAUNCH", True, None, "inference ResBlock as one launch | two"),
+    "fused_bwd": ("conv", "fused_bwd", "WM_FUSED_BWD", True, None, "ResBlock backward: data + weight gradient of a convolution in one launch | two"),
+    "mask_on_load": ("conv", "mask_on_load", "WM_MASK_ON_LOAD", True, None, "fused ResBlock backward masks g on load | writes the masked gradient first"),
+    "pair_fold": ("conv", "pair_fold", "WM_PAIR_FOLD", True, None, "two ResBlocks in a row as one tape node | two nodes"),
+    "bwd_f16x3": ("conv", "bwd_f16x3", "WM_BWD_F16X3", True, None, "fused ResBlock backward on the f16 two-piece split | bf16x6"),
+    "fwd_f16x3": ("conv", "fwd_f16x3", "WM_FWD_F16X3", True, None, "ResBlock forward convolutions on the f16 two-piece split | bf16x6"),
+    "conv7_f16x3": ("conv", "conv7_f16x3", "WM_CONV7_F16X3", True, None, "ConvTranspose1d(64,64,7) on the f16 two-piece split | bf16x6"),
+    "eval_f16x3": ("conv", "eval_f16x3", "WM_EVAL_F16X3", True, None, "one-launch inference ResBlock on the f16 two-piece split | bf16x6"),
+    "lstm_fused": ("lstm", "fused", "WM_LSTM_FUSED", True, None, "LSTM input projection inside the recurrence kernel | wm_lstm_xproj + wm_lstm_fwd"),
+    "lstm_bwd_fused": ("lstm", "bwd_fused", "WM_LSTM_BWD_FUSED", False, None, "wm_lstm_bwd + wm_lstm_dx as one launch | two (the default)"),
+    "lstm_bwd_ws": ("lstm", "bwd_ws", "WM_LSTM_BWD_WS", True, None, "LSTM weight gradients on helper waves beside the BPTT | wm_lstm_bwd + wm_lstm_wgrad"),
+    "lstm_fwd_ws": ("lstm", "fwd_ws", "WM_LSTM_FWD_WS", True, "wm_set_lstm_fwd_wave_specialised", "LSTM forward input projection on helper waves | in the recurrence's own waves"),
+    "gconv_f16x3": ("gconv", "f16x3", "WM_GCONV_F16X3", True, None, "main14b_2 generic convolutions on the f16 two-piece split | native fp32 MFMA"),
+    "fused_strided_dgrad": ("main14b_2", "_FUSED_STRIDED_DGRAD", "WM_FUSED_STRIDED_DGRAD", True, None, "main14b_2 down-sampling block: both data gradients into x in one launch | two"),
+}
+
+
+def read_switches(environ) -> dict:
+    """{"conv": {key: value}, "lstm": {...}, "gconv": {...}, "main14b_2": {...}, "library": [names]}: what every switch starts with under `environ` (pure: no
+    store, no library call).  "library": the library-backed switches whose variable is present -- only those must reach libwm_hip.so"""
+    out = {"conv": {}, "lstm": {}, "gconv": {}, "main14b_2": {}, "library": []}
+    for name, (store, key, env, default, libfn, _) in SWITCHES.items():
+        raw = environ.get(env)
+        out[store][key] = default if raw is None else int(raw) if type(default) is int else raw == "1"
+        if libfn and raw is not None:
+            out["library"].append(name)
+    return out
+
+
+_LIVE = read_switches(os.environ)
+_CONV, _LSTM, _GCONV = _LIVE["conv"], _LIVE["lstm"], _LIVE["gconv"]
+
+
+def bind_store(store, namespace):
+    """a module that keeps its switches as plain globals (main14b_2) hands over its namespace: seeded with the starting values, it IS the store"""
+    namespace.update(_LIVE[store])
+    _LIVE[store] = namespace
+
+
+def set_switch(name, value):
+    """the common setter: store[key] = value (and the library's copy, for a library-backed switch)"""
+    store, key, _, default, libfn, _ = SWITCHES[name]
+    value = type(default)(value)
+    if libfn:
+        getattr(lib, libfn)(int(value), None)
+    _LIVE[store][key] = value
+
+
+for _name in _LIVE["library"]:
+    set_switch(_name, _LIVE[SWITCHES[_name][0]][SWITCHES[_name][1]])
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """run a block under other switch values (names: SWITCHES); the PREVIOUS values come back on exit, also when the block raises.
+    An unknown name raises KeyError before anything changes.  For tests and diagnostics, not for the step path."""
+    prev = {name: _LIVE[SWITCHES[name][0]][SWITCHES[name][1]] for name in values}
+    try:
+        for name, value in values.items():
+            set_switch(name, value)
+        yield
+    finally:
+        for name, value in prev.items():
+            set_switch(name, value)
 
 
 def set_conv_bf_schedule(schedule: int):
     """0: phase-serial kernel, 2: register-resident weights + interleaved split (csrc/conv64.hip)."""
-    lib.wm_set_conv_bf_schedule(int(schedule), None)
-    _CONV["schedule"] = int(schedule)
-
-
-if "WM_CONV_BF_SCHEDULE" in _os.environ:
-    set_conv_bf_schedule(int(_os.environ["WM_CONV_BF_SCHEDULE"]))
+    set_switch("schedule", schedule)
 
 
 def set_conv_bf16x6(on: bool):
-    _CONV["bf16x6"] = bool(on)
+    set_switch("bf16x6", on)
 
 
 def set_fused_backward(on: bool):
     """ResBlock backward: data gradient + weight gradient of each convolution in ONE launch (wm_dwgrad64_bf, default) or as two
     (wm_conv64_bf + wm_wgrad64_bf).  WM_FUSED_BWD=0/1 in the environment sets the default."""
-    _CONV["fused_bwd"] = bool(on)
+    set_switch("fused_bwd", on)
 
 
 def set_mask_on_load(on: bool):
     """fused ResBlock backward: 1 (default) the masked gradient dz2 = g * (out > 0) is never written -- the reduction pass forms
     only the BatchNorm sums and wm_dwgrad64_bf masks g on load; 0 it is materialised first.  WM_MASK_ON_LOAD=0/1 sets the default."""
-    _CONV["mask_on_load"] = bool(on)
+    set_switch("mask_on_load", on)
 
 
 def set_bwd_f16x3(on: bool):
     """fused ResBlock backward arithmetic: 1 (default) f16 two-piece split, three products per product on the f16 matrix cores
     (half the matrix work of bf16x6; power-of-two scales from max |w| and max |A| max |dz| keep the operands in the f16 range),
     0 bf16x6 as in the forward.  WM_BWD_F16X3=0/1 sets the default."""
-    _CONV["bwd_f16x3"] = bool(on)
+    set_switch("bwd_f16x3", on)
 
 
 def set_fwd_f16x3(on: bool):
     """ResBlock forward convolutions launched through wm_conv64_bf (schedule 2, T % 128 == 0): 1 (default) the f16 two-piece split
     (three products per product instead of six; weights scaled by a power of two from max |w|, activations unscaled), 0 bf16x6.
     WM_FWD_F16X3=0/1 sets the default.  The one-launch inference ResBlock has its own switch (set_eval_f16x3)."""
-    _CONV["fwd_f16x3"] = bool(on)
+    set_switch("fwd_f16x3", on)
 
 
 def set_eval_f16x3(on: bool):
     """one-launch inference ResBlock (wm_resblock_eval_bf): 1 (default) the f16 two-piece split, 0 bf16x6.  WM_EVAL_F16X3=0/1."""
-    _CONV["eval_f16x3"] = bool(on)
+    set_switch("eval_f16x3", on)
 
 
 def pack_w64_h(w: torch.Tensor, mode: int) -> torch.Tensor:
@@ -211,13 +272,13 @@ def set_pair_fold(on: bool):
     """two ResBlocks in a row (encoder.1 -> encoder.2, model.1 -> model.2) as ONE tape node whose backward lets the second block's
     conv1 launch also do the first block's ReLU backward and BatchNorm sums (no reduction pass for the first block).
     WM_PAIR_FOLD=0/1 sets the default; off = two ResBlockFn nodes."""
-    _CONV["pair_fold"] = bool(on)
+    set_switch("pair_fold", on)
 
 
 def set_resblock_one_launch(on: bool):
     """inference ResBlock: one launch (wm_resblock_eval_bf, default) or the two-launch form (conv1; conv2 with BN2 + add + ReLU
     in its epilogue).  WM_RESBLOCK_ONE_LAUNCH=0/1 in the environment sets the default."""
-    _CONV["one_launch_eval"] = bool(on)
+    set_switch("one_launch_eval", on)
 
 
 def conv_bf16x6() -> bool:
@@ -234,13 +295,33 @@ def set_conv7_f16x3(on: bool):
     """ConvTranspose1d(64,64,7) forward / data gradient / weight gradient (T % 128 == 0): 1 (default) the f16 two-piece split (three
     products per product; weights scaled by a power of two from max |w|, the incoming gradient by one from max |g| -- one streaming
     pass over g, wm_gscale_absmax), 0 bf16x6.  WM_CONV7_F16X3=0/1 sets the default."""
-    _CONV["conv7_f16x3"] = bool(on)
+    set_switch("conv7_f16x3", on)
 
 
 def pack_w64_h7(w: torch.Tensor, mode: int) -> torch.Tensor:
     wph = torch.empty(2 * 7 * 4096 + 4, dtype=torch.int16, device=w.device)      # two f16 pieces + {ws, 1 / ws}
     lib.wm_pack_w64_h7(_p(w), _p(wph), mode, _stream())
     return wph
+
+
+def set_lstm_fwd_wave_specialised(on: bool):
+    """LSTM forward (wm_lstm_fwd_fused): 1 (default) the input projection of the next 32-step chunk runs on four helper waves beside the
+    recurrence, 0 inside the recurrence's own waves.  Bit-identical results.  WM_LSTM_FWD_WS=0/1 sets the default."""
+    set_switch("lstm_fwd_ws", on)
+
+
+def set_lstm_bwd_wave_specialised(on: bool):
+    """LSTM backward: 1 (default) wm_lstm_bwd_wgrad -- the weight gradients are formed by four helper waves beside the recurrence, from
+    the chunk of da it has just finished (T % 32 == 0, T >= 64); 0 wm_lstm_bwd followed by wm_lstm_wgrad.  WM_LSTM_BWD_WS=0/1."""
+    set_switch("lstm_bwd_ws", on)
+
+
+def set_gconv_f16x3(on: bool):
+    """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
+    two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
+    per clip), 0 native fp32
+    MFMA.  WM_GCONV_F16X3=0/1 sets the default."""
+    set_switch("gconv_f16x3", on)
 
 
 # max |g| per producer workgroup of gradient tensors whose producer formed it anyway, keyed by the tensor OBJECT (a weak reference
@@ -330,62 +411,70 @@ def pack_w64(w: torch.Tensor, kw: int, mode: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ ResBlock
+def _resblock_fwd(x, params, training, want_grad):
+    """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for params = (w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2).
+    Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx."""
+    w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = params
+    x = _frames(x, "ResBlock input", 64)
+    B, _, T = x.shape
+    dev, st = x.device, _stream()
+    out = torch.empty_like(x)
+    cst = _f32(8, 64, device=dev)       # sc1 sh1 mean1 is1 sc2 sh2 mean2 is2
+    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
+    if training:
+        y1, y2 = torch.empty_like(x), torch.empty_like(x)
+        stats = _f32(NCU * 128, device=dev)
+        _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, stats, B, T, 0, 0)
+        lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g1), _p(be1), _p(rm1), _p(rv1), _p(nbt1), BN_MOMENTUM, BN_EPS,
+                           _p(sc1), _p(sh1), _p(mu1), _p(is1), st)
+        _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, stats, B, T, 1, 0)
+        lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g2), _p(be2), _p(rm2), _p(rv2), _p(nbt2), BN_MOMENTUM, BN_EPS,
+                           _p(sc2), _p(sh2), _p(mu2), _p(is2), st)
+    else:
+        lib.wm_bn_eval_scale_shift(_p(g1), _p(be1), _p(rm1), _p(rv1), BN_EPS, _p(sc1), _p(sh1), st)
+        lib.wm_bn_eval_scale_shift(_p(g2), _p(be2), _p(rm2), _p(rv2), BN_EPS, _p(sc2), _p(sh2), st)
+        if not want_grad and _CONV["bf16x6"] and _CONV["one_launch_eval"]:
+            # inference: the whole block is ONE launch -- x in, out out, the intermediate activation stays in LDS
+            h = _CONV["eval_f16x3"]                     # f16 two-piece split (three products per product) | bf16x6
+            wp1 = torch.empty((2 * 3 * 4096 + 4) if h else 3 * 3 * 4096, dtype=torch.int16, device=dev)   # both images alive at the launch
+            wp2 = torch.empty_like(wp1)
+            pack = lib.wm_pack_w64_h_scaled if h else lib.wm_pack_w64_bf_scaled
+            pack(_p(w1), _p(sc1), _p(wp1), st)
+            pack(_p(w2), _p(sc2), _p(wp2), st)
+            lib.wm_resblock_eval_bf(_p(x), _p(wp1), _p(wp2), _p(b1), _p(sc1), _p(sh1), _p(b2), _p(sc2), _p(sh2), _p(out), B, T,
+                                    1 if h else 0, st)
+            return out, None
+        y1 = torch.empty_like(x)
+        _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, None, B, T, 0, 0)
+        if not want_grad and _CONV["bf16x6"] and _CONV["schedule"] == 2 and T % 128 == 0:
+            # inference: BN2 + residual add + ReLU ride in conv2's epilogue -- the block is two launches
+            _conv3(y1, None, w2, 0, sc1, sh1, None, b2, x, sc2, sh2, out, None, B, T, 1, 4)
+            return out, None
+        y2 = torch.empty_like(x)
+        _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, None, B, T, 1, 0)
+        # saved (mean, invstd) for an eval-mode backward = running statistics
+        mu1.copy_(rm1); is1.copy_(torch.rsqrt(rv1 + BN_EPS)); mu2.copy_(rm2); is2.copy_(torch.rsqrt(rv2 + BN_EPS))
+    if want_grad:
+        # the backward needs only the SIGN of `out`: one bit per element, written beside it (a frame pass less in backward)
+        mask = torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=dev)
+        lib.wm_bn_add_relu_mask(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), _p(mask), B, T, st)
+    else:
+        mask = None
+        lib.wm_bn_add_relu(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), B, T, st)
+    return out, (x, y1, y2, mask, cst, w1, w2, g1, g2)
+
+
 class ResBlockFn(GradAwareFunction):
     """relu(x + BN2(conv2(relu(BN1(conv1(x))))))  -- ResBlock.forward, py/main16.py:124-125."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2, training):
-        x = _frames(x, "ResBlock input", 64)
-        B, _, T = x.shape
-        dev, st = x.device, _stream()
-        out = torch.empty_like(x)
-        cst = _f32(8, 64, device=dev)       # sc1 sh1 mean1 is1 sc2 sh2 mean2 is2
-        sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
-        if training:
-            y1, y2 = torch.empty_like(x), torch.empty_like(x)
-            stats = _f32(NCU * 128, device=dev)
-            _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, stats, B, T, 0, 0)
-            lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g1), _p(be1), _p(rm1), _p(rv1), _p(nbt1), BN_MOMENTUM, BN_EPS,
-                               _p(sc1), _p(sh1), _p(mu1), _p(is1), st)
-            _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, stats, B, T, 1, 0)
-            lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g2), _p(be2), _p(rm2), _p(rv2), _p(nbt2), BN_MOMENTUM, BN_EPS,
-                               _p(sc2), _p(sh2), _p(mu2), _p(is2), st)
-        else:
-            lib.wm_bn_eval_scale_shift(_p(g1), _p(be1), _p(rm1), _p(rv1), BN_EPS, _p(sc1), _p(sh1), st)
-            lib.wm_bn_eval_scale_shift(_p(g2), _p(be2), _p(rm2), _p(rv2), BN_EPS, _p(sc2), _p(sh2), st)
-            if not wants_grad(ctx) and _CONV["bf16x6"] and _CONV["one_launch_eval"]:
-                # inference: the whole block is ONE launch -- x in, out out, the intermediate activation stays in LDS
-                h = _CONV["eval_f16x3"]                     # f16 two-piece split (three products per product) | bf16x6
-                wp1 = torch.empty((2 * 3 * 4096 + 4) if h else 3 * 3 * 4096, dtype=torch.int16, device=dev)   # both images alive at the launch
-                wp2 = torch.empty_like(wp1)
-                pack = lib.wm_pack_w64_h_scaled if h else lib.wm_pack_w64_bf_scaled
-                pack(_p(w1), _p(sc1), _p(wp1), st)
-                pack(_p(w2), _p(sc2), _p(wp2), st)
-                lib.wm_resblock_eval_bf(_p(x), _p(wp1), _p(wp2), _p(b1), _p(sc1), _p(sh1), _p(b2), _p(sc2), _p(sh2), _p(out), B, T,
-                                        1 if h else 0, st)
-                return out
-            y1 = torch.empty_like(x)
-            _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, None, B, T, 0, 0)
-            if not wants_grad(ctx) and _CONV["bf16x6"] and _CONV["schedule"] == 2 and T % 128 == 0:
-                # inference: BN2 + residual add + ReLU ride in conv2's epilogue -- the block is two launches
-                _conv3(y1, None, w2, 0, sc1, sh1, None, b2, x, sc2, sh2, out, None, B, T, 1, 4)
-                return out
-            y2 = torch.empty_like(x)
-            _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, None, B, T, 1, 0)
-            # saved (mean, invstd) for an eval-mode backward = running statistics
-            mu1.copy_(rm1); is1.copy_(torch.rsqrt(rv1 + BN_EPS)); mu2.copy_(rm2); is2.copy_(torch.rsqrt(rv2 + BN_EPS))
-        if wants_grad(ctx):
-            # the backward needs only the SIGN of `out`: one bit per element, written beside it (a frame pass less in backward)
-            mask = torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=dev)
-            lib.wm_bn_add_relu_mask(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), _p(mask), B, T, st)
-        else:
-            mask = None
-            lib.wm_bn_add_relu(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), B, T, st)
-        ctx.training = bool(training)
-        ctx.gdst = _gdst(w1, b1, w2, b2)
-        ctx._wm_saved = (x, y1, y2, mask, cst, w1, w2, g1, g2)
-        if not getattr(ctx, "_wm_pair", False):
-            ctx.save_for_backward(*ctx._wm_saved)
+    def forward(ctx, x, *args):
+        params, training = args[:14], args[14]
+        out, saved = _resblock_fwd(x, params, training, wants_grad(ctx))
+        if saved is not None:
+            ctx.training = bool(training)
+            ctx.gdst = _gdst(params[0], params[1], params[4], params[5])      # w1, b1, w2, b2
+            ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
@@ -397,12 +486,10 @@ class ResBlockFn(GradAwareFunction):
         dev, st = x.device, _stream()
         ev = 0 if ctx.training else 1
         n = float(B * T)
-        gw1, gb1, gw2, gb2 = ctx.gdst
-        side = all(g is not None for g in ctx.gdst)
-        fused = _CONV["bf16x6"] and _CONV["fused_bwd"] and not side and T % 64 == 0
-        if fused:
+        if _CONV["bf16x6"] and _CONV["fused_bwd"] and T % 64 == 0 and not all(g is not None for g in ctx.gdst):
             dx, grads, _ = _resblock_bwd_fused(ctx.saved_tensors, ctx.training, g_out)
             return (dx,) + grads + (None,) * 7
+        (dw1, db1, dw2, db2), acc, launch = _wgrad_dst(ctx.gdst, dev, w1.shape, (64,), w2.shape, (64,))
         part = _f32(max(B, 1) * 128, device=dev)
         dz2 = torch.empty_like(x)
         lib.wm_relu_bwd_reduce_mask(_p(g_out), _p(mask), _p(y2), _p(dz2), _p(part), None, B, T, st)
@@ -414,39 +501,24 @@ class ResBlockFn(GradAwareFunction):
         stats = _f32(NCU * 128, device=dev)
         _conv3(dz2, y2, w2, 1, k2[0], k2[1], k2[3], None, y1, sc1, sh1, dz1, stats, B, T, 3, 1)
 
-        def wgrad2():
+        def wgrad(dz, y, k, xin, sc, sh, xpro, dw, db):
             wpart = _f32(2 * NCU * (3 * 4096 + 64), device=dev)
             if _CONV["bf16x6"]:
-                lib.wm_wgrad64_bf(_p(dz2), _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(y1), _p(sc1), _p(sh1), _p(wpart),
-                                  _p(gw2 if side else dw2), _p(gb2 if side else db2), B, T, 3, 1, 3 if side else 0, _stream())
+                lib.wm_wgrad64_bf(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
+                                  B, T, 3, xpro, 3 if acc else 0, _stream())
             else:
-                lib.wm_wgrad64(_p(dz2), _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(y1), _p(sc1), _p(sh1), _p(wpart),
-                               _p(gw2 if side else dw2), _p(gb2 if side else db2), B, T, 3, 3, 1, 0, 1 if side else 0, _stream())
-        dw2, db2 = (None, None) if side else (torch.empty_like(w2), _f32(64, device=dev))
-        if side:
-            _on_side((dz2, y2, k2, y1, cst), wgrad2)
-        else:
-            wgrad2()
+                lib.wm_wgrad64(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
+                               B, T, 3, 3, xpro, 0, 1 if acc else 0, _stream())
+        launch((dz2, y2, k2, y1, cst), lambda: wgrad(dz2, y2, k2, y1, sc1, sh1, 1, dw2, db2))
         k1 = _f32(4, 64, device=dev)
         dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
         lib.wm_bn_bwd_finalize(_p(stats), NCU, n, _p(g1), _p(mu1), _p(is1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(dg1), _p(dbe1), 0, ev, None, 0, None, st)
         # conv1: data gradient + residual path, weight gradient
         dx = torch.empty_like(x)
         _conv3(dz1, y1, w1, 1, k1[0], k1[1], k1[3], None, dz2, None, None, dx, None, B, T, 3, 2)
-        def wgrad1():
-            wpart = _f32(2 * NCU * (3 * 4096 + 64), device=dev)
-            if _CONV["bf16x6"]:
-                lib.wm_wgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(x), None, None, _p(wpart),
-                                  _p(gw1 if side else dw1), _p(gb1 if side else db1), B, T, 3, 0, 3 if side else 0, _stream())
-            else:
-                lib.wm_wgrad64(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(x), None, None, _p(wpart),
-                               _p(gw1 if side else dw1), _p(gb1 if side else db1), B, T, 3, 3, 0, 0, 1 if side else 0, _stream())
-        dw1, db1 = (None, None) if side else (torch.empty_like(w1), _f32(64, device=dev))
-        if side:
-            _on_side((dz1, y1, k1, x), wgrad1)
-        else:
-            wgrad1()
-        return dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, None, None, None, None, None, None, None
+        launch((dz1, y1, k1, x), lambda: wgrad(dz1, y1, k1, x, None, None, 0, dw1, db1))
+        g1_, g2_ = ((None, None),) * 2 if acc else ((dw1, db1), (dw2, db2))     # (dw / db stay bound: the queued launches read them later)
+        return (dx,) + g1_ + (dg1, dbe1) + g2_ + (dg2, dbe2) + (None,) * 7
 
 
 def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
@@ -514,9 +586,15 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
     return dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fout
 
 
+def pair_node_applies(x) -> bool:
+    """ResBlockPairFn's precondition on input and switches (the caller adds: both blocks in training mode, no forward hooks)"""
+    return (torch.is_grad_enabled() and x.is_cuda and x.dim() == 3 and x.shape[-1] % 64 == 0 and _CONV["bf16x6"]
+            and _CONV["fused_bwd"] and _CONV["mask_on_load"] and _CONV["pair_fold"] and not _ASYNC["on"])
+
+
 class ResBlockPairFn(GradAwareFunction):
     """Two ResBlocks in a row (py/main16.py:135-136 encoder.1 -> encoder.2, :178-179 model.1 -> model.2) as one tape node.
-    Forward = ResBlockFn's training forward twice.  Backward: the second block's conv1 launch (data + weight gradient) applies the
+    Forward = _resblock_fwd twice.  Backward: the second block's conv1 launch (data + weight gradient) applies the
     FIRST block's ReLU mask to the gradient it has just formed and accumulates that block's two BatchNorm sums in its epilogue
     (wm_dwgrad64_bf epi 8), so the first block needs no reduction pass and the gradient between the blocks is written once, masked.
     Used by modules.resblock_pair when the fused path applies (bf16x6, T % 64 == 0, mask-on-load, gradients wanted)."""
@@ -524,11 +602,9 @@ class ResBlockPairFn(GradAwareFunction):
     @staticmethod
     def forward(ctx, x, *args):
         p1, p2, training = args[:14], args[14:28], args[28]
-        ctx._wm_pair = True                                  # ResBlockFn.forward then leaves the saving to this node
-        mid = ResBlockFn.forward(ctx, x, *p1, training)
-        ctx.saved1 = ctx._wm_saved                       # (x, y1, y2, mask, cst, w1, w2, g1, g2) of block 1
-        out = ResBlockFn.forward(ctx, mid, *p2, training)
-        ctx.save_for_backward(*(ctx.saved1 + ctx._wm_saved))
+        mid, first = _resblock_fwd(x, p1, training, wants_grad(ctx))
+        out, second = _resblock_fwd(mid, p2, training, wants_grad(ctx))
+        ctx.save_for_backward(*(first + second))
         ctx.training = bool(training)
         return out
 
@@ -625,28 +701,6 @@ class HeadNFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ LSTM
-_LSTM_FUSED = _os.environ.get("WM_LSTM_FUSED", "1") == "1"     # 0: separate wm_lstm_xproj + wm_lstm_fwd launches
-_LSTM_BWD_FUSED = _os.environ.get("WM_LSTM_BWD_FUSED", "0") == "1"   # 1: wm_lstm_bwd + wm_lstm_dx as one launch
-_LSTM = {"bwd_ws": _os.environ.get("WM_LSTM_BWD_WS", "1") == "1", "fwd_ws": True}
-
-
-def set_lstm_fwd_wave_specialised(on: bool):
-    """LSTM forward (wm_lstm_fwd_fused): 1 (default) the input projection of the next 32-step chunk runs on four helper waves beside the
-    recurrence, 0 inside the recurrence's own waves.  Bit-identical results.  WM_LSTM_FWD_WS=0/1 sets the default."""
-    lib.wm_set_lstm_fwd_wave_specialised(1 if on else 0, None)
-    _LSTM["fwd_ws"] = bool(on)
-
-
-if "WM_LSTM_FWD_WS" in _os.environ:
-    set_lstm_fwd_wave_specialised(_os.environ["WM_LSTM_FWD_WS"] == "1")
-
-
-def set_lstm_bwd_wave_specialised(on: bool):
-    """LSTM backward: 1 (default) wm_lstm_bwd_wgrad -- the weight gradients are formed by four helper waves beside the recurrence, from
-    the chunk of da it has just finished (T % 32 == 0, T >= 64); 0 wm_lstm_bwd followed by wm_lstm_wgrad.  WM_LSTM_BWD_WS=0/1."""
-    _LSTM["bwd_ws"] = bool(on)
-
-
 class LSTMFn(GradAwareFunction):
     """nn.LSTM(64,64,batch_first=True) on channel-first frames: (B,64,T) -> (B,64,T); the two permutes of
     py/main16.py:152,154 are folded into the kernels' addressing."""
@@ -659,24 +713,18 @@ class LSTMFn(GradAwareFunction):
         need_grad = wants_grad(ctx)
         h = torch.empty_like(x)
         release_deferred_wgrads()                  # side stream: work queued for "beside the recurrence" starts now (eval_forward)
-        if _LSTM_FUSED and T >= 8:                 # input projection inside the recurrence kernel (no xp tensor)
-            gates = cst = None
-            if need_grad:
-                gates, cst = _f32(B, T, 256, device=dev), _f32(B, T, 64, device=dev)
+        cst = _f32(B, T, 64, device=dev) if need_grad else None
+        if _LSTM["fused"] and T >= 8:               # input projection inside the recurrence kernel (no xp tensor)
+            gates = _f32(B, T, 256, device=dev) if need_grad else None
             lib.wm_lstm_fwd_fused(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
-            if need_grad:
-                ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
-                ctx.save_for_backward(x, h, gates, cst, w_ih, w_hh)
-            return h
-        xp = _f32(B, T, 256, device=dev)
-        lib.wm_lstm_xproj(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(xp), B, T, st)
-        if need_grad:
-            gates, cst = xp, _f32(B, T, 64, device=dev)     # activations overwrite the projections in place
+        else:
+            xp = _f32(B, T, 256, device=dev)
+            lib.wm_lstm_xproj(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(xp), B, T, st)
+            gates = xp if need_grad else None       # activations overwrite the projections in place
             lib.wm_lstm_fwd(_p(xp), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
+        if need_grad:
             ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
             ctx.save_for_backward(x, h, gates, cst, w_ih, w_hh)
-        else:
-            lib.wm_lstm_fwd(_p(xp), _p(w_hh), _p(h), None, None, B, T, st)
         return h
 
     @staticmethod
@@ -688,39 +736,23 @@ class LSTMFn(GradAwareFunction):
         dev, st = x.device, _stream()
         dx = torch.empty_like(x)
         release_deferred_wgrads()                  # side stream: the queued weight-gradient GEMMs run beside the recurrence
-        if _LSTM["bwd_ws"] and not _LSTM_BWD_FUSED and T % 32 == 0 and T >= 64:
-            part = _f32(B * (256 * 128 + 256), device=dev)
-            if all(g is not None for g in ctx.gdst):           # accumulate into the flat gradient store
-                gwi, gwh, gbi, gbh = ctx.gdst
-                lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), _p(gwi), _p(gwh), _p(gbi), _p(gbh),
-                                      B, T, 1, st)
-                lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
-                return dx, None, None, None, None
-            dwi, dwh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-            dbi, dbh = _f32(256, device=dev), _f32(256, device=dev)
-            lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), _p(dwi), _p(dwh), _p(dbi), _p(dbh),
-                                  B, T, 0, st)
+        dst, acc, launch = _wgrad_dst(ctx.gdst, dev, w_ih.shape, w_hh.shape, (256,), (256,))     # dwi, dwh, dbi, dbh
+        if _LSTM["bwd_ws"] and not _LSTM["bwd_fused"] and T % 32 == 0 and T >= 64:
+            part = _f32(B * (256 * 128 + 256), device=dev)       # (this launch accumulates into the flat store from the main stream)
+            lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), st)
             lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
-            return dx, dwi, dwh, dbi, dbh
-        if _LSTM_BWD_FUSED:                        # measured: no faster than the two launches; off by default
+            return (dx,) + ((None,) * 4 if acc else dst)
+        if _LSTM["bwd_fused"]:                    # measured: no faster than the two launches; off by default
             lib.wm_lstm_bwd_fused(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(w_ih), _p(dx), B, T, st)   # gates now holds da
         else:
             lib.wm_lstm_bwd(_p(gates), _p(cst), _p(dh), _p(w_hh), B, T, st)      # gates now holds da
             lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
-        side = all(g is not None for g in ctx.gdst)
-        if side:
-            gwi, gwh, gbi, gbh = ctx.gdst
 
-            def wg():
-                part = _f32(NCU * (256 * 128 + 256), device=dev)
-                lib.wm_lstm_wgrad(_p(gates), _p(x), _p(h), _p(part), _p(gwi), _p(gwh), _p(gbi), _p(gbh), B, T, 1, _stream())
-            _on_side((gates, x, h), wg)
-            return dx, None, None, None, None
-        part = _f32(NCU * (256 * 128 + 256), device=dev)
-        dwi, dwh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-        dbi, dbh = _f32(256, device=dev), _f32(256, device=dev)
-        lib.wm_lstm_wgrad(_p(gates), _p(x), _p(h), _p(part), _p(dwi), _p(dwh), _p(dbi), _p(dbh), B, T, 0, st)
-        return dx, dwi, dwh, dbi, dbh
+        def wg():
+            part = _f32(NCU * (256 * 128 + 256), device=dev)
+            lib.wm_lstm_wgrad(_p(gates), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), _stream())
+        launch((gates, x, h), wg)
+        return (dx,) + ((None,) * 4 if acc else dst)
 
 
 # ------------------------------------------------------------------------------------------ embedding + convT
@@ -731,7 +763,7 @@ class LSTMFn(GradAwareFunction):
 #              sync, the launch queue never drains -- what train_step uses (a mid-step sync costs the config-5 step 6 ms: its
 #              LSTM chain is 200 short launches the host can only cover when it runs ahead);
 #   "off"      no check (out-of-range ids read as a zero row).
-_CHECK_INDEX = {"mode": {"1": "sync", "0": "off"}.get(_os.environ.get("WM_CHECK_INDEX", "1"), _os.environ.get("WM_CHECK_INDEX", "sync")),
+_CHECK_INDEX = {"mode": {"1": "sync", "0": "off"}.get(os.environ.get("WM_CHECK_INDEX", "1"), os.environ.get("WM_CHECK_INDEX", "sync")),
                 "pending": []}
 
 
@@ -742,19 +774,19 @@ def set_index_check(mode):
         raise ValueError("index check mode must be 'sync', 'deferred' or 'off'")
 
 
-class index_check_mode:
-    """context manager: run a block under another index-check mode"""
+@contextlib.contextmanager
+def index_check_mode(mode=None):
+    """context manager: run a block under another index-check mode; None (a train step's forward): "sync" becomes "deferred", the others stay"""
+    prev = _CHECK_INDEX["mode"]
+    set_index_check(("deferred" if prev == "sync" else prev) if mode is None else mode)
+    try:
+        yield
+    finally:
+        _CHECK_INDEX["mode"] = prev
 
-    def __init__(self, mode):
-        self.mode = mode
 
-    def __enter__(self):
-        self.prev = _CHECK_INDEX["mode"]
-        set_index_check(self.mode)
-
-    def __exit__(self, *exc):
-        _CHECK_INDEX["mode"] = self.prev
-        return False
+def index_check() -> str:                       # "sync" | "deferred" | "off"
+    return _CHECK_INDEX["mode"]
 
 
 def check_message_ids(wait=True, what="an earlier Generator call"):
@@ -817,6 +849,20 @@ class EmbedFn(torch.autograd.Function):
         return dtable, None
 
 
+def _conv7_arith(T) -> str:
+    """arithmetic of the 7-tap 64->64 convolution on clips of T samples (forward, data gradient and weight gradient alike)"""
+    return "fp32" if not _CONV["bf16x6"] else "f16x3" if _CONV["conv7_f16x3"] and T % 128 == 0 else "bf16x6"
+
+
+def _conv7(arith, x, w, wmode, vec, b, y, B, T, pro, epi, gsc, st):
+    """one k7 64->64 convolution launch (wmode / epi 2 / 0: ConvTranspose1d forward, 3 / 3: its data gradient) in arithmetic `arith`"""
+    if arith == "fp32":
+        lib.wm_conv64(_p(x), None, _p(pack_w64(w, 7, wmode)), _p(vec), None, None, _p(b), None, None, None, _p(y), None, B, T, 7, pro, epi, st)
+    else:
+        h = arith == "f16x3"
+        lib.wm_conv64_bf7(_p(x), _p((pack_w64_h7 if h else pack_w64_bf7)(w, wmode)), _p(vec), _p(b), _p(y), B, T, pro, epi, int(h), _p(gsc), st)
+
+
 class ConvT7Fn(torch.autograd.Function):
     """ConvTranspose1d(64,64,7,padding=3) applied to x + emb[:, :, None]  (py/main16.py:144,156-161);
     `vec` (B,64) is the looked-up embedding row or None."""
@@ -826,15 +872,7 @@ class ConvT7Fn(torch.autograd.Function):
         x = _frames(x, "decoder input", 64)
         B, _, T = x.shape
         y = torch.empty_like(x)
-        pro = 2 if vec is not None else 0
-        if _CONV["bf16x6"]:
-            if _CONV["conv7_f16x3"] and T % 128 == 0:
-                lib.wm_conv64_bf7(_p(x), _p(pack_w64_h7(w, 2)), _p(vec), _p(b), _p(y), B, T, pro, 0, 1, None, _stream())
-            else:
-                lib.wm_conv64_bf7(_p(x), _p(pack_w64_bf7(w, 2)), _p(vec), _p(b), _p(y), B, T, pro, 0, 0, None, _stream())
-        else:
-            lib.wm_conv64(_p(x), None, _p(pack_w64(w, 7, 2)), _p(vec), None, None, _p(b), None, None, None, _p(y), None, B, T, 7, pro, 0,
-                          _stream())
+        _conv7(_conv7_arith(T), x, w, 2, vec, b, y, B, T, 2 if vec is not None else 0, 0, None, _stream())
         ctx.has_vec = vec is not None
         ctx.gdst = _gdst(w, b)
         ctx.save_for_backward(x, w, vec if vec is not None else x.new_empty(0))
@@ -848,35 +886,26 @@ class ConvT7Fn(torch.autograd.Function):
         B, _, T = x.shape
         dev, st = x.device, _stream()
         dx = torch.empty_like(x)
-        h7 = _CONV["bf16x6"] and _CONV["conv7_f16x3"] and T % 128 == 0
-        gsc = gscale_of(g) if h7 else None              # the scale both f16-split launches apply to g (.contiguous() above returns g itself)
-        if h7:
-            lib.wm_conv64_bf7(_p(g), _p(pack_w64_h7(w, 3)), None, None, _p(dx), B, T, 0, 3, 1, _p(gsc), st)
-        elif _CONV["bf16x6"]:
-            lib.wm_conv64_bf7(_p(g), _p(pack_w64_bf7(w, 3)), None, None, _p(dx), B, T, 0, 3, 0, None, st)
-        else:
-            lib.wm_conv64(_p(g), None, _p(pack_w64(w, 7, 3)), None, None, None, None, None, None, None, _p(dx), None, B, T, 7, 0, 3, st)
-        gw, gbias = ctx.gdst
-        side = gw is not None and gbias is not None
+        arith = _conv7_arith(T)
+        h = arith == "f16x3"
+        gsc = gscale_of(g) if h else None               # the scale both f16-split launches apply to g (.contiguous() above returns g itself)
+        _conv7(arith, g, w, 3, None, None, dx, B, T, 0, 3, gsc, st)
+        (dw, db), acc, launch = _wgrad_dst(ctx.gdst, dev, w.shape, (64,))
+        pro = 2 if vec is not None else 0
 
         def wg():
             part = _f32(2 * NCU * (7 * 4096 + 64), device=dev)
-            if _CONV["bf16x6"]:
-                lib.wm_wgrad64_bf7(_p(g), _p(x), _p(vec), _p(part), _p(gw if side else dw), _p(gbias if side else db), B, T,
-                                   2 if vec is not None else 0, 1 if side else 0, 1 if h7 else 0, _p(gsc), _stream())
-                return
-            lib.wm_wgrad64(_p(g), None, None, None, None, _p(x), _p(vec), None, _p(part), _p(gw if side else dw),
-                           _p(gbias if side else db), B, T, 7, 0, 2 if vec is not None else 0, 1, 1 if side else 0, _stream())
-        dw, db = (None, None) if side else (torch.empty_like(w), _f32(64, device=dev))
-        if side:
-            _on_side((g, x, vec, gsc), wg)
-        else:
-            wg()
+            if arith == "fp32":
+                lib.wm_wgrad64(_p(g), None, None, None, None, _p(x), _p(vec), None, _p(part), _p(dw), _p(db), B, T, 7, 0, pro, 1, int(acc),
+                               _stream())
+            else:
+                lib.wm_wgrad64_bf7(_p(g), _p(x), _p(vec), _p(part), _p(dw), _p(db), B, T, pro, int(acc), int(h), _p(gsc), _stream())
+        launch((g, x, vec, gsc), wg)
         dvec = None
         if vec is not None and ctx.needs_input_grad[1]:
             dvec = _f32(B, 64, device=dev)
             lib.wm_rowsum(_p(dx), _p(dvec), B * 64, T, st)
-        return dx, dvec, dw, db
+        return (dx, dvec) + ((None, None) if acc else (dw, db))
 
 
 # ------------------------------------------------------------------------------------------ delta post-processing

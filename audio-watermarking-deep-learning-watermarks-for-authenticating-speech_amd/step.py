@@ -6,7 +6,7 @@ from collections import OrderedDict
 
 import torch
 
-from . import losses as L
+from . import losses as L, ops
 
 # py/main16.py:38-43
 LOSS_WEIGHTS = OrderedDict(l1=1.0, mel=4.0, loud=20.0, loc=10.0, bce=1.0, hf=5.0)
@@ -34,15 +34,13 @@ def forward_losses(generator, detector, s, message):
                               bce=bce, hf=hf, raw_total=raw, total=total)
 
 
-def train_step(generator, detector, optimizer, s, message, grad_sync=None):
-    """One iteration of train_one_epoch's loop body (:242-278): zero_grad, forward, backward, optimizer step.
-    `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce."""
+def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync):
+    """the step around a model family's forward_losses: zero_grad, forward, backward, gradient sync, message-id check, update"""
     optimizer.zero_grad(set_to_none=not hasattr(optimizer, "flat"))
     if hasattr(grad_sync, "begin_step"):
         grad_sync.begin_step()
-    from . import ops
     try:
-        with ops.index_check_mode("deferred" if ops._CHECK_INDEX["mode"] == "sync" else ops._CHECK_INDEX["mode"]):
+        with ops.index_check_mode():
             total, out = forward_losses(generator, detector, s, message)   # no mid-step sync for the message-id range check ...
         total.backward()
         if hasattr(optimizer, "finish_backward"):
@@ -59,13 +57,18 @@ def train_step(generator, detector, optimizer, s, message, grad_sync=None):
     return out
 
 
+def train_step(generator, detector, optimizer, s, message, grad_sync=None):
+    """One iteration of train_one_epoch's loop body (:242-278): zero_grad, forward, backward, optimizer step.
+    `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce."""
+    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync)
+
+
 @torch.no_grad()
 def eval_forward(generator, detector, s, message):
     """evaluate_model's per-batch quantities (:383-403).  In eval mode BatchNorm uses running statistics, so the Detector's
     rows are independent: the clean half D(s) does not wait for the Generator -- it is queued for the side stream and released
     when the Generator reaches its latency-bound LSTM (B clips keep only B of the 256 CUs busy there), and the two halves are
     concatenated afterwards (bit-identical to the single 2B-row call)."""
-    from . import ops
     B = s.shape[0]
     overlap = (not generator.training) and (not detector.training) and s.is_cuda
     box = {}

@@ -92,15 +92,11 @@ def test_gconv_f16_split_is_fp32_grade(M, cin, cout, k, stride, pad, L, gscale):
     zr = F.conv1d(xr, wr, b.double(), stride=stride, padding=pad)
     (dxr,) = torch.autograd.grad(zr, xr, g.double())
     outs = []
-    try:
-        for h in (False, True):
-            M.set_gconv_f16x3(h)
-            with torch.no_grad():
-                y = M._gconv(x.to(dev), w.to(dev), b.to(dev), stride, pad, act=1) if gscale == 1.0 else None
-                dx = M._conv_dgrad(g.to(dev), w.to(dev), stride, pad, L)
-            outs.append((y, dx))
-    finally:
-        M.set_gconv_f16x3(True)
+    for h in (False, True):
+        with torch.no_grad(), M.ops.switches(gconv_f16x3=h):
+            y = M._gconv(x.to(dev), w.to(dev), b.to(dev), stride, pad, act=1) if gscale == 1.0 else None
+            dx = M._conv_dgrad(g.to(dev), w.to(dev), stride, pad, L)
+        outs.append((y, dx))
     for name, a, h_, r in (("y", outs[0][0], outs[1][0], yr), ("dx", outs[0][1], outs[1][1], dxr)):
         if a is None:
             continue

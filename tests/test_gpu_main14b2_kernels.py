@@ -412,12 +412,11 @@ RB_SHAPES = [(32, 64, 2, 1002), (64, 128, 4, 1001), (128, 256, 5, 402), (256, 51
 @pytest.mark.parametrize("cin,cout,stride,L", RB_SHAPES)
 @pytest.mark.parametrize("fused", [True, False])
 @pytest.mark.parametrize("h", [True, False])
-def test_residual_block_fn_vs_fp64(M, monkeypatch, cin, cout, stride, L, fused, h):
+def test_residual_block_fn_vs_fp64(M, cin, cout, stride, L, fused, h):
     """every (Cin, Cout, stride) block the Generator / Detector build, at ragged lengths; fused strided data gradient on / off,
     f16 split on / off: output, dx and all six parameter gradients"""
     if not fused and not (stride >= 3 and cin != cout):
         pytest.skip("the fused strided data gradient only exists for down-sampling blocks with stride >= 3")
-    monkeypatch.setattr(M, "_FUSED_STRIDED_DGRAD", fused)
     skip = stride != 1 or cin != cout
     s = cin * 7 + cout + stride
     w1, b1 = _uni(cout, cin, 3, fan_in=cin * 3, seed=s), _uni(cout, fan_in=cin * 3, seed=s + 1)
@@ -432,12 +431,9 @@ def test_residual_block_fn_vs_fp64(M, monkeypatch, cin, cout, stride, L, fused, 
     gy = rnd(*yr.shape, seed=s + 7)
     yr.backward(gy.double())
     xd, pd = x.to(DEV).requires_grad_(), [p.to(DEV).requires_grad_() for p in params]
-    M.set_gconv_f16x3(h)
-    try:
+    with M.ops.switches(gconv_f16x3=h, fused_strided_dgrad=fused):
         y = M.ResidualBlockFn.apply(xd, pd[0], pd[1], pd[2], pd[3], pd[4] if skip else None, pd[5] if skip else None, stride)
         y.backward(gy.to(DEV))
-    finally:
-        M.set_gconv_f16x3(True)
     check_elementwise(y, yr, "y")
     check_elementwise(xd.grad, xr.grad, "dx")
     for n, a, r in zip(("dw1", "db1", "dw2", "db2", "dws", "dbs"), pd, pr):
@@ -577,12 +573,8 @@ def test_gconv_h_activation_scale(M, cin, cout, k, stride, pad, L, xs):
     ref = F.elu(F.conv1d(x.double(), w.double(), b.double(), stride=stride, padding=pad))
 
     def run(h):
-        M.set_gconv_f16x3(h)
-        try:
-            with torch.no_grad():
-                return M._gconv(x.to(DEV), w.to(DEV), b.to(DEV), stride, pad, act=1)
-        finally:
-            M.set_gconv_f16x3(True)
+        with torch.no_grad(), M.ops.switches(gconv_f16x3=h):
+            return M._gconv(x.to(DEV), w.to(DEV), b.to(DEV), stride, pad, act=1)
     _f16_vs_fp32(run, ref, f"{cin}>{cout} k{k} s{stride} x {xs}")
 
 
@@ -595,11 +587,8 @@ def test_gconvT_activation_scale(M, cin, cout, st, L, xs):
     ref = F.conv_transpose1d(x.double(), w.double(), b.double(), stride=st, padding=st // 2)
 
     def run(h):
-        M.set_gconv_f16x3(h)
-        try:
+        with M.ops.switches(gconv_f16x3=h):
             return M._gconvT(x.to(DEV), w.to(DEV), b.to(DEV), st)
-        finally:
-            M.set_gconv_f16x3(True)
     _f16_vs_fp32(run, ref, f"convT {cin}>{cout} st{st} x {xs}")
 
 
@@ -612,11 +601,8 @@ def test_lstm_input_projection_activation_scale(M, xs):
     ref = torch.einsum("gh,thb->tgb", w.double(), seq.double()) + b.double()[None, :, None]
 
     def run(h):
-        M.set_gconv_f16x3(h)
-        try:
+        with M.ops.switches(gconv_f16x3=h):
             return M._lstm_proj(seq.to(DEV), w.to(DEV), b.to(DEV))
-        finally:
-            M.set_gconv_f16x3(True)
     _f16_vs_fp32(run, ref, f"lstm projection x {xs}")
 
 

@@ -166,17 +166,16 @@ def test_resblock_inference_fused_epilogue(awm, dev, B, T, one_launch):
         whole.append((a[10], a[11]))                          # B, T
         return orig_rb(*a)
     awm.lib.wm_conv64_bf, awm.lib.wm_resblock_eval_bf = spy, spy_rb
-    awm.ops.set_resblock_one_launch(one_launch)
     try:
-        with torch.no_grad():
-            y_fused = m(x.to(dev))
-        fused_calls, fused_whole = list(calls), list(whole)
-        del calls[:], whole[:]
-        y_unfused = m(x.to(dev).requires_grad_())          # grad mode on + an input gradient wanted -> the unfused path
-        unfused_calls, unfused_whole = list(calls), list(whole)
+        with awm.ops.switches(one_launch_eval=one_launch):
+            with torch.no_grad():
+                y_fused = m(x.to(dev))
+            fused_calls, fused_whole = list(calls), list(whole)
+            del calls[:], whole[:]
+            y_unfused = m(x.to(dev).requires_grad_())          # grad mode on + an input gradient wanted -> the unfused path
+            unfused_calls, unfused_whole = list(calls), list(whole)
     finally:
         awm.lib.wm_conv64_bf, awm.lib.wm_resblock_eval_bf = orig, orig_rb
-        awm.ops.set_resblock_one_launch(True)
     if awm.ops.conv_bf16x6():
         # under no_grad the fast path is taken although ctx.needs_input_grad reports the trainable parameters; with the tape
         # recording neither fused form is used
@@ -213,12 +212,10 @@ def test_resblock_eval_f16_split_matches_bf16x6(awm, dev, B, T):
     awm.lib.wm_resblock_eval_bf = spy
     try:
         for h in (False, True):
-            awm.ops.set_eval_f16x3(h)
-            with torch.no_grad():
+            with torch.no_grad(), awm.ops.switches(eval_f16x3=h):
                 ys.append(m(x.to(dev)))
     finally:
         awm.lib.wm_resblock_eval_bf = orig
-        awm.ops.set_eval_f16x3(True)
     assert ar == [0, 1], ar
     assert rel_err(ys[1], ys[0]) < 2e-6, rel_err(ys[1], ys[0])
     yr = O.resblock({k: v.clone() for k, v in sd.items()}, "", x, False, {})
@@ -319,6 +316,30 @@ def test_resblock(awm, dev, training, B, T):
                 assert int(st[k]) == int(v)
 
 
+@pytest.mark.parametrize("pair", [False, True])
+def test_resblock_releases_its_activations_after_backward(awm, dev, pair):
+    """After backward() nothing a ResBlock saved may stay allocated while its output is still held (a training loop keeps the
+    step's outputs across the next forward): the node hands its tensors to save_for_backward only, never to a ctx attribute.
+    One frame is F = B*64*T*4 bytes = 8 MiB here.  New since the first reading: `out` and `x.grad` (2 F), parameter gradients and
+    scratch (well under 1 MiB) -- so below 2.5 F.  Saved activations kept alive would add y1 and y2 of every block (>= 4 F on top
+    for one block, >= 7 F for the pair node with its mid activation)."""
+    from awm_amd.modules import resblock_pair
+    B, T = 8, 4096
+    frame = B * 64 * T * 4
+    ms = [awm.ResBlock(64).to(dev).train() for _ in range(2 if pair else 1)]
+    x = (rnd(B, 64, T, seed=13).abs() * 0.7).to(dev).requires_grad_()
+    g = rnd(B, 64, T, seed=14).to(dev)
+    torch.cuda.synchronize()
+    m0 = torch.cuda.memory_allocated()
+    out = resblock_pair(ms[0], ms[1], x) if pair else ms[0](x)
+    out.backward(g)
+    torch.cuda.synchronize()
+    m1 = torch.cuda.memory_allocated()
+    print(f"{type(out.grad_fn).__name__}: {(m1 - m0) / frame:.3f} F allocated after backward with the output held")
+    assert x.grad is not None and out.grad_fn is not None
+    assert m1 - m0 < 2.5 * frame, f"{(m1 - m0) / frame:.3f} F still allocated after backward (out + x.grad = 2 F)"
+
+
 @pytest.mark.parametrize("B,T", [(1, 64), (2, 128), (3, 640)])
 def test_resblock_backward_fused_vs_two_launches(awm, dev, B, T):
     """ResBlock backward with each convolution's data + weight gradient in ONE launch (wm_dwgrad64_bf, the default for
@@ -336,19 +357,18 @@ def test_resblock_backward_fused_vs_two_launches(awm, dev, B, T):
     awm.lib.wm_dwgrad64_bf = spy
     try:
         for fused in (True, False):
-            awm.ops.set_fused_backward(fused)
-            del calls[:]
-            m = awm.ResBlock(64)
-            m.load_state_dict(sd)
-            m.to(dev).train()
-            xd = x.to(dev).requires_grad_()
-            m(xd).backward(g.to(dev))
-            res[fused] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
-            if awm.ops.conv_bf16x6():
-                assert calls == ([(1, 1), (0, 2)] if fused else []), (fused, calls)
+            with awm.ops.switches(fused_bwd=fused):
+                del calls[:]
+                m = awm.ResBlock(64)
+                m.load_state_dict(sd)
+                m.to(dev).train()
+                xd = x.to(dev).requires_grad_()
+                m(xd).backward(g.to(dev))
+                res[fused] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
+                if awm.ops.conv_bf16x6():
+                    assert calls == ([(1, 1), (0, 2)] if fused else []), (fused, calls)
     finally:
         awm.lib.wm_dwgrad64_bf = orig
-        awm.ops.set_fused_backward(True)
     wmax = float(res[False]["block.0.weight"].abs().max())
     for k in res[True]:
         if k.endswith("block.0.bias") or k.endswith("block.3.bias"):
@@ -407,18 +427,17 @@ def test_resblock_backward_mask_on_load_is_bit_identical(awm, dev, B, T):
     awm.lib.wm_dwgrad64_bf = spy
     try:
         for on in (True, False):
-            awm.ops.set_mask_on_load(on)
-            del seen[:]
-            m = awm.ResBlock(64)
-            m.load_state_dict(sd)
-            m.to(dev).train()
-            xd = x.to(dev).requires_grad_()
-            m(xd).backward(g.to(dev))
-            assert seen == [on, on], seen
-            res[on] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
+            with awm.ops.switches(mask_on_load=on):
+                del seen[:]
+                m = awm.ResBlock(64)
+                m.load_state_dict(sd)
+                m.to(dev).train()
+                xd = x.to(dev).requires_grad_()
+                m(xd).backward(g.to(dev))
+                assert seen == [on, on], seen
+                res[on] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
     finally:
         awm.lib.wm_dwgrad64_bf = orig
-        awm.ops.set_mask_on_load(True)
     for k in res[True]:
         assert torch.equal(res[True][k], res[False][k]), (k, float((res[True][k] - res[False][k]).abs().max()))
 
@@ -445,18 +464,17 @@ def test_resblock_backward_f16_split_is_fp32_grade(awm, dev, B, T, gscale):
     awm.lib.wm_dwgrad64_bf = spy
     try:
         for on in (True, False):
-            awm.ops.set_bwd_f16x3(on)
-            del ar[:]
-            m = awm.ResBlock(64)
-            m.load_state_dict(sd)
-            m.to(dev).train()
-            xd = x.to(dev).requires_grad_()
-            m(xd).backward(g.to(dev))
-            assert ar == [int(on)] * 2, ar
-            res[on] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
+            with awm.ops.switches(bwd_f16x3=on):
+                del ar[:]
+                m = awm.ResBlock(64)
+                m.load_state_dict(sd)
+                m.to(dev).train()
+                xd = x.to(dev).requires_grad_()
+                m(xd).backward(g.to(dev))
+                assert ar == [int(on)] * 2, ar
+                res[on] = {"dx": xd.grad.clone(), **{k: p.grad.clone() for k, p in m.named_parameters()}}
     finally:
         awm.lib.wm_dwgrad64_bf = orig
-        awm.ops.set_bwd_f16x3(True)
     wmax = float(res[False]["block.0.weight"].abs().max())
     for k in res[True]:
         a, b = res[True][k], res[False][k]
@@ -487,21 +505,20 @@ def test_resblock_pair_fold_matches_two_nodes(awm, dev, B, T):
     awm.lib.wm_dwgrad64_bf = spy
     try:
         for on in (True, False):
-            awm.ops.set_pair_fold(on)
-            del epis[:]
-            m1, m2 = awm.ResBlock(64), awm.ResBlock(64)
-            m1.load_state_dict(sd1); m2.load_state_dict(sd2)
-            m1.to(dev).train(); m2.to(dev).train()
-            xd = x.to(dev).requires_grad_()
-            out = resblock_pair(m1, m2, xd)
-            out.backward(g.to(dev))
-            assert epis == ([1, 8, 1, 2] if on else [1, 2, 1, 2]), (on, epis)
-            res[on] = {"out": out.detach().clone(), "dx": xd.grad.clone(),
-                       **{f"1.{k}": p.grad.clone() for k, p in m1.named_parameters()}, **{f"2.{k}": p.grad.clone() for k, p in m2.named_parameters()},
-                       **{f"1.{k}": v.clone() for k, v in m1.state_dict().items() if "running" in k or "tracked" in k}}
+            with awm.ops.switches(pair_fold=on):
+                del epis[:]
+                m1, m2 = awm.ResBlock(64), awm.ResBlock(64)
+                m1.load_state_dict(sd1); m2.load_state_dict(sd2)
+                m1.to(dev).train(); m2.to(dev).train()
+                xd = x.to(dev).requires_grad_()
+                out = resblock_pair(m1, m2, xd)
+                out.backward(g.to(dev))
+                assert epis == ([1, 8, 1, 2] if on else [1, 2, 1, 2]), (on, epis)
+                res[on] = {"out": out.detach().clone(), "dx": xd.grad.clone(),
+                           **{f"1.{k}": p.grad.clone() for k, p in m1.named_parameters()}, **{f"2.{k}": p.grad.clone() for k, p in m2.named_parameters()},
+                           **{f"1.{k}": v.clone() for k, v in m1.state_dict().items() if "running" in k or "tracked" in k}}
     finally:
         awm.lib.wm_dwgrad64_bf = orig
-        awm.ops.set_pair_fold(True)
     assert torch.equal(res[True]["out"], res[False]["out"])
     wmax = float(res[False]["1.block.0.weight"].abs().max())
     for k in res[True]:
@@ -559,14 +576,11 @@ def test_convT_f16_split_is_fp32_grade(awm, dev, gscale):
     yr.backward(g.double())
     res = []
     for h in (False, True):
-        ops.set_conv7_f16x3(h)
-        try:
+        with ops.switches(conv7_f16x3=h):
             xd, wd, bd = (t.to(dev).requires_grad_() for t in (x, w, b))
             y = ops.ConvT7Fn.apply(xd, vec.to(dev), wd, bd)
             y.backward(g.to(dev))
             res.append((y.detach(), xd.grad, wd.grad, bd.grad))
-        finally:
-            ops.set_conv7_f16x3(True)
     for name, a, h_, r in zip(("y", "dx", "dw", "db"), res[0], res[1], (yr, xr.grad, wr.grad, br.grad)):
         e_b, e_h = rel_err(a, r), rel_err(h_, r)
         print(f"g x {gscale:g} {name}: bf16x6 {e_b:.2e} f16 {e_h:.2e}")
@@ -642,12 +656,10 @@ def test_lstm_small(awm, dev, B, T):
 
 @pytest.mark.parametrize("fwd_fused,bwd_fused", [(False, False), (True, True), (False, True)])
 @pytest.mark.parametrize("B,T", [(2, 200), (1, 36)])
-def test_lstm_launch_variants(awm, dev, monkeypatch, fwd_fused, bwd_fused, B, T):
+def test_lstm_launch_variants(awm, dev, fwd_fused, bwd_fused, B, T):
     """every C-ABI route through the LSTM (wm_lstm_xproj + wm_lstm_fwd | wm_lstm_fwd_fused; wm_lstm_bwd + wm_lstm_dx |
     wm_lstm_bwd_fused) against the oracle, on lengths that leave ragged 32-step chunks and 16-step groups"""
     from awm_amd import ops
-    monkeypatch.setattr(ops, "_LSTM_FUSED", fwd_fused)
-    monkeypatch.setattr(ops, "_LSTM_BWD_FUSED", bwd_fused)
     g = torch.Generator().manual_seed(40)
     k = 1.0 / 8.0
     wi, wh = (torch.rand(256, 64, generator=g) * 2 - 1) * k, (torch.rand(256, 64, generator=g) * 2 - 1) * k
@@ -658,11 +670,12 @@ def test_lstm_launch_variants(awm, dev, monkeypatch, fwd_fused, bwd_fused, B, T)
     gg = rnd(B, 64, T, seed=42)
     hr.backward(gg)
     xd, wid, whd, bid, bhd = (t.to(dev).requires_grad_() for t in (x, wi, wh, bi, bh))
-    h = ops.LSTMFn.apply(xd, wid, whd, bid, bhd)
-    check(h, hr, FWD_TOL, "lstm fwd")
-    with torch.no_grad():
-        check(ops.LSTMFn.apply(x.to(dev), wid.detach(), whd.detach(), bid.detach(), bhd.detach()), hr, FWD_TOL, "lstm fwd (inference)")
-    h.backward(gg.to(dev))
+    with ops.switches(lstm_fused=fwd_fused, lstm_bwd_fused=bwd_fused):
+        h = ops.LSTMFn.apply(xd, wid, whd, bid, bhd)
+        check(h, hr, FWD_TOL, "lstm fwd")
+        with torch.no_grad():
+            check(ops.LSTMFn.apply(x.to(dev), wid.detach(), whd.detach(), bid.detach(), bhd.detach()), hr, FWD_TOL, "lstm fwd (inference)")
+        h.backward(gg.to(dev))
     check(xd.grad, xr.grad, GRAD_TOL, "lstm dx")
     check(wid.grad, wir.grad, GRAD_TOL, "lstm dW_ih")
     check(whd.grad, whr.grad, GRAD_TOL, "lstm dW_hh")
@@ -692,9 +705,9 @@ def test_lstm_bwd_wave_specialised(awm, dev, monkeypatch, B, T):
         return orig(*a)
     monkeypatch.setattr(awm.lib, "wm_lstm_bwd_wgrad", spy)
     for ws in (True, False):
-        monkeypatch.setitem(ops._LSTM, "bwd_ws", ws)
         xd, wid, whd, bid, bhd = (t.to(dev).requires_grad_() for t in (x, wi, wh, bi, bh))
-        ops.LSTMFn.apply(xd, wid, whd, bid, bhd).backward(gg.to(dev))
+        with ops.switches(lstm_bwd_ws=ws):
+            ops.LSTMFn.apply(xd, wid, whd, bid, bhd).backward(gg.to(dev))
         grads.append([t.grad.clone() for t in (xd, wid, whd, bid, bhd)])
     assert len(calls) == 1, "the wave-specialised launch did not run"
     for name, a, r in zip(("dx", "dW_ih", "dW_hh", "db_ih", "db_hh"), grads[0], (xr, wir, whr, bir, bhr)):
@@ -717,17 +730,14 @@ def test_lstm_fwd_wave_specialised_is_bit_identical(awm, dev, B, T):
     bi, bh = ((torch.rand(256, generator=g) * 2 - 1) * k).to(dev), ((torch.rand(256, generator=g) * 2 - 1) * k).to(dev)
     x = rnd(B, 64, T, seed=56).to(dev)
     outs = []
-    try:
-        for ws in (True, False):
-            ops.set_lstm_fwd_wave_specialised(ws)
+    for ws in (True, False):
+        with ops.switches(lstm_fwd_ws=ws):
             for save in (True, False):
                 h = torch.full((B, 64, T), float("nan"), device=dev)
                 gates = torch.full((B, T, 256), float("nan"), device=dev) if save else None
                 cst = torch.full((B, T, 64), float("nan"), device=dev) if save else None
                 lib.wm_lstm_fwd_fused(_p(x), _p(wi), _p(bi), _p(bh), _p(wh), _p(h), _p(gates), _p(cst), B, T, _stream())
                 outs.append((h, gates, cst))
-    finally:
-        ops.set_lstm_fwd_wave_specialised(True)
     for a, b_ in ((outs[0], outs[2]), (outs[1], outs[3])):
         for t_a, t_b in zip(a, b_):
             if t_a is not None:
@@ -925,10 +935,8 @@ def test_all_grads_vs_oracle(awm, dev):
     d3 = {k: v.clone().requires_grad_(v.dtype.is_floating_point and "running" not in k) for k, v in dsd.items()}
     tot_c, _ = O.step_losses(g3, d3, s, msg, training=True, g_stats={}, d_stats={})
     tot_c.backward()
-    prev = ops.conv_bf16x6()
-    try:
-        for mode in (True, False):
-            ops.set_conv_bf16x6(mode)
+    for mode in (True, False):
+        with ops.switches(bf16x6=mode):
             G, D, _, _ = make_models(awm, dev, gsd, dsd)
             G.train(); D.train()
             total, out = awm.forward_losses(G, D, s.to(dev), msg.to(dev))
@@ -964,8 +972,6 @@ def test_all_grads_vs_oracle(awm, dev):
             assert not bad, "gradients outside the bar (ratio, name, hip-vs-fp64, cpu32-vs-fp64), bf16x6=%s: %s" % (
                 mode, sorted(bad, reverse=True)[:8])
             print("worst grad rel err vs fp64", worst, "bf16x6 =", mode)
-    finally:
-        ops.set_conv_bf16x6(prev)
 
 
 def _dft_logmel(x, n_fft=1024, hop=256):
@@ -1060,10 +1066,8 @@ def test_all_grads_smooth_functional(awm, dev):
 
     def total_of(o, msq, K):
         return W["l1"] * o["l1"] + W["mel"] * K * msq + W["loud"] * o["loud"] + W["loc"] * o["loc"] + W["bce"] * o["bce"] + W["hf"] * o["hf"]
-    prev = ops.conv_bf16x6()
-    try:
-        for mode in (True, False):
-            ops.set_conv_bf16x6(mode)
+    for mode in (True, False):
+        with ops.switches(bf16x6=mode):
             G, D, out, sites = hip_run()
             g2, d2, o2, msq2 = cpu_run(torch.float64, sites)
             K = float(o2["mel"].detach() / msq2.detach())                       # surrogate term as large as the term it replaces
@@ -1096,8 +1100,6 @@ def test_all_grads_smooth_functional(awm, dev):
             assert not bad, "smooth-functional gradients outside max(2 x e_cpu, %g) (ratio, name, hip-vs-fp64, cpu32-vs-fp64), bf16x6=%s: %s" % (
                 GRAD_FLOOR, mode, sorted(bad, reverse=True)[:8])
             print("smooth functional: worst ratio to the bar", max(t[0] for t in table), "bf16x6 =", mode)
-    finally:
-        ops.set_conv_bf16x6(prev)
 
 
 @pytest.mark.parametrize("B,T", [(3, 4000), (2, 16000)])
