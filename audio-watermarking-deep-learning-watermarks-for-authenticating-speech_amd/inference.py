@@ -2,7 +2,8 @@
 models at B=1 per segment in a Python loop (py/main16.py:977-1066, :1114-1207, :723-762).  Here ALL segments of a
 recording go through the HIP path as one [N,1,16000] batch; per-segment random messages, remainder pad/trim and the
 returned dict schemas are the reference's.  Like the reference's wrappers (and unlike its training loop) no
-fir/clamp/rms post-processing is applied to delta."""
+fir/clamp/rms post-processing is applied to delta.  A recording that is not at 16 kHz is mixed down,
+resampled and cut into those segments by one launch (`orig_freq=`, ops.resample; `resample` / `Resample` / `load_audio` here)."""
 from __future__ import annotations
 
 import math
@@ -16,9 +17,59 @@ import torch.nn.functional as F
 SAMPLE_RATE = 16000
 
 
-def load_audio(file_path, sample_rate=SAMPLE_RATE):
-    """(1, N) fp32 mono waveform.  Uses torchaudio when it is installed (the reference's loader, :714-720); otherwise
-    16-bit PCM .wav files at the target rate are read with the standard library."""
+def _as_channels(waveform):
+    """(N,) or (C, N) -> (C, N) float32"""
+    if not isinstance(waveform, torch.Tensor):
+        raise TypeError(f"waveform: expected a tensor, got {type(waveform).__name__}")
+    x = waveform.unsqueeze(0) if waveform.dim() == 1 else waveform
+    if x.dim() != 2:
+        raise ValueError(f"waveform: expected (channels, samples) or (samples,), got shape {tuple(waveform.shape)}")
+    return x.to(torch.float32)
+
+
+def resample(waveform, orig_freq, new_freq):
+    """torchaudio.functional.resample(waveform, orig_freq, new_freq) with its documented defaults (sinc_interp_hann,
+    lowpass_filter_width=6, rolloff=0.99), restated from the published description (ops.resample_table), preceded by the mono
+    mixdown every file-level entry point of the reference applies first (py/main16.py:717-720): a (C, N) or (N,) waveform
+    becomes (1, ceil(new * N / orig)).  A CUDA tensor goes to the HIP kernel (ops.resample); a CPU tensor goes through the same
+    float32 table as one strided F.conv1d -- the only CPU arithmetic here, it is what lets load_audio read a 48 kHz file on a
+    machine without a GPU.  Equal rates return the waveform unchanged.
+    PARITY WITH TORCHAUDIO UNPINNED: torchaudio is absent from this image; tests/test_resample_cpu.py pins it on the first
+    machine that has it."""
+    from . import ops
+    tab = ops.resample_table(orig_freq, new_freq)
+    if tab["K"] == 1:
+        return waveform
+    x = _as_channels(waveform)
+    if x.is_cuda:
+        return ops.resample(x, orig_freq, new_freq)
+    # channels added in float64, one rounding to float32 (as the kernel does): the mean's error is an ulp of the mean, also where channels cancel
+    mono = x.double().mean(dim=0, keepdim=True).float() if x.shape[0] > 1 else x
+    P, Q, width = tab["P"], tab["Q"], tab["width"]
+    n = mono.shape[1]
+    padded = F.pad(mono, (width, width + P))
+    y = F.conv1d(padded[None], tab["dense"][:, None, :], stride=P)                 # (1, Q, n // P + 1): [phase][period]
+    return y.transpose(1, 2).reshape(1, -1)[:, :ops.resample_length(n, orig_freq, new_freq)].contiguous()
+
+
+class Resample(torch.nn.Module):
+    """torchaudio.transforms.Resample(orig_freq, new_freq) for code written against it: calls `resample`"""
+
+    def __init__(self, orig_freq=SAMPLE_RATE, new_freq=SAMPLE_RATE):
+        super().__init__()
+        from . import ops
+        ops.resample_table(orig_freq, new_freq)          # bad rates fail here, as torchaudio's constructor does
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+
+    def forward(self, waveform):
+        return resample(waveform, self.orig_freq, self.new_freq)
+
+
+def load_audio(file_path, sample_rate=SAMPLE_RATE, device=None):
+    """(1, N) fp32 mono waveform at `sample_rate`.  Uses torchaudio when it is installed (the reference's loader, :714-720).
+    Otherwise .wav files (16- / 24-bit PCM, 32-bit float, plain or WAVE_FORMAT_EXTENSIBLE header) are read with the standard
+    library, mixed down to mono and, when the file is at another rate, resampled with `resample`.  `device` (e.g. "cuda"):
+    the decoded (C, N) samples are uploaded once and mixdown + resampling run on the GPU; the result stays there."""
     try:
         import torchaudio  # noqa: F401
         waveform, sr = torchaudio.load(file_path)
@@ -26,40 +77,55 @@ def load_audio(file_path, sample_rate=SAMPLE_RATE):
             waveform = waveform.mean(dim=0, keepdim=True)
         if sr != sample_rate:
             waveform = torchaudio.transforms.Resample(sr, sample_rate)(waveform)
-        return waveform
+        return waveform if device is None else waveform.to(device)
     except ImportError:
         data, rate = _read_wav(file_path)
+        if device is not None and torch.device(device).type != "cpu":
+            x = torch.from_numpy(np.ascontiguousarray(data.T)).to(device)
+            if rate != sample_rate:
+                return resample(x, rate, sample_rate)
+            return x.mean(dim=0, keepdim=True) if x.shape[0] > 1 else x
         if rate != sample_rate:
-            raise ValueError(f"without torchaudio no resampling is available (file is {rate} Hz)")
+            return resample(torch.from_numpy(np.ascontiguousarray(data.T)), rate, sample_rate)
         return torch.from_numpy(data.mean(axis=1).astype(np.float32)).unsqueeze(0)
 
 
 def _read_wav(path):
-    """RIFF/WAVE reader for the two encodings this package writes: 16-bit signed PCM (format 1, scaled by 1/32768 as
-    torchaudio.load normalises it) and 32-bit IEEE float (format 3).  Returns ((frames, channels) float32, sample rate)."""
+    """RIFF/WAVE reader: 16-bit and 24-bit signed PCM (format 1, scaled by 1/32768 and 1/2**23 as torchaudio.load normalises
+    them) and 32-bit IEEE float (format 3), under a plain header or WAVE_FORMAT_EXTENSIBLE (format 0xFFFE, where the first two
+    bytes of the sub-format GUID carry the code).  Returns ((frames, channels) float32, sample rate)."""
     import struct
     with open(path, "rb") as f:
         blob = f.read()
     if blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
         raise ValueError(f"{path}: not a RIFF/WAVE file")
-    pos, fmt, data = 12, None, None
+    pos, fmt, data, ext = 12, None, None, None
     while pos + 8 <= len(blob):
         tag, size = blob[pos:pos + 4], struct.unpack("<I", blob[pos + 4:pos + 8])[0]
         body = blob[pos + 8:pos + 8 + size]
         if tag == b"fmt ":
             fmt = struct.unpack("<HHIIHH", body[:16])
+            ext = struct.unpack("<H", body[24:26])[0] if len(body) >= 40 else None
         elif tag == b"data":
             data = body
         pos += 8 + size + (size & 1)
     if fmt is None or data is None:
         raise ValueError(f"{path}: missing fmt or data chunk")
     code, channels, rate, _, _, bits = fmt
+    if code == 0xFFFE:
+        if ext is None:
+            raise ValueError(f"{path}: WAVE_FORMAT_EXTENSIBLE header without a sub-format")
+        code = ext
     if code == 1 and bits == 16:
         x = np.frombuffer(data, dtype="<i2").astype(np.float32) / 32768.0
+    elif code == 1 and bits == 24:
+        b = np.frombuffer(data[:len(data) - len(data) % 3], dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0
     elif code == 3 and bits == 32:
         x = np.frombuffer(data, dtype="<f4").astype(np.float32)
     else:
-        raise ValueError("without torchaudio only 16-bit PCM and 32-bit float wav files can be read")
+        raise ValueError("without torchaudio only 16- / 24-bit PCM and 32-bit float wav files can be read")
     return x.reshape(-1, channels), rate
 
 
@@ -137,6 +203,21 @@ def _segments(waveform, seg_len=SAMPLE_RATE):
     return torch.stack(segs, dim=0), remainder
 
 
+def _ingest(waveform, orig_freq, device, seg_len=SAMPLE_RATE):
+    """(segments [S,1,seg_len], remainder, the (1, n) waveform at the model rate) for a wrapper's `waveform` argument.
+    orig_freq None (or already the model rate): the (1, N) waveform is cut on the host, as before.  Any other rate: the
+    (C, N) waveform at that rate is uploaded once and ops.resample does mixdown, resampling, tail padding and segment
+    stacking in one launch; the segments stay on the device and the 16 kHz waveform is a view of them."""
+    if orig_freq is None or int(orig_freq) == seg_len:
+        segs, remainder = _segments(waveform.float(), seg_len)
+        return segs, remainder, waveform
+    from . import ops
+    x = _as_channels(waveform).to(device)
+    segs = ops.resample(x, orig_freq, seg_len, seg_len=seg_len)
+    n = ops.resample_length(x.shape[1], orig_freq, seg_len)
+    return segs, n % seg_len, segs.reshape(1, -1)[:, :n]
+
+
 def _si_snr_db(ref, est, eps):
     """scale-invariant SNR in dB along axis 1: both signals centred, `est` split into its projection on `ref` and the rest,
     10 log10 of the energy ratio (eps added to the projection's denominator and to the residual energy, as py/main16.py:764-773)"""
@@ -154,13 +235,15 @@ def compute_si_snr(s, s_hat, eps=1e-8):
 
 
 @torch.no_grad()
-def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages=None, max_batch=512):
+def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages=None, max_batch=512, orig_freq=None):
     """process_audio_file_with_delta (:723-762) on an in-memory waveform, batched.
-    Returns (watermarked_waveform, delta_waveform, original_waveform), each (1, N) on the CPU."""
+    Returns (watermarked_waveform, delta_waveform, original_waveform), each (1, N) on the CPU.  `orig_freq`: the rate of a
+    (C, N) waveform that is not at 16 kHz yet (see _ingest); the three returned waveforms are at 16 kHz, as the reference's."""
     generator.eval()
-    segs, remainder = _segments(waveform.float())
+    segs, remainder, waveform = _ingest(waveform, orig_freq, device)
     S = segs.shape[0]
     if S == 0:
+        waveform = waveform.cpu()
         return waveform.clone(), torch.zeros_like(waveform), waveform
     if messages is None:       # a fresh random message per second, as :1001
         messages = torch.randint(0, 2 ** message_bits, (S,), device=device)
@@ -169,17 +252,21 @@ def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages
         x = segs[i:i + max_batch].to(device)
         deltas.append(generator(x, messages[i:i + max_batch].to(device)).cpu())
     delta = torch.cat(deltas, dim=0)                    # [S,1,16000]
-    wm = segs + delta
+    wm = segs.cpu() + delta
     n = waveform.shape[1]
     delta_w = delta.reshape(1, -1)[:, :n]
     wm_w = wm.reshape(1, -1)[:, :n]
-    return wm_w, delta_w, waveform
+    return wm_w, delta_w, waveform.cpu()
 
 
-def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda"):
-    """py/main16.py:977-1066 with one batched Generator call; same result dict."""
-    waveform = load_audio(input_file) if isinstance(input_file, (str, os.PathLike)) else input_file
-    wm, delta, orig = embed_waveform(waveform, generator, message_bits=message_bits, device=device)
+def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None):
+    """py/main16.py:977-1066 with one batched Generator call; same result dict.  A path is loaded (and resampled) by
+    load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz."""
+    if isinstance(input_file, (str, os.PathLike)):
+        waveform, orig_freq = load_audio(input_file), None
+    else:
+        waveform = input_file
+    wm, delta, orig = embed_waveform(waveform, generator, message_bits=message_bits, device=device, orig_freq=orig_freq)
     watermark_rms = torch.sqrt((delta ** 2).mean()).item()
     si_snr = compute_si_snr(orig, wm)
     power_ratio_db = 10 * np.log10(torch.mean(orig ** 2).item() / max(torch.mean(delta ** 2).item(), 1e-30))
@@ -190,12 +277,13 @@ def generate_watermarked_audio(input_file, generator, output_file=None, message_
 
 
 @torch.no_grad()
-def detect_waveform(waveform, detector, detection_threshold=0.5, device="cuda", max_batch=512):
+def detect_waveform(waveform, detector, detection_threshold=0.5, device="cuda", max_batch=512, orig_freq=None):
     """detect_watermark (:1114-1207) on an in-memory waveform, batched; same result dict (no plotting).  The
     per-segment reductions run on the device: only the temporal probability track the reference returns ((N,) floats)
-    and 1+bits scalars cross to the host, never the [S,T,1+bits] logits."""
+    and 1+bits scalars cross to the host, never the [S,T,1+bits] logits.  `orig_freq`: the rate of a (C, N) waveform that is
+    not at 16 kHz yet (see _ingest); the temporal track is then at 16 kHz."""
     detector.eval()
-    segs, remainder = _segments(waveform.float())
+    segs, remainder, waveform = _ingest(waveform, orig_freq, device)
     S = segs.shape[0]
     n = waveform.shape[1]
     bits = int(getattr(detector, "message_bits", 0))
@@ -222,19 +310,25 @@ def detect_waveform(waveform, detector, detection_threshold=0.5, device="cuda", 
     return result
 
 
-def detect_watermark(input_file, detector, detection_threshold=0.5, visualize=False, device="cuda"):
-    waveform = load_audio(input_file) if isinstance(input_file, (str, os.PathLike)) else input_file
-    return detect_waveform(waveform, detector, detection_threshold, device)
+def detect_watermark(input_file, detector, detection_threshold=0.5, visualize=False, device="cuda", orig_freq=None):
+    if isinstance(input_file, (str, os.PathLike)):
+        waveform, orig_freq = load_audio(input_file), None
+    else:
+        waveform = input_file
+    return detect_waveform(waveform, detector, detection_threshold, device, orig_freq=orig_freq)
 
 
 @torch.no_grad()
-def detect_prob(file_path, detector, sample_rate=SAMPLE_RATE, device="cuda", max_batch=512):
+def detect_prob(file_path, detector, sample_rate=SAMPLE_RATE, device="cuda", max_batch=512, orig_freq=None):
     """py/main16.py:1575-1596: average over the file's 1-s segments of each segment's mean detection probability.  The
     mean of a segment runs over all 16 000 samples of the zero-PADDED tail segment too (unlike detect_watermark, which
     trims it), so this is a mean of per-segment means, not the mean of the temporal track.  One batched Detector call;
-    accepts a path or an in-memory (1,N) waveform."""
-    waveform = load_audio(file_path, sample_rate) if isinstance(file_path, (str, os.PathLike)) else file_path
-    segs, _ = _segments(waveform.float(), sample_rate)
+    accepts a path or an in-memory (1,N) waveform, or a (C,N) one at `orig_freq` (see _ingest)."""
+    if isinstance(file_path, (str, os.PathLike)):
+        waveform, orig_freq = load_audio(file_path, sample_rate), None
+    else:
+        waveform = file_path
+    segs, _, _ = _ingest(waveform, orig_freq, device, sample_rate)
     if segs.shape[0] == 0:
         return float("nan")                                             # np.mean([]) in the reference
     seg_means = []
@@ -253,20 +347,22 @@ def _si_snr_rows(s, s_hat, eps=1e-8):
 
 
 @torch.no_grad()
-def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_bits=16, messages=None, max_batch=256):
+def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_bits=16, messages=None, max_batch=256,
+                         orig_freq=None):
     """py/main16.py:1263-1299 with all 1-s segments of the file as one batch: returns (mean clean detection probability,
     mean watermarked detection probability, mean SI-SNR, mean delta RMS) over the segments, or four Nones when the file
     cannot be read (:1264-1267).  A fresh random message per segment (:1287) unless `messages` is given.  Accepts a path
-    or an in-memory (1,N) waveform.  Per-segment reductions run on the device; four scalars come back."""
+    or an in-memory (1,N) waveform, or a (C,N) one at `orig_freq` (see _ingest).  Per-segment reductions run on the device;
+    four scalars come back."""
     if isinstance(filepath, (str, os.PathLike)):
         try:
-            waveform = load_audio(filepath)
+            waveform, orig_freq = load_audio(filepath), None
         except Exception:
             return None, None, None, None
     else:
         waveform = filepath
     generator.eval(); detector.eval()
-    segs, _ = _segments(waveform.float())
+    segs, _, _ = _ingest(waveform, orig_freq, device)
     S = segs.shape[0]
     if S == 0:
         return (float("nan"),) * 4

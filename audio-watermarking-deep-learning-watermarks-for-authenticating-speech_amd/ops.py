@@ -1021,3 +1021,113 @@ class L1Fn(torch.autograd.Function):
         dx = torch.empty_like(x)
         lib.wm_l1_bwd(_p(x), _p(g.contiguous().float().reshape(1)), _p(dx), x.numel(), _stream())
         return dx
+
+
+# ---------------------------------------------------------------------------------------------- sample-rate conversion
+# torchaudio.functional.resample with its documented defaults (resampling_method="sinc_interp_hann", lowpass_filter_width=6,
+# rolloff=0.99), restated from the published description.  The reference resamples every file that is not at 16 kHz before a
+# model sees it (py/main16.py:717-720).  The table is formed in float64 and rounded once to float32; the clamp of the filter
+# argument makes every tap beyond +-6 zero crossings exactly 0.0, so only each phase's run of non-zero taps goes to the device.
+RESAMPLE_LOWPASS_WIDTH = 6
+RESAMPLE_ROLLOFF = 0.99
+_RESAMPLE_HOST = {}      # (orig, new) -> table dict (CPU tensors)
+_RESAMPLE_DEV = {}       # (orig, new, device) -> (taps, first) on the device
+
+
+def _rate(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != int(v) or int(v) <= 0:
+        raise ValueError(f"{name} must be a positive integer number of Hz, got {v!r}")
+    return int(v)
+
+
+def resample_length(n, orig_freq, new_freq):
+    """ceil(new * n / orig): the number of samples torchaudio keeps for an input of n"""
+    import math
+    g = math.gcd(int(orig_freq), int(new_freq))
+    P, Q = int(orig_freq) // g, int(new_freq) // g
+    return -((-Q * int(n)) // P)
+
+
+def resample_table(orig_freq, new_freq):
+    """Host tables of one rate pair (cached): P, Q, width, K = 2*width + P, the dense float32 table `dense` (Q, K), and the compact
+    one the kernel reads: `taps` (Q, W) with `first` (Q,) int32 such that dense[i, first[i]:first[i]+W] == taps[i] and every other
+    entry of dense is 0.0.  W is the longest run of non-zero taps over the phases, made odd where K allows (LDS banks)."""
+    import math
+    orig_freq, new_freq = _rate(orig_freq, "orig_freq"), _rate(new_freq, "new_freq")
+    key = (orig_freq, new_freq)
+    if key in _RESAMPLE_HOST:
+        return _RESAMPLE_HOST[key]
+    g = math.gcd(orig_freq, new_freq)
+    P, Q = orig_freq // g, new_freq // g
+    if P == Q:       # equal rates: the identity as a one-tap table (only the segment padding of the kernel is used)
+        tab = {"P": 1, "Q": 1, "width": 0, "K": 1, "W": 1, "dense": torch.ones(1, 1), "taps": torch.ones(1, 1),
+               "first": torch.zeros(1, dtype=torch.int32)}
+        _RESAMPLE_HOST[key] = tab
+        return tab
+    lpw = RESAMPLE_LOWPASS_WIDTH
+    base = min(P, Q) * RESAMPLE_ROLLOFF
+    width = int(math.ceil(lpw * P / base))
+    K = 2 * width + P
+    j = torch.arange(-width, width + P, dtype=torch.float64)[None, :] / P
+    i = torch.arange(0, -Q, -1, dtype=torch.float64)[:, None] / Q
+    t = ((i + j) * base).clamp_(-lpw, lpw)
+    window = torch.cos(t * math.pi / lpw / 2) ** 2
+    t = t * math.pi
+    sinc = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t)
+    dense = (sinc * (window * (base / P))).to(torch.float32)                   # (Q, K), the one rounding
+    nz = dense != 0
+    assert bool(nz.any(dim=1).all())
+    idx = torch.arange(K)
+    lo = torch.where(nz, idx, K).min(dim=1).values
+    hi = torch.where(nz, idx, -1).max(dim=1).values
+    W = int((hi - lo + 1).max())
+    if W % 2 == 0 and W < K:
+        W += 1
+    first = torch.minimum(lo, torch.tensor(K - W)).to(torch.int32)
+    taps = torch.stack([dense[q, int(first[q]):int(first[q]) + W] for q in range(Q)]).contiguous()
+    tab = {"P": P, "Q": Q, "width": width, "K": K, "W": W, "dense": dense, "taps": taps, "first": first}
+    _RESAMPLE_HOST[key] = tab
+    return tab
+
+
+def resample_tile_periods(orig_freq, new_freq):
+    """output periods (Q samples each) one workgroup of the LDS kernel handles at a time; 0: the table does not fit LDS and the
+    one-thread-per-sample kernel runs"""
+    import ctypes
+    tab = resample_table(orig_freq, new_freq)
+    out = (ctypes.c_longlong * 1)()
+    lib.wm_resample_plan(tab["P"], tab["Q"], tab["width"], tab["W"], ctypes.addressof(out), None)
+    return int(out[0])
+
+
+def resample(x, orig_freq, new_freq, seg_len=0, out=None):
+    """Channel mean + sinc resampling of a CUDA waveform (C, N) or (N,) in one launch.  seg_len = 0: (1, L) with
+    L = ceil(new * N / orig).  seg_len > 0: (S, 1, seg_len), S = ceil(L / seg_len), the tail of the last segment zero -- the
+    Generator / Detector batch of the recording.  Equal rates with seg_len = 0 return x unchanged.  `out` (optional): a
+    contiguous fp32 CUDA buffer of exactly the result's size to write into."""
+    tab = resample_table(orig_freq, new_freq)
+    seg_len = int(seg_len)
+    if seg_len < 0:
+        raise ValueError(f"seg_len must be >= 0, got {seg_len}")
+    if isinstance(x, torch.Tensor) and x.dim() == 1:
+        x = x.unsqueeze(0)
+    x = _chk(x, "waveform", 2)
+    if tab["K"] == 1 and seg_len == 0 and out is None:
+        return x
+    C, N = x.shape
+    if C < 1:
+        raise ValueError("waveform: needs at least one channel")
+    L = -((-tab["Q"] * N) // tab["P"])
+    S = -(-L // seg_len) if seg_len else 1
+    total = S * seg_len if seg_len else L
+    dkey = (int(orig_freq), int(new_freq), x.device)
+    if dkey not in _RESAMPLE_DEV:
+        _RESAMPLE_DEV[dkey] = (tab["taps"].to(x.device), tab["first"].to(x.device))
+    taps, first = _RESAMPLE_DEV[dkey]
+    if out is None:
+        out = _f32(total, device=x.device)
+    else:
+        if not out.is_contiguous() or _chk(out, "out").numel() != total or out.device != x.device:
+            raise ValueError(f"out: expected {total} floats on {x.device}, got {out.numel()} on {out.device}")
+    lib.wm_resample(_p(x), _p(taps), _p(first), _p(out), C, N, tab["P"], tab["Q"], tab["width"], tab["W"], L, total, _stream())
+    return out.view(S, 1, seg_len) if seg_len else out.view(1, L)

@@ -315,6 +315,21 @@ int wm_lstm_seq_fwd(float* xp, const float* whh, float* hs, float* cs, int T, in
 int wm_lstm_seq_bwd(float* gates, const float* cs, const float* dout, const float* whhT, float* dc, int T, int H, int B,
                     wm_stream_t stream);
 
+/* ---- file ingest: mono mixdown + sample-rate conversion + 1-s segment padding in one launch ----------------------
+ * replaces, for a recording that is not at 16 kHz, `waveform.mean(dim=0, keepdim=True)`, torchaudio.transforms.Resample(sr, 16000)
+ * and the zero-padded tail segment of the reference's file-level entry points (py/main16.py:714-760).
+ *   x (C, N) channel-major, any C >= 1;  P = orig / gcd, Q = new / gcd;  y[m*Q + i] = sum_{k<W} taps[i][k] * xmono[m*P + first[i] + k - width]
+ *   with xmono the channel mean (channels added in float64, rounded once to fp32; 0 outside [0, N)), for the L = ceil(Q*N/P) samples of the result; y[L .. total) = 0, so that with
+ *   total = ceil(L / seg_len) * seg_len the output is the [S,1,seg_len] model batch (total = L: no padding).
+ *   taps [Q][W] fp32 / first [Q] int32: the compact table of torchaudio's default design (sinc_interp_hann, lowpass_filter_width 6,
+ *   rolloff 0.99; width = ceil(6 P / (0.99 min(P, Q)))), each phase's run of non-zero taps, W <= 2*width + P, first[i] + W <= 2*width + P.
+ * The additions of one sample run k = 0..W-1 whatever kernel or tile computes it.  Rate pairs whose table does not fit LDS run from a
+ * one-thread-per-sample kernel that reads it through the cache.  wm_resample_plan (host-only, tile_periods is a HOST pointer, stream
+ * unused) reports the output periods of one LDS tile, 0 when that kernel runs. */
+int wm_resample_plan(int P, int Q, int width, int W, long long* tile_periods, wm_stream_t stream);
+int wm_resample(const float* x, const float* taps, const int* first, float* y, int C, long long N, int P, int Q, int width, int W,
+                long long L, long long total, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
