@@ -65,6 +65,41 @@ class Resample(torch.nn.Module):
         return resample(waveform, self.orig_freq, self.new_freq)
 
 
+def resample_add(x, delta, orig_freq, delta_freq=SAMPLE_RATE):
+    """The way back of `resample`: `delta` (at delta_freq, read flat) taken to the rate `orig_freq` of the recording `x` ((C, N) or (N,))
+    and added to every channel of it.  Of delta the first n_d = ceil(delta_freq * N / orig_freq) samples count (fewer: ValueError); what
+    lies behind them is ignored.  Returns (out (C, N), up (1, N)): up is resample(delta[:n_d], delta_freq, orig_freq)[:, :N] and
+    out[c] = x[c] + up[0].  CUDA tensors go to the HIP kernel (ops.resample_add, one launch); CPU tensors through the CPU twin of
+    `resample` and one add."""
+    from . import ops
+    ops.resample_table(delta_freq, orig_freq)                        # bad rates fail here
+    x = _as_channels(x)
+    if not isinstance(delta, torch.Tensor):
+        raise TypeError(f"delta: expected a tensor, got {type(delta).__name__}")
+    n = x.shape[1]
+    n_d = ops.resample_length(n, orig_freq, delta_freq)
+    if delta.numel() < n_d:
+        raise ValueError(f"delta: {n} samples at {orig_freq} Hz need {n_d} at {delta_freq} Hz, got {delta.numel()}")
+    if x.is_cuda:
+        return ops.resample_add(x.contiguous(), delta.to(torch.float32).contiguous(), orig_freq, delta_freq)
+    d = delta.to(torch.float32).reshape(1, -1)[:, :n_d]
+    up = resample(d, delta_freq, orig_freq)[:, :n]
+    up = up.clone() if up.data_ptr() == delta.data_ptr() else up.contiguous()     # equal rates hand delta itself back: never a view of it
+    return x + up, up
+
+
+def read_audio(file_path):
+    """((C, N) float32 waveform, sample rate): the file's own channels at the file's own rate -- what `native_rate=True` embeds into.
+    torchaudio.load where it is installed, else the .wav reader of load_audio."""
+    try:
+        import torchaudio
+    except ImportError:
+        data, rate = _read_wav(file_path)
+        return torch.from_numpy(np.ascontiguousarray(data.T)), int(rate)
+    waveform, sr = torchaudio.load(file_path)
+    return waveform.to(torch.float32), int(sr)
+
+
 def load_audio(file_path, sample_rate=SAMPLE_RATE, device=None):
     """(1, N) fp32 mono waveform at `sample_rate`.  Uses torchaudio when it is installed (the reference's loader, :714-720).
     Otherwise .wav files (16- / 24-bit PCM, 32-bit float, plain or WAVE_FORMAT_EXTENSIBLE header) are read with the standard
@@ -235,11 +270,17 @@ def compute_si_snr(s, s_hat, eps=1e-8):
 
 
 @torch.no_grad()
-def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages=None, max_batch=512, orig_freq=None):
+def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages=None, max_batch=512, orig_freq=None, native_rate=False):
     """process_audio_file_with_delta (:723-762) on an in-memory waveform, batched.
     Returns (watermarked_waveform, delta_waveform, original_waveform), each (1, N) on the CPU.  `orig_freq`: the rate of a
-    (C, N) waveform that is not at 16 kHz yet (see _ingest); the three returned waveforms are at 16 kHz, as the reference's."""
+    (C, N) waveform that is not at 16 kHz yet (see _ingest); the three returned waveforms are at 16 kHz, as the reference's.
+    `native_rate=True` (no counterpart in the reference): the recording keeps its channels and its rate.  The (C, N) waveform at
+    `orig_freq` (None: 16 kHz) is uploaded once, its mixdown at 16 kHz feeds the generator as above, the batches write delta into one
+    (S, 1, 16000) device buffer and ONE wm_resample_add launch takes that delta up to `orig_freq` and adds it to every channel of the
+    untouched recording.  Returns (watermarked (C, N), delta (1, N), original (C, N)) on the CPU at `orig_freq`."""
     generator.eval()
+    if native_rate:
+        return _embed_native(waveform, generator, message_bits, device, messages, max_batch, orig_freq)
     segs, remainder, waveform = _ingest(waveform, orig_freq, device)
     S = segs.shape[0]
     if S == 0:
@@ -259,21 +300,58 @@ def embed_waveform(waveform, generator, message_bits=16, device="cuda", messages
     return wm_w, delta_w, waveform.cpu()
 
 
-def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None):
+def _embed_native(waveform, generator, message_bits, device, messages, max_batch, orig_freq, seg_len=SAMPLE_RATE):
+    """embed_waveform(native_rate=True): everything between the upload of the recording and the download of the result stays on the device.
+    The segments come from the launch _ingest uses for a recording that is not at 16 kHz, called here directly: _ingest cuts a 16 kHz
+    waveform on the host without a mixdown (the old call, which must not change) and does not hand back the uploaded (C, N) channels that
+    wm_resample_add adds delta to."""
+    from . import ops
+    rate = seg_len if orig_freq is None else ops._rate(orig_freq, "orig_freq")
+    original = _as_channels(waveform)
+    x = original.to(device).contiguous()
+    segs = ops.resample(x, rate, seg_len, seg_len=seg_len)           # (S, 1, seg_len): mixdown (+ resampling) + tail padding, one launch
+    S = segs.shape[0]
+    if S == 0:
+        original = original.cpu()
+        return original.clone(), original.new_zeros(1, 0), original
+    if messages is None:       # a fresh random message per second, as :1001
+        messages = torch.randint(0, 2 ** message_bits, (S,), device=device)
+    delta = torch.empty_like(segs)
+    for i in range(0, S, max_batch):
+        delta[i:i + max_batch] = generator(segs[i:i + max_batch], messages[i:i + max_batch].to(device))
+    wm, up = ops.resample_add(x, delta, rate, seg_len)               # Nd = n16: the generator's output for the zero tail is not read
+    return wm.cpu(), up.cpu(), original.cpu()
+
+
+def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None, native_rate=False):
     """py/main16.py:977-1066 with one batched Generator call; same result dict.  A path is loaded (and resampled) by
-    load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz."""
-    if isinstance(input_file, (str, os.PathLike)):
-        waveform, orig_freq = load_audio(input_file), None
+    load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz.
+    `native_rate=True`: a path is read by read_audio (its channels, its rate), an in-memory (C, N) waveform is at `orig_freq`; the three
+    waveforms come back at that rate with all channels (embed_waveform), `output_file` is written at that rate with all channels, the
+    metrics are taken at that rate (SI-SNR over the channel rows) and the dict gains "sample_rate"."""
+    if native_rate:
+        if isinstance(input_file, (str, os.PathLike)):
+            waveform, rate = read_audio(input_file)
+        else:
+            waveform, rate = input_file, (SAMPLE_RATE if orig_freq is None else int(orig_freq))
+        wm, delta, orig = embed_waveform(waveform, generator, message_bits=message_bits, device=device, orig_freq=rate, native_rate=True)
     else:
-        waveform = input_file
-    wm, delta, orig = embed_waveform(waveform, generator, message_bits=message_bits, device=device, orig_freq=orig_freq)
+        if isinstance(input_file, (str, os.PathLike)):
+            waveform, orig_freq = load_audio(input_file), None
+        else:
+            waveform = input_file
+        wm, delta, orig = embed_waveform(waveform, generator, message_bits=message_bits, device=device, orig_freq=orig_freq)
+        rate = SAMPLE_RATE
     watermark_rms = torch.sqrt((delta ** 2).mean()).item()
     si_snr = compute_si_snr(orig, wm)
     power_ratio_db = 10 * np.log10(torch.mean(orig ** 2).item() / max(torch.mean(delta ** 2).item(), 1e-30))
     if output_file:
-        save_audio_float(wm, output_file)                 # :1051-1055 stores the float waveform as is
-    return {"watermarked_waveform": wm, "delta_waveform": delta, "original_waveform": orig,
-            "metrics": {"watermark_rms": watermark_rms, "si_snr_db": si_snr, "power_ratio_db": power_ratio_db}}
+        save_audio_float(wm, output_file, rate)           # :1051-1055 stores the float waveform as is
+    result = {"watermarked_waveform": wm, "delta_waveform": delta, "original_waveform": orig,
+              "metrics": {"watermark_rms": watermark_rms, "si_snr_db": si_snr, "power_ratio_db": power_ratio_db}}
+    if native_rate:
+        result["sample_rate"] = rate
+    return result
 
 
 @torch.no_grad()

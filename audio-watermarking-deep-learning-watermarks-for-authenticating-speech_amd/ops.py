@@ -1131,3 +1131,43 @@ def resample(x, orig_freq, new_freq, seg_len=0, out=None):
             raise ValueError(f"out: expected {total} floats on {x.device}, got {out.numel()} on {out.device}")
     lib.wm_resample(_p(x), _p(taps), _p(first), _p(out), C, N, tab["P"], tab["Q"], tab["width"], tab["W"], L, total, _stream())
     return out.view(S, 1, seg_len) if seg_len else out.view(1, L)
+
+
+def resample_add(x, delta, orig_freq, delta_freq=16000, out=None, want_up=True):
+    """The way back of the embed path in one launch: `delta` (at delta_freq) resampled to the recording's rate `orig_freq` and added to
+    every channel of the recording `x` ((C, N) or (N,), fp32, CUDA).  `delta`: any contiguous fp32 CUDA tensor, read flat; its first
+    n_d = resample_length(N, orig_freq, delta_freq) samples count, the rest is never read.  Returns (out (C, N), up (1, N) or None):
+    up is ops.resample(delta[:n_d], delta_freq, orig_freq)[:, :N] bit for bit, out[c] = x[c] + up[0].  `out` (optional): a contiguous
+    (C, N) fp32 buffer to write into; it may be x itself.  want_up=False: up is neither formed in memory nor returned."""
+    tab = resample_table(delta_freq, orig_freq)
+    inplace = out is x
+    if isinstance(x, torch.Tensor) and x.dim() == 1:
+        x = x.unsqueeze(0)                      # a view: an in-place sum still lands in the caller's (N,) tensor
+    if isinstance(x, torch.Tensor) and x.dim() != 2:
+        raise ValueError(f"waveform: expected (channels, samples) or (samples,), got shape {tuple(x.shape)}")
+    if inplace and not x.is_contiguous():
+        raise ValueError("out: an in-place sum needs a contiguous waveform")
+    x = _chk(x, "waveform", 2)
+    delta = _chk(delta, "delta")
+    C, N = x.shape
+    if C < 1:
+        raise ValueError("waveform: needs at least one channel")
+    n_d = resample_length(N, orig_freq, delta_freq)
+    if delta.numel() < n_d:
+        raise ValueError(f"delta: {N} samples at {orig_freq} Hz need {n_d} at {delta_freq} Hz, got {delta.numel()}")
+    if delta.device != x.device:
+        raise ValueError(f"delta: on {delta.device}, the waveform is on {x.device}")
+    if out is None:
+        out = _f32(C, N, device=x.device)
+    elif inplace:
+        out = x                                 # the (C, N) view of the caller's tensor
+    elif (not out.is_contiguous() or tuple(_chk(out, "out").shape) != (C, N) or out.device != x.device):
+        raise ValueError(f"out: expected a contiguous ({C}, {N}) buffer on {x.device}, got {tuple(out.shape)} on {out.device}")
+    up = _f32(1, N, device=x.device) if want_up else None
+    dkey = (int(delta_freq), int(orig_freq), x.device)
+    if dkey not in _RESAMPLE_DEV:
+        _RESAMPLE_DEV[dkey] = (tab["taps"].to(x.device), tab["first"].to(x.device))
+    taps, first = _RESAMPLE_DEV[dkey]
+    lib.wm_resample_add(_p(delta), _p(taps), _p(first), _p(x), _p(out), _p(up), C, N, n_d, tab["P"], tab["Q"], tab["width"], tab["W"],
+                        _stream())
+    return out, up

@@ -330,6 +330,23 @@ int wm_resample_plan(int P, int Q, int width, int W, long long* tile_periods, wm
 int wm_resample(const float* x, const float* taps, const int* first, float* y, int C, long long N, int P, int Q, int width, int W,
                 long long L, long long total, wm_stream_t stream);
 
+/* The way back of the embed path: delta at the model rate -> the recording's own rate, added to every channel of the untouched recording,
+ * one launch (the reference has no counterpart: it returns and saves the watermarked signal at 16 kHz mono).
+ *   P = delta rate / gcd, Q = recording rate / gcd; taps [Q][W] / first [Q]: the compact table of the pair (delta rate, recording rate), as
+ *   for wm_resample;
+ *     up[o]     = sum_{k<W} taps[i][k] * d[m*P + first[i] + k - width]      o = m*Q + i,  0 <= o < N
+ *     out[c][o] = x[c][o] + up[o]                                           0 <= c < C
+ *   d: flat fp32 of which the first Nd samples count; everything outside [0, Nd) is zero BY PREDICATE -- the buffer behind Nd is never read
+ *   and may hold anything, NaN included.  N need not be ceil(Q*Nd/P): samples whose window lies past Nd get up = 0.
+ *   x, out (C, N) channel-major, C <= 65536.  ALIASING: out may be x itself (in place); no other overlap between d, x, out and up is allowed.
+ *   up (N,) may be NULL: not wanted, not written.
+ * up[o] is the single chain fmaf(taps[i][k], d, acc), k = 0..W-1, that wm_resample runs -- it equals wm_resample of d[0 .. Nd) with C = 1 bit
+ * for bit, whatever tile, workgroup or kernel computed it -- followed by one fp32 add per channel.  Tiles and the choice between the LDS
+ * kernel and the one-thread-per-sample kernel are those of wm_resample_plan(P, Q, width, W).  Rows leave as 16-byte accesses when
+ * N % 4 == 0 and x, out and up are 16-byte aligned, as 4-byte accesses otherwise (coalesced either way).  N == 0 returns 0 without a launch. */
+int wm_resample_add(const float* d, const float* taps, const int* first, const float* x, float* out, float* up, int C, long long N,
+                    long long Nd, int P, int Q, int width, int W, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
