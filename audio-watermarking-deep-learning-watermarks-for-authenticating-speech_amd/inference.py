@@ -207,20 +207,26 @@ def pcm16(waveform):
     return (waveform.detach().cpu().clamp(-1.0, 1.0) * 32767).to(torch.int16)
 
 
-def save_audio(waveform, output_path, sample_rate=SAMPLE_RATE, lowpass_hz=7000):
+def save_audio(waveform, output_path, sample_rate=SAMPLE_RATE, lowpass_hz=7000, device=None):
     """py/main15.py:850-867 `save_audio(waveform, output_path, sample_rate)`: 7 kHz biquad low-pass -> clamp -> x32767 ->
     truncating int16 cast -> 16-bit signed PCM WAV.  The container is written with the standard library (`torchaudio.save(...,
     encoding="PCM_S", bits_per_sample=16)` in the reference; a mono or (C, N) waveform, samples interleaved by channel).
-    `lowpass_hz=None` skips the filter (the PCM bytes are then exactly pcm16(waveform))."""
+    `lowpass_hz=None` skips the filter (the PCM bytes are then exactly pcm16(waveform)).
+    `device` (e.g. "cuda"): filter and quantiser run there as one launch (codec.encode_pcm16; the waveform is uploaded if it is not
+    there yet) and int16 codes come back, half the bytes of the float waveform.  None: the host path, also for a CUDA waveform."""
     out_dir = os.path.dirname(output_path)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
-    x = waveform.detach().cpu()
-    if x.dim() == 1:
-        x = x.unsqueeze(0)
-    if lowpass_hz is not None:
-        x = lowpass_biquad(x, sample_rate, cutoff_freq=lowpass_hz)
-    pcm = pcm16(x).numpy()                                   # (C, N)
+    if device is not None and torch.device(device).type != "cpu":
+        from .codec import encode_pcm16
+        pcm = encode_pcm16(waveform.detach().to(device), sample_rate, lowpass_hz).cpu().numpy()
+    else:
+        x = waveform.detach().cpu()
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if lowpass_hz is not None:
+            x = lowpass_biquad(x, sample_rate, cutoff_freq=lowpass_hz)
+        pcm = pcm16(x).numpy()                               # (C, N)
     with wave.open(output_path, "wb") as w:
         w.setnchannels(pcm.shape[0]); w.setsampwidth(2); w.setframerate(sample_rate)
         w.writeframes(np.ascontiguousarray(pcm.T).astype("<i2").tobytes())
@@ -461,10 +467,11 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
 
 
 @torch.no_grad()
-def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None):
+def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None, codec=None):
     """evaluate_model (:369-423): the per-batch reductions run on the device (step.eval_forward); the per-clip values of
     all batches are pooled and averaged once, as the reference's np.mean over its extended lists does (so a ragged last
-    batch weighs by its clips).  `messages` (optional list, one tensor per batch) replaces the randint draw of :381."""
+    batch weighs by its clips).  `messages` (optional list, one tensor per batch) replaces the randint draw of :381.
+    `codec` (a codec.PcmCodec): the Detector is evaluated on codec(s + delta), as in main15c's validate_one_epoch."""
     from .step import eval_forward
     generator.eval(); detector.eval()
     keys = {"watermarked_prob": "prob_watermarked", "clean_prob": "prob_clean", "bit_accuracy": "bit_accuracy",
@@ -474,7 +481,7 @@ def evaluate_batches(generator, detector, batches, device="cuda", message_bits=1
         s = s.to(device)
         message = (messages[bi].to(device) if messages is not None else
                    torch.randint(0, 2 ** message_bits, (s.shape[0],), device=device))
-        out = eval_forward(generator, detector, s, message)
+        out = eval_forward(generator, detector, s, message, codec=codec)
         for k, src in keys.items():
             acc[k].append(out[src])
     return {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in acc.items()}

@@ -1171,3 +1171,153 @@ def resample_add(x, delta, orig_freq, delta_freq=16000, out=None, want_up=True):
     lib.wm_resample_add(_p(delta), _p(taps), _p(first), _p(x), _p(out), _p(up), C, N, n_d, tab["P"], tab["Q"], tab["width"], tab["W"],
                         _stream())
     return out, up
+
+
+# ---------------------------------------------------------------------------------------------- biquad + 16-bit PCM codec
+# The reference's 16-bit save path (py/main15.py:850-867: 7 kHz biquad low-pass -> clamp -> x32767 -> int16) and main15c's
+# perceptual_postprocess (round(lowpass_biquad(x, 16000, 7000) * 32767) / 32767 on s_w inside the train / validation step) as one
+# launch of wm_biquad.  The section is the RBJ cookbook low-pass torchaudio.functional.lowpass_biquad is published as.
+BIQUAD_MODES = {"float": 0, "round": 1, "pcm16": 2}
+BIQUAD_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0)       # the quantiser alone
+_BIQUAD_COEFFS = {}
+_BIQUAD_PLAN = {}
+
+
+def biquad_lowpass_coeffs(sample_rate, cutoff_freq, Q=0.707):
+    """(b0, b1, b2, a1, a2) of the low-pass section exactly as inference.lowpass_biquad forms it: float64, divided by a0, each value
+    rounded once to float32 (returned as Python floats that hold those float32 values).  Host-only, cached."""
+    import math
+    key = (sample_rate, cutoff_freq, Q)
+    try:
+        return _BIQUAD_COEFFS[key]
+    except (KeyError, TypeError):
+        pass
+    for v, name in ((sample_rate, "sample_rate"), (cutoff_freq, "cutoff_freq"), (Q, "Q")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+    if 2.0 * float(cutoff_freq) >= float(sample_rate):
+        raise ValueError(f"cutoff_freq must lie below half the sample rate, got {cutoff_freq} Hz at {sample_rate} Hz")
+    import numpy as np
+    w0 = 2.0 * math.pi * float(cutoff_freq) / float(sample_rate)
+    alpha = math.sin(w0) / (2.0 * float(Q))
+    cw = math.cos(w0)
+    b = np.array([(1.0 - cw) / 2.0, 1.0 - cw, (1.0 - cw) / 2.0], dtype=np.float64)
+    a = np.array([1.0 + alpha, -2.0 * cw, 1.0 - alpha], dtype=np.float64)
+    b32, a32 = (b / a[0]).astype(np.float32), (a / a[0]).astype(np.float32)
+    out = (float(b32[0]), float(b32[1]), float(b32[2]), float(a32[1]), float(a32[2]))
+    _BIQUAD_COEFFS[key] = out
+    return out
+
+
+def _biquad_coeffs(coeffs):
+    import math
+    import numpy as np
+    try:
+        c = tuple(float(v) for v in coeffs)
+    except TypeError:
+        raise ValueError(f"coeffs: expected (b0, b1, b2, a1, a2), got {coeffs!r}") from None
+    if len(c) != 5 or not all(math.isfinite(v) and float(np.float32(v)) == v for v in c):
+        raise ValueError(f"coeffs: expected five finite float32 values (b0, b1, b2, a1, a2), got {coeffs!r}")
+    return c
+
+
+def biquad_warm(coeffs):
+    """the smallest W with r^W <= 2^-40, r the pole radius of 1 / (1 + a1 z^-1 + a2 z^-2): the warm-up after which a recursion started
+    from a zero state has forgotten that (0 for a section without poles).  An unstable section (r >= 1) raises ValueError."""
+    import math
+    _, _, _, a1, a2 = _biquad_coeffs(coeffs)
+    disc = a1 * a1 - 4.0 * a2
+    r = math.sqrt(a2) if disc < 0 else (abs(a1) + math.sqrt(disc)) / 2.0
+    if r >= 1.0:
+        raise ValueError(f"coeffs: the section is not stable (pole radius {r})")
+    if r == 0.0:
+        return 0
+    W = max(0, int(math.ceil(-40.0 * math.log(2.0) / math.log(r))) - 1)
+    while r ** W > 2.0 ** -40:
+        W += 1
+    return W
+
+
+def biquad_plan(coeffs):
+    """(warm, chunk) wm_biquad runs this section with: the time-parallel kernel with chunks of `chunk` samples and biquad_warm(coeffs)
+    samples of warm-up, or (-1, 0), one lane per row, where the library finds that warm-up too long.  A function of the coefficients alone."""
+    import ctypes
+    c = _biquad_coeffs(coeffs)
+    if c not in _BIQUAD_PLAN:
+        W = biquad_warm(c)
+        out = (ctypes.c_int * 1)()
+        lib.wm_biquad_plan(W, ctypes.addressof(out), None)
+        _BIQUAD_PLAN[c] = (W, int(out[0])) if out[0] else (-1, 0)
+    return _BIQUAD_PLAN[c]
+
+
+def biquad(x, coeffs, *, clamp=True, mode="float", reverse=False, mask_out=False, mask_in=None, out=None):
+    """Second-order section along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows, each from a zero state),
+    one launch (wm_biquad).  mode "float": clamp(y, -1, 1) (clamp=False: y) | "round": round(clamp(y) * 32767) / 32767 | "pcm16": int16
+    codes (clamp(y) * 32767).to(int16).  reverse: flip(filter(flip(x))), the adjoint.  mask_out: also returns the int32 bit mask of
+    |y| <= 1 ((rows, ceil(n / 32)), bit t % 32 of word t / 32) as (out, mask).  mask_in: such a mask, applied to x on load.  `out`: a
+    contiguous buffer of x's shape (int16 for "pcm16") that does not overlap x."""
+    if mode not in BIQUAD_MODES:
+        raise ValueError(f"mode must be one of {sorted(BIQUAD_MODES)}, got {mode!r}")
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+        raise ValueError(f"x: ops.biquad runs on the GPU only (got a {x.device} tensor); perceptual_postprocess / encode_pcm16 take CPU tensors")
+    c = _biquad_coeffs(coeffs)
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    if mode == "pcm16" and not clamp:
+        raise ValueError('mode "pcm16" needs clamp=True (the int16 cast is defined on [-1, 1] only)')
+    if mask_out and reverse:
+        raise ValueError("mask_out is not available with reverse=True")
+    warm, _ = biquad_plan(c)
+    odt = torch.int16 if mode == "pcm16" else torch.float32
+    if out is None:
+        out = torch.empty(x.shape, dtype=odt, device=x.device)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != x.device or out.dtype != odt or \
+                not out.is_contiguous() or out.shape != x.shape:
+            raise ValueError(f"out: expected a contiguous {odt} buffer of shape {tuple(x.shape)} on {x.device}")
+        xa, oa = x.data_ptr(), out.data_ptr()
+        if xa < oa + out.numel() * out.element_size() and oa < xa + x.numel() * 4:
+            raise ValueError("out: overlaps x (the filter reads x behind the samples it writes; in place is not supported)")
+    nw = (n + 31) // 32
+    if mask_in is not None:
+        mask_in = _chk(mask_in, "mask_in", None, torch.int32)
+        if mask_in.numel() != rows * nw or mask_in.device != x.device:
+            raise ValueError(f"mask_in: expected {rows} x {nw} int32 words on {x.device}, got {mask_in.numel()} on {mask_in.device}")
+    mask = torch.empty(rows, nw, dtype=torch.int32, device=x.device) if mask_out else None
+    lib.wm_biquad(_p(x), _p(out), _p(mask), _p(mask_in), *c, rows, n, warm, BIQUAD_MODES[mode], int(bool(clamp)), int(bool(reverse)),
+                  _stream())
+    return (out, mask) if mask_out else out
+
+
+class PcmCodecFn(torch.autograd.Function):
+    """main15c's perceptual_postprocess, round(clamp(biquad(x)) * 32767) / 32767, on the tape.  grad "reference": the output is
+    non-differentiable, as in torch (torch.round has a zero gradient, so nothing downstream of the codec reaches the Generator; marking
+    it also spares the Detector an input gradient that would be multiplied by zero).  grad "straight_through" (no counterpart in the
+    reference): the rounding passes the gradient unchanged, the clamp where its saved bit is set, the filter through its adjoint --
+    one reverse launch with mask_in."""
+
+    @staticmethod
+    def forward(ctx, x, coeffs, grad):
+        if grad not in ("reference", "straight_through"):
+            raise ValueError(f'grad must be "reference" or "straight_through", got {grad!r}')
+        ctx.coeffs = coeffs
+        if grad == "reference" or not ctx.needs_input_grad[0]:
+            out = biquad(x, coeffs, mode="round")
+            ctx.mark_non_differentiable(out)
+            ctx.st = False
+            return out
+        out, mask = biquad(x, coeffs, mode="round", mask_out=True)
+        ctx.save_for_backward(mask)
+        ctx.st = True
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.st:
+            return None, None, None
+        (mask,) = ctx.saved_tensors
+        return biquad(g.contiguous(), ctx.coeffs, clamp=False, reverse=True, mask_in=mask), None, None

@@ -15,12 +15,15 @@ _mel = L.MultiScaleMelLoss()
 _loud = L.TFLoudnessLoss()
 
 
-def forward_losses(generator, detector, s, message):
-    """delta -> post-processing -> detector on cat([s_w, s]) -> the six loss terms and both totals."""
+def forward_losses(generator, detector, s, message, codec=None):
+    """delta -> post-processing -> detector on cat([s_w, s]) -> the six loss terms and both totals.
+    `codec` (a codec.PcmCodec): the main15c graph -- s_w = codec(s + delta) is what the Detector, mel and loudness see."""
     B = s.shape[0]
     delta_raw = generator(s, message)                                  # :244
     delta = L.postprocess(delta_raw)                                   # :245-247
     s_w = s + delta                                                    # :248
+    if codec is not None:
+        s_w = codec(s_w)                                               # main15c: perceptual_postprocess(s + delta)
     logits = detector(torch.cat([s_w, s], dim=0), input_grad_rows=s.shape[0])                    # :249-250
     loc, bce = L.detection_losses(logits, message)                     # :252-264
     l1 = L.l1_to_zero(delta)                                           # :266
@@ -34,14 +37,16 @@ def forward_losses(generator, detector, s, message):
                               bce=bce, hf=hf, raw_total=raw, total=total)
 
 
-def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync):
-    """the step around a model family's forward_losses: zero_grad, forward, backward, gradient sync, message-id check, update"""
+def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec=None):
+    """the step around a model family's forward_losses: zero_grad, forward, backward, gradient sync, message-id check, update.
+    `codec` is handed to forward_losses only when given (a family without one keeps its signature)."""
+    extra = {} if codec is None else {"codec": codec}
     optimizer.zero_grad(set_to_none=not hasattr(optimizer, "flat"))
     if hasattr(grad_sync, "begin_step"):
         grad_sync.begin_step()
     try:
         with ops.index_check_mode():
-            total, out = forward_losses(generator, detector, s, message)   # no mid-step sync for the message-id range check ...
+            total, out = forward_losses(generator, detector, s, message, **extra)   # no mid-step sync for the message-id range check ...
         total.backward()
         if hasattr(optimizer, "finish_backward"):
             optimizer.finish_backward()
@@ -57,18 +62,21 @@ def _train_step(forward_losses, generator, detector, optimizer, s, message, grad
     return out
 
 
-def train_step(generator, detector, optimizer, s, message, grad_sync=None):
+def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec=None):
     """One iteration of train_one_epoch's loop body (:242-278): zero_grad, forward, backward, optimizer step.
-    `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce."""
-    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync)
+    `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce.
+    `codec` (a codec.PcmCodec): main15c's step, see forward_losses."""
+    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec)
 
 
 @torch.no_grad()
-def eval_forward(generator, detector, s, message):
+def eval_forward(generator, detector, s, message, codec=None):
     """evaluate_model's per-batch quantities (:383-403).  In eval mode BatchNorm uses running statistics, so the Detector's
     rows are independent: the clean half D(s) does not wait for the Generator -- it is queued for the side stream and released
     when the Generator reaches its latency-bound LSTM (B clips keep only B of the 256 CUs busy there), and the two halves are
-    concatenated afterwards (bit-identical to the single 2B-row call)."""
+    concatenated afterwards (bit-identical to the single 2B-row call).
+    `codec` (a codec.PcmCodec): the Detector sees codec(s + delta), as in main15c's validate_one_epoch, on both branches; the processed
+    signal is returned as "s_w"."""
     B = s.shape[0]
     overlap = (not generator.training) and (not detector.training) and s.is_cuda
     box = {}
@@ -77,15 +85,19 @@ def eval_forward(generator, detector, s, message):
             box["lg"] = detector(s)
         ops._on_side((s,), clean_half)                # queued: released on the side stream when the LSTM launch is reached
     delta = L.postprocess(generator(s, message))
+    s_w = s + delta if codec is None else codec(s + delta)
     if overlap:
-        lg_wm = detector(s + delta)
+        lg_wm = detector(s_w)
         ops.join_side_stream()                        # (also releases the queue if the Generator had no LSTM call)
         box["lg"].record_stream(torch.cuda.current_stream())
         logits = torch.cat([lg_wm, box["lg"]], dim=0)
     else:
-        logits = detector(torch.cat([s + delta, s], dim=0))
+        logits = detector(torch.cat([s_w, s], dim=0))
     probs = torch.sigmoid(logits[:, :, 0]).mean(dim=1)
     decoded = (torch.sigmoid(logits[:B, :, 1:]) > 0.5).float().mean(dim=1) > 0.5
     bits = ((message.unsqueeze(1) & (1 << torch.arange(logits.shape[-1] - 1, device=s.device))) > 0)
-    return OrderedDict(delta=delta, logits=logits, prob_watermarked=probs[:B], prob_clean=probs[B:],
-                       bit_accuracy=(decoded == bits).float().mean(dim=1), delta_rms=torch.sqrt((delta ** 2).mean(dim=[1, 2])))
+    out = OrderedDict(delta=delta, logits=logits, prob_watermarked=probs[:B], prob_clean=probs[B:],
+                      bit_accuracy=(decoded == bits).float().mean(dim=1), delta_rms=torch.sqrt((delta ** 2).mean(dim=[1, 2])))
+    if codec is not None:
+        out["s_w"] = s_w
+    return out

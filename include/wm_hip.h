@@ -347,6 +347,33 @@ int wm_resample(const float* x, const float* taps, const int* first, float* y, i
 int wm_resample_add(const float* d, const float* taps, const int* first, const float* x, float* out, float* up, int C, long long N,
                     long long Nd, int P, int Q, int width, int W, wm_stream_t stream);
 
+/* ---- 16-bit save path and main15c codec: biquad section + clamp + 16-bit quantiser in one launch -----------------------
+ * replaces the host-only `lowpass_biquad(waveform, sample_rate, cutoff_freq=7000)` -> clamp(-1, 1) -> * 32767 -> .to(torch.int16) of the
+ * reference's save_audio (py/main15.py:850-867), and `perceptual_postprocess(x) = round(lowpass_biquad(x, 16000, 7000) * 32767) / 32767`
+ * that main15c.ipynb applies to s_w = s + delta in train_one_epoch / validate_one_epoch (its cell "perceptual_postprocess").
+ *   x (rows, n) fp32, rows >= 1, n >= 1 (any values), every row filtered on its own from a zero state:
+ *     y[u] = b0 x[u] + b1 x[u-1] + b2 x[u-2] - a1 y[u-1] - a2 y[u-2]     as one product and four fmaf in this order of terms, -a1 y[u-1] last;
+ *     u = t, or with reverse != 0 u = n-1-t: flip(filter(flip(x))) by index mirroring, the adjoint of the forward filter.
+ *   warm >= 0 (<= 1024): rows are cut into chunks of 32 samples (in u); each chunk's recursion starts `warm` samples early from a zero state
+ *     (before the row: zeros, so chunks within `warm` of the row start are exact) and the warm-up results are dropped.  The host passes
+ *     the smallest warm with (pole radius)^warm <= 2^-40.  warm = -1: exact zero-state recursion, one lane per row.  A sample's bits depend
+ *     on x, the coefficients, warm and reverse only -- never on the grid; two launches give identical bits.  No atomics.
+ *   clamp != 0: c = clamp(y, -1, 1) (torchaudio's lfilter(clamp=True)), else c = y.
+ *   mode 0: out fp32 = c | 1: out fp32 = rintf(c * 32767.0f) / 32767.0f (half to even, IEEE division) | 2: out int16 = (int16)(c * 32767.0f),
+ *     truncated toward zero, 2 bytes per sample (needs clamp != 0).
+ *   mask_out (optional, not with reverse): bit t % 32 of word t / 32, ceil(n / 32) words per row (the layout of wm_bn_add_relu_mask), set
+ *     where |y| <= 1 before the clamp.  mask_in (optional, same layout): x is multiplied by its bit on load -- with reverse this is the
+ *     backward of "filter, then clamp" in one launch.
+ *   b0 = 1, b1 = b2 = a1 = a2 = 0: the quantiser alone (x is passed on as it is).
+ * x, the masks and an fp32 out may start at any multiple of 4 bytes (int16 out: of 2); rows leave as 16-byte (int16: 8-byte) accesses
+ * wherever a whole aligned group lies inside the row.  hipErrorInvalidValue before any launch: rows or n < 1, a null x or out, out (or a
+ * mask) overlapping x -- a chunk reads x behind itself, so in place is not supported --, warm outside -1..1024, mode 2 without clamp,
+ * mask_out with reverse.  wm_biquad_plan (host-only, chunk_len is a HOST pointer, stream unused): the chunk length for this warm, 0 when
+ * the one-lane-per-row kernel runs. */
+int wm_biquad_plan(int warm, int* chunk_len, wm_stream_t stream);
+int wm_biquad(const float* x, void* out, void* mask_out, const void* mask_in, float b0, float b1, float b2, float a1, float a2,
+              long long rows, long long n, int warm, int mode, int clamp, int reverse, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
