@@ -1321,3 +1321,43 @@ class PcmCodecFn(torch.autograd.Function):
             return None, None, None
         (mask,) = ctx.saved_tensors
         return biquad(g.contiguous(), ctx.coeffs, clamp=False, reverse=True, mask_in=mask), None, None
+
+
+# ---------------------------------------------------------------------------------------------- channel distortions
+class DistortFn(torch.autograd.Function):
+    """wm_distort on the tape: y = g_r x + s_r z per row of a contiguous fp32 CUDA tensor (all leading axes are rows), with the row's gain,
+    SNR and noise coin drawn in the kernel from (seed, draw, row0 + r).  bounds = (gain_lo, gain_hi, snr_lo, snr_hi, p_noise).  Returns
+    (y, stat), stat (rows, 4) = {g_r, s_r, ms_r, snr_db_r or inf}, not differentiable.  Saved for the backward: x and stat -- never the
+    noise, which wm_distort_bwd regenerates from the same counters.  through: the noise level s_r takes part in the gradient."""
+
+    @staticmethod
+    def _scratch(rows, n, device):
+        import ctypes
+        need = ctypes.c_longlong(0)
+        lib.wm_distort_plan(rows, n, ctypes.addressof(need), None)
+        return _f32(need.value, device=device)
+
+    @staticmethod
+    def forward(ctx, x, bounds, seed, draw, row0, through):
+        x = _chk(x, "x")
+        if x.dim() < 1 or x.numel() == 0:
+            raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+        n = x.shape[-1]
+        rows = x.numel() // n
+        seed = int(seed) & (2 ** 64 - 1)
+        ctx.key = (rows, n, int(row0), seed - 2 ** 64 if seed >= 2 ** 63 else seed, int(draw))
+        ctx.through = bool(through)
+        y, stat = torch.empty_like(x), _f32(rows, 4, device=x.device)
+        lib.wm_distort(_p(x), _p(y), _p(stat), _p(DistortFn._scratch(rows, n, x.device)), *ctx.key, *map(float, bounds), _stream())
+        ctx.save_for_backward(x, stat)
+        ctx.mark_non_differentiable(stat)
+        return y, stat
+
+    @staticmethod
+    def backward(ctx, g, _gstat):
+        x, stat = ctx.saved_tensors
+        g = _chk(g, "grad")
+        dx = torch.empty_like(x)
+        lib.wm_distort_bwd(_p(g), _p(x), _p(stat), _p(dx), _p(DistortFn._scratch(*ctx.key[:2], x.device)), *ctx.key, int(ctx.through),
+                           _stream())
+        return dx, None, None, None, None, None

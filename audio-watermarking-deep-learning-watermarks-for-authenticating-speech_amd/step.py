@@ -69,6 +69,16 @@ def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec
     return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec)
 
 
+def _eval_reductions(logits, message, delta):
+    """evaluate_model's per-clip reductions (:386-403) of the Detector's logits on cat([watermarked, clean]) (2B rows)"""
+    B = delta.shape[0]
+    probs = torch.sigmoid(logits[:, :, 0]).mean(dim=1)
+    decoded = (torch.sigmoid(logits[:B, :, 1:]) > 0.5).float().mean(dim=1) > 0.5
+    bits = ((message.unsqueeze(1) & (1 << torch.arange(logits.shape[-1] - 1, device=logits.device))) > 0)
+    return OrderedDict(delta=delta, logits=logits, prob_watermarked=probs[:B], prob_clean=probs[B:],
+                       bit_accuracy=(decoded == bits).float().mean(dim=1), delta_rms=torch.sqrt((delta ** 2).mean(dim=[1, 2])))
+
+
 @torch.no_grad()
 def eval_forward(generator, detector, s, message, codec=None):
     """evaluate_model's per-batch quantities (:383-403).  In eval mode BatchNorm uses running statistics, so the Detector's
@@ -77,7 +87,6 @@ def eval_forward(generator, detector, s, message, codec=None):
     concatenated afterwards (bit-identical to the single 2B-row call).
     `codec` (a codec.PcmCodec): the Detector sees codec(s + delta), as in main15c's validate_one_epoch, on both branches; the processed
     signal is returned as "s_w"."""
-    B = s.shape[0]
     overlap = (not generator.training) and (not detector.training) and s.is_cuda
     box = {}
     if overlap:
@@ -93,11 +102,7 @@ def eval_forward(generator, detector, s, message, codec=None):
         logits = torch.cat([lg_wm, box["lg"]], dim=0)
     else:
         logits = detector(torch.cat([s_w, s], dim=0))
-    probs = torch.sigmoid(logits[:, :, 0]).mean(dim=1)
-    decoded = (torch.sigmoid(logits[:B, :, 1:]) > 0.5).float().mean(dim=1) > 0.5
-    bits = ((message.unsqueeze(1) & (1 << torch.arange(logits.shape[-1] - 1, device=s.device))) > 0)
-    out = OrderedDict(delta=delta, logits=logits, prob_watermarked=probs[:B], prob_clean=probs[B:],
-                      bit_accuracy=(decoded == bits).float().mean(dim=1), delta_rms=torch.sqrt((delta ** 2).mean(dim=[1, 2])))
+    out = _eval_reductions(logits, message, delta)
     if codec is not None:
         out["s_w"] = s_w
     return out

@@ -374,6 +374,40 @@ int wm_biquad_plan(int warm, int* chunk_len, wm_stream_t stream);
 int wm_biquad(const float* x, void* out, void* mask_out, const void* mask_in, float b0, float b1, float b2, float a1, float a2,
               long long rows, long long n, int warm, int mode, int clamp, int reverse, wm_stream_t stream);
 
+/* ---- channel distortions: per-row gain and white Gaussian noise at a per-row SNR, forward and backward ------------------
+ * the "volume changes" and "additive noise" of the reference README's "Robustness Testing" section as a step of the graph (the reference
+ * ships no code for them).  x (rows, n) fp32, rows >= 1, 1 <= n <= 2^34, every row on its own:
+ *     ms_r = (1/n) sum_t x[r][t]^2      g_r = 10^(gain_db_r / 20)      s_r = |g_r| sqrt(ms_r) 10^(-snr_db_r / 20)   (0: the row gets no noise)
+ *     y[r][t] = g_r x[r][t] + s_r z(seed, draw, row0 + r, t)            as fmaf(s_r, z, g_r * x); g_r * x alone where s_r == 0
+ *   so the SNR of a noisy row is snr_db_r.  0 dB is exactly 1: gain_lo = gain_hi = 0 with p_noise = 0 hands x on bit for bit.
+ *   z: Philox4x32-10, key (seed low word, seed high word), counter (q low, q high, row0 + r, draw), q = t >> 2; its words o0..o3 give
+ *     u = ((o >> 9) + 0.5) * 2^-23 and samples 4q, 4q+1 = sqrt(-2 ln u(o0)) * (cos, sin)(2 pi u(o1)), 4q+2, 4q+3 the same from (o2, o3), with
+ *     the accurate logf / sincospif; |z| <= 5.77.  Nothing of it is stored: the backward call regenerates it.
+ *   The row's parameters are drawn in the kernel from the counter (0xFFFFFFFF, 0xFFFFFFFF, row0 + r, draw), which no sample has:
+ *     gain_db_r = fmaf(gain_hi - gain_lo, u(o0), gain_lo), snr_db_r = fmaf(snr_hi - snr_lo, u(o1), snr_lo), noise iff u(o2) < p_noise
+ *     (lo == hi: a fixed value; p_noise = 0: gain only).  0 <= row0, row0 + rows <= 2^32, 0 <= draw < 2^32; seed: any 64 bits.
+ *   stat (rows, 4) fp32 out: {g_r, s_r, ms_r, snr_db_r or +inf where the row got no noise}.
+ *   scratch: wm_distort_plan(rows, n) fp32 elements (host-only query, scratch_floats is a HOST pointer, stream unused), caller-allocated.
+ * A sample's bits depend on x, the scalars, seed, draw, row0 + r and t only -- never on the grid or on the rows of the launch: rows [0, R) in
+ * one call equal R one-row calls with row0 = r.  No atomics.  ms_r is added in one order, a function of n: segments of 16384 samples, in
+ * each 256 lanes over the row's quads i, i + 256, ... with one fmaf chain per position in the quad, (c0 + c1) + (c2 + c3), the xor butterfly
+ * 32..1 over a wave, waves 0 + 1 + 2 + 3; the segment totals of a longer row (one workgroup each) by one wave, lane j over segments j, j + 64, ...
+ * and the same butterfly.  One call enqueues the sum kernel, for n > 16384 the kernel that adds segment totals, and the apply kernel.
+ * x, y, stat and scratch may start at any multiple of 4 bytes; y leaves as 16-byte accesses wherever a whole aligned group lies inside the
+ * row, and x is read so when it shares y's alignment (the sums read a row that does not start on a 16-byte boundary by 4-byte loads: their
+ * order counts quads from the row start).  IN PLACE IS REFUSED: y (dx) may not overlap x (dy, x).
+ * wm_distort_bwd, for the same (rows, n, row0, seed, draw) and the stat of the forward call:
+ *     dx[r][t] = g_r dy[r][t] + through * (s_r x[r][t] / (n ms_r)) * sum_u dy[r][u] z(.., u)
+ *   the second term 0 where ms_r == 0 or the row had no noise; the row sum in the order above (fmaf(dy, z, chain)).  through = 0: the noise level
+ *   is a constant, dx = g_r * dy bit for bit, and z is not generated.
+ * hipErrorInvalidValue before any launch: rows or n < 1, n > 2^34, row0 or draw out of range, a null or misaligned pointer, p_noise outside
+ * [0, 1], a non-finite bound, lo > hi, overlapping input and output. */
+int wm_distort_plan(long long rows, long long n, long long* scratch_floats, wm_stream_t stream);
+int wm_distort(const float* x, float* y, float* stat, float* scratch, long long rows, long long n, long long row0, long long seed,
+               long long draw, float gain_lo, float gain_hi, float snr_lo, float snr_hi, float p_noise, wm_stream_t stream);
+int wm_distort_bwd(const float* dy, const float* x, const float* stat, float* dx, float* scratch, long long rows, long long n,
+                   long long row0, long long seed, long long draw, int through, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
