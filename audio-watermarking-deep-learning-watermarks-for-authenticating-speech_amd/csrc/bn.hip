@@ -68,27 +68,6 @@ __global__ void bn_eval_kernel(const float* gamma, const float* beta, const floa
 #ifndef WM_BNAR_UNROLL
 #define WM_BNAR_UNROLL 4
 #endif
-#ifndef WM_STREAM_NT
-#define WM_STREAM_NT 1      // nontemporal loads / stores on the frame streams: 0.59 -> 0.57 ms (bn_add_relu), 0.34 -> 0.32 ms (sums pass) at B = 256
-#endif
-// frame-sized operands that are read / written once per launch (1 GB per frame at B = 256: far beyond L2 + Infinity Cache)
-__device__ __forceinline__ float4 stream_load(const float4* p) {
-#if WM_STREAM_NT
-    typedef float f32x4_ __attribute__((ext_vector_type(4)));
-    const f32x4_ v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void stream_store(float4* p, const float4& v) {
-#if WM_STREAM_NT
-    typedef float f32x4_ __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f32x4_{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_*>(p));
-#else
-    *p = v;
-#endif
-}
 // out = relu(x + y*scale[c] + shift[c]);  grid (rows = B*64), float4 over T
 // MASK: also record sign(out) as one bit per element -- the only thing the backward needs from `out`.  Layout: natural bit
 // order, mask[row][t / 32] bit (t % 32), ceil(T / 32) dwords per (clip, channel) row -- any consumer finds the bits of a run of

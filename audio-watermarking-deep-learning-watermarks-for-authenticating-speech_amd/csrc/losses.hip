@@ -8,15 +8,6 @@ using namespace wm;
 
 namespace {
 
-// softplus(-|x|) = log1p(e^-|x|) on the hardware transcendentals: u = e^-|x| in (0, 1]; a cubic series below 0.01 (error
-// < 3e-9 absolute), log(1 + u) above (the rounding of 1 + u costs <= 6e-6 relative there).  libm's log1pf/expf pair made
-// the 139 M-element pass VALU-bound (0.7 ms at B = 256).
-__device__ __forceinline__ float softplus_neg_abs(float x) {
-    const float u = __expf(-fabsf(x));
-    return (u < 0.01f) ? u * fmaf(u, fmaf(u, 0.33333334f, -0.5f), 1.0f) : __logf(1.0f + u);
-}
-__device__ __forceinline__ float bce_logits(float x, float y) { return fmaxf(x, 0.f) - x * y + softplus_neg_abs(x); }
-
 // Both BCE kernels walk one clip's [T][NO] logits in flat, coalesced order: grid = (chunks of 4096 elements, clips).
 // The channel o = idx % NO comes from a float reciprocal with a fix-up (idx < 2^23): the 64-bit div/mod per element of
 // the first version made these kernels 6x slower than the memory system allows.
@@ -71,10 +62,9 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ 
         if (idx < per_clip) {
             const int o = mod_small(idx, NO, inv);
             const float x = lp[idx];
-            const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-x));     // as in the LSTM gates: error <= 3e-8
             float d;
-            if (o == 0) d = kl * (sg - yl);
-            else d = (r < B) ? kb * (sg - (float)((msg >> (o - 1)) & 1)) : 0.f;
+            if (o == 0) d = bce_logits_grad(x, yl, kl);
+            else d = (r < B) ? bce_logits_grad(x, (float)((msg >> (o - 1)) & 1), kb) : 0.f;
             dp[idx] = d;
         }
     }
@@ -118,6 +108,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 }  // namespace
+
+namespace wm {
+int launch_sum_scale2(const float* partial, int n, double scale, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(256), 0, stream, partial, n, scale, out);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace wm
 
 extern "C" {
 

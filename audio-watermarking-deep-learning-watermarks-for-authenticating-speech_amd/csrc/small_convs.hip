@@ -245,6 +245,54 @@ __global__ __launch_bounds__(256) void head1_fwd_kernel(const float* __restrict_
     reinterpret_cast<float4*>(y)[i] = o;
 }
 
+// head1 with the ResBlock tail in front of it: v = relu(x + y2*scale[c] + shift[c]) (bn_add_relu_kernel's expression, csrc/bn.hip)
+// is formed here, stored to `out` (head1_bwd's saved input) and never read back; MASK: its sign bits in wm_bn_add_relu_mask's
+// layout.  block = (clip, 1024-step tile), so that lane & 7 == q & 7 and eight lanes cover one mask word (merged by three lane
+// exchanges, which need all 64 lanes: no early return, lanes past the clip work on a clamped address and store nothing).
+// Channels go in groups of 8 with the group's loads issued first; the channel order into the one accumulator is head1_fwd_kernel's.
+template <bool MASK>
+__global__ __launch_bounds__(256) void head1_tail_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y2,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             float* __restrict__ out, unsigned* __restrict__ mask,
+                                                             const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ y, int T4) {
+    const int tilesPerClip = (T4 + 255) / 256;
+    const int b = blockIdx.x / tilesPerClip, q = (blockIdx.x % tilesPerClip) * 256 + (int)threadIdx.x;
+    const bool ok = q < T4;
+    const int lane = threadIdx.x & 63, nw = (T4 + 7) >> 3;
+    const size_t base = (size_t)b * 64 * T4 + min(q, T4 - 1);
+    const float4* x4 = reinterpret_cast<const float4*>(x) + base;
+    const float4* y4 = reinterpret_cast<const float4*>(y2) + base;
+    float4* o4 = reinterpret_cast<float4*>(out) + base;
+    const float b0 = bias[0];
+    float4 o = make_float4(b0, b0, b0, b0);
+#pragma unroll 1
+    for (int c0 = 0; c0 < 64; c0 += 8) {
+        float4 a[8], r[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { a[k] = stream_load(x4 + (size_t)(c0 + k) * T4); r[k] = stream_load(y4 + (size_t)(c0 + k) * T4); }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int c = c0 + k;
+            const float sc = scale[c], sh = shift[c], wc = w[c];
+            float4 v;
+            v.x = fmaxf(a[k].x + fmaf(r[k].x, sc, sh), 0.f);
+            v.y = fmaxf(a[k].y + fmaf(r[k].y, sc, sh), 0.f);
+            v.z = fmaxf(a[k].z + fmaf(r[k].z, sc, sh), 0.f);
+            v.w = fmaxf(a[k].w + fmaf(r[k].w, sc, sh), 0.f);
+            if (ok) stream_store(o4 + (size_t)c * T4, v);
+            if (MASK) {
+                unsigned m = ((v.x > 0.f) ? 1u : 0u) | ((v.y > 0.f) ? 2u : 0u) | ((v.z > 0.f) ? 4u : 0u) | ((v.w > 0.f) ? 8u : 0u);
+                m = ok ? m << (4 * (lane & 7)) : 0u;
+                m |= __shfl_xor(m, 1); m |= __shfl_xor(m, 2); m |= __shfl_xor(m, 4);
+                if ((lane & 7) == 0 && ok) mask[((size_t)b * 64 + c) * nw + (q >> 3)] = m;
+            }
+            o.x = fmaf(wc, v.x, o.x); o.y = fmaf(wc, v.y, o.y); o.z = fmaf(wc, v.z, o.z); o.w = fmaf(wc, v.w, o.w);
+        }
+    }
+    if (ok) reinterpret_cast<float4*>(y)[(size_t)b * T4 + q] = o;
+}
+
 // dx[c,t] = w[c] g[t];  dw[c] = sum g[t] x[c,t];  db = sum g   -> partial[block][65]
 __global__ __launch_bounds__(256) void head1_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                         const float* __restrict__ w, float* __restrict__ dx,
@@ -278,75 +326,115 @@ __global__ __launch_bounds__(256) void head1_bwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------ headN
-// logits[b,t,o] = bias[o] + sum_c w[o][c] x[b,c,t]     NO = 1 + message_bits (<= 17)
-template <int NO>
-__global__ __launch_bounds__(256) void headN_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, float* __restrict__ y, int T) {
-    // One thread = one time step: its 64 channel values sit in registers and every weight is a wave-uniform scalar
-    // operand (s_load through the scalar cache) -- the first version broadcast the weights through LDS reads, whose
-    // return path (64 lanes x 16 B per read) bounded the kernel at half the HBM rate.
-    __shared__ float os[256 * NO];
-    const int tilesPerClip = (T + 255) / 256;
-    const int b = blockIdx.x / tilesPerClip, t0 = (blockIdx.x % tilesPerClip) * 256;
-    const int t = min(t0 + (int)threadIdx.x, T - 1);           // clamped: lanes past T compute a copy that is never stored
-    const float* xb = x + (size_t)b * 64 * T + t;
-    float v[64];
-#pragma unroll
-    for (int c = 0; c < 64; ++c) v[c] = xb[(size_t)c * T];
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-        const float* wo = w + o * 64;                            // uniform address: scalar loads
-        float a0 = bias[o], a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 64; c += 4) {
-            a0 = fmaf(wo[c], v[c], a0); a1 = fmaf(wo[c + 1], v[c + 1], a1);
-            a2 = fmaf(wo[c + 2], v[c + 2], a2); a3 = fmaf(wo[c + 3], v[c + 3], a3);
-        }
-        os[threadIdx.x * NO + o] = (a0 + a1) + (a2 + a3);
-    }
-    __syncthreads();
-    const int nvalid = min(256, T - t0) * NO;
-    float* yb = y + ((size_t)b * T + t0) * NO;
-    for (int i = threadIdx.x; i < nvalid; i += 256) yb[i] = os[i];
-}
-
 // i / d for 0 <= i <= 2^14 and 2 <= d <= 64, with magic = ceil(2^32 / d): the error i * (magic - 2^32/d) / 2^32 < 2^-18 stays
 // below the 1/d gap between i/d and the next integer
 __device__ __forceinline__ int div_small(int i, unsigned magic) { return (int)__umulhi((unsigned)i, magic); }
 
-// The same computation at a run-time width 2 <= no <= 64 (1 and 17 take the exact-width instantiations above).  The loop over
-// outputs is not unrolled or software-pipelined: either keeps more weights live than there are scalar registers and spills.  The
-// staging rows get the odd stride no | 1: a row stride of 32 or 64 floats would put every lane's store on one bank.
-__global__ __launch_bounds__(256) void headN_fwd_any_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ bias, float* __restrict__ y, int T,
-                                                            int no, unsigned magic) {
-    extern __shared__ float os[];                                // [256][no | 1]
-    const int OS = no | 1;
+// logits[r,t,o] = bias[o] + sum_c w[o][c] v[r,c,t]     NO = 1 + message_bits
+// One thread = one time step: its 64 channel values sit in registers and every weight is a wave-uniform scalar
+// operand (s_load through the scalar cache) -- the first version broadcast the weights through LDS reads, whose
+// return path (64 lanes x 16 B per read) bounded the kernel at half the HBM rate.
+// NOC > 0: the width is a compile-time constant (1 and 17: the 0- and 16-bit models).  NOC == 0: a run-time width 2 <= no <= 64 with
+// magic = ceil(2^32 / no); the loop over outputs is then not unrolled or software-pipelined (either keeps more weights live than
+// there are scalar registers and spills) and the staging rows get the odd stride no | 1 (a row stride of 32 or 64 floats would put
+// every lane's store on one bank).
+// TAIL: v = relu(x + y2*scale[c] + shift[c]), the ResBlock tail in bn_add_relu_kernel's own expression (csrc/bn.hip), formed here in
+//   groups of 16 channels (the group's loads first, then its tail and stores) and stored to `out` -- headN_bwd's saved input, never
+//   read back in forward.  mask (optional): the sign bits in wm_bn_add_relu_mask's layout; a wave's ballot of v > 0 IS words
+//   t / 32, t / 32 + 1 of one row; lane c keeps channel c's pair and writes it at the end.  Lanes past T (clamped address) add zero
+//   bits and store nothing.  Else v = x.
+// LOSS: both BCE sums of bce_fwd_kernel (csrc/losses.hip) from the logits the thread holds: partial[block] = sum of the detection
+//   terms (output 0, label 1 for rows < BL), partial[gridDim.x + block] = sum of the bit terms (outputs >= 1 of rows < BL).
+template <int NOC, bool TAIL, bool LOSS>
+__global__ __launch_bounds__(256) void headN_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y2,
+                                                        const float* __restrict__ scale, const float* __restrict__ shift,
+                                                        float* __restrict__ out, unsigned* __restrict__ mask,
+                                                        const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ y, const long long* __restrict__ message, int BL,
+                                                        float* __restrict__ partial, int T, int no, unsigned magic) {
+    extern __shared__ float os[];                                // [256][OS]
+    __shared__ float scratch[8];
+    const int NO = NOC > 0 ? NOC : no, OS = NOC > 0 ? NOC : (no | 1);
     const int tilesPerClip = (T + 255) / 256;
     const int b = blockIdx.x / tilesPerClip, t0 = (blockIdx.x % tilesPerClip) * 256;
-    const int t = min(t0 + (int)threadIdx.x, T - 1);
-    const float* xb = x + (size_t)b * 64 * T + t;
+    const bool valid = t0 + (int)threadIdx.x < T;
+    const int t = min(t0 + (int)threadIdx.x, T - 1);           // clamped: lanes past T compute a copy that is never stored
+    const size_t base = (size_t)b * 64 * T + t;
     float v[64];
+    if constexpr (TAIL) {
+        const int lane = threadIdx.x & 63;
+        unsigned mlo = 0u, mhi = 0u;
 #pragma unroll
-    for (int c = 0; c < 64; ++c) v[c] = xb[(size_t)c * T];
-#pragma unroll 1
-    for (int o = 0; o < no; ++o) {
+        for (int c0 = 0; c0 < 64; c0 += 16) {
+            float xa[16], ya[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) { xa[k] = stream_load(x + base + (size_t)(c0 + k) * T); ya[k] = stream_load(y2 + base + (size_t)(c0 + k) * T); }
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[c0 + k] = fmaxf(xa[k] + fmaf(ya[k], scale[c0 + k], shift[c0 + k]), 0.f);
+            if (valid) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) stream_store(out + base + (size_t)(c0 + k) * T, v[c0 + k]);
+            }
+            if (mask) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const unsigned long long bal = __ballot(valid && v[c0 + k] > 0.f);
+                    if (lane == c0 + k) { mlo = (unsigned)bal; mhi = (unsigned)(bal >> 32); }
+                }
+            }
+        }
+        if (mask) {
+            const int nw = (T + 31) >> 5, w0 = (t0 >> 5) + 2 * (int)(threadIdx.x >> 6);
+            unsigned* mrow = mask + ((size_t)b * 64 + lane) * nw;
+            if (w0 < nw) mrow[w0] = mlo;
+            if (w0 + 1 < nw) mrow[w0 + 1] = mhi;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 64; ++c) v[c] = x[base + (size_t)c * T];
+    }
+    float sl = 0.f, sb = 0.f, yl = 0.f;
+    long long msg = 0;
+    if constexpr (LOSS) {
+        if (b < BL) { msg = message[b]; yl = 1.f; }
+    }
+    auto one_output = [&](int o) {
         const float* wo = w + o * 64;                            // uniform address: scalar loads
-        __builtin_amdgcn_sched_barrier(0);                      // keep the next output's 64 weights from being hoisted
         float a0 = bias[o], a1 = 0.f, a2 = 0.f, a3 = 0.f;
 #pragma unroll
         for (int c = 0; c < 64; c += 4) {
             a0 = fmaf(wo[c], v[c], a0); a1 = fmaf(wo[c + 1], v[c + 1], a1);
             a2 = fmaf(wo[c + 2], v[c + 2], a2); a3 = fmaf(wo[c + 3], v[c + 3], a3);
         }
-        os[threadIdx.x * OS + o] = (a0 + a1) + (a2 + a3);
+        const float lg = (a0 + a1) + (a2 + a3);
+        os[threadIdx.x * OS + o] = lg;
+        if constexpr (LOSS) {
+            const float term = valid ? bce_logits(lg, o == 0 ? yl : (float)((msg >> ((o - 1) & 63)) & 1)) : 0.f;
+            if (o == 0) sl += term;
+            else if (b < BL) sb += term;
+        }
+    };
+    if constexpr (NOC > 0) {
+#pragma unroll
+        for (int o = 0; o < NOC; ++o) one_output(o);
+    } else {
+#pragma unroll 1
+        for (int o = 0; o < no; ++o) {
+            __builtin_amdgcn_sched_barrier(0);                  // keep the next output's 64 weights from being hoisted
+            one_output(o);
+        }
     }
     __syncthreads();
-    const int nvalid = min(256, T - t0) * no;
-    float* yb = y + ((size_t)b * T + t0) * no;
+    const int nvalid = min(256, T - t0) * NO;
+    float* yb = y + ((size_t)b * T + t0) * NO;
     for (int i = threadIdx.x; i < nvalid; i += 256) {
-        const int r = div_small(i, magic);
-        yb[i] = os[r * OS + (i - r * no)];
+        if constexpr (NOC > 0) yb[i] = os[i];
+        else { const int r = div_small(i, magic); yb[i] = os[r * OS + (i - r * NO)]; }
+    }
+    if constexpr (LOSS) {
+        sl = block_sum<4>(sl, scratch);
+        sb = block_sum<4>(sb, scratch + 4);
+        if (threadIdx.x == 0) { partial[blockIdx.x] = sl; partial[gridDim.x + blockIdx.x] = sb; }
     }
 }
 
@@ -357,14 +445,24 @@ __global__ __launch_bounds__(256) void headN_fwd_any_kernel(const float* __restr
 // NOC > 0: the width is a compile-time constant (1 and 17: the 0- and 16-bit models, NT = 1).  NOC == 0: any width
 // 2 <= no <= 32*NT, given at run time with magic = ceil(2^32 / no) for the tile scatter.
 // partial[block][NO*64 + NO]
-template <int NOC, int NT>
+// DL: g holds the LOGITS, and the gradient of g_loc * loc + g_bce * bce is formed from them while the tile is staged -- element for
+// element what bce_bwd_kernel (csrc/losses.hip) would have written (rows < BL carry a message and the label 1), so neither that
+// launch nor its [B,T,NO] tensor exists.  Everything behind the staging is the same code on the same values.
+template <int NOC, int NT, bool DL>
 __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                         const float* __restrict__ w, float* __restrict__ dx,
-                                                        float* __restrict__ partial, int B, int T, int no, unsigned magic) {
+                                                        float* __restrict__ partial, int B, int T, int no, unsigned magic,
+                                                        const long long* __restrict__ message, const float* __restrict__ g_loc,
+                                                        const float* __restrict__ g_bce, int BL) {
     constexpr int XS = 257, OB = 32 * NT, GS = OB + 1;
     constexpr int NOMAX = NOC > 0 ? NOC : OB;
     const int NO = NOC > 0 ? NOC : no;
     const int KS = (NO + 1) / 2;                 // k-steps of the dx product
+    float kl = 0.f, kb = 0.f;                    // DL: the scales of bce_bwd_kernel
+    if constexpr (DL) {
+        kl = g_loc[0] / (float)((double)B * T);
+        kb = (NO > 1) ? g_bce[0] / (float)((double)BL * T * (NO - 1)) : 0.f;
+    }
     extern __shared__ __align__(16) float smem[];
     float* xs = smem;                  // [64][XS]
     float* gsm = xs + 64 * XS;         // [256][GS], columns >= NO are zero
@@ -403,6 +501,10 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
     auto write_tile = [&](int tile) {
         const int t0 = (tile % tilesPerClip) * 256;
         const int nt = min(256, T - t0);
+        const int row = tile / tilesPerClip;
+        long long msg = 0;
+        if constexpr (DL) msg = (row < BL) ? message[row] : 0;
+        const float yl = row < BL ? 1.f : 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const int i = tid + k * 256, c = i >> 6, q = i & 63;
@@ -420,9 +522,13 @@ __global__ __launch_bounds__(256) void headN_bwd_kernel(const float* __restrict_
                 for (int j = 0; j < 4; ++j) {
                     const int i = 4 * f + j;
                     if (i < 256 * NO) {
-                        const float val = (i < nt * NO) ? e[j] : 0.f;
-                        if constexpr (NOC > 0) gsm[(i / NO) * GS + (i % NO)] = val;
-                        else { const int r = div_small(i, magic); gsm[r * GS + (i - r * NO)] = val; }
+                        const int r = NOC > 0 ? i / NO : div_small(i, magic), o = i - r * NO;
+                        float val = e[j];
+                        if constexpr (DL) {
+                            if (o == 0) val = bce_logits_grad(val, yl, kl);
+                            else val = (row < BL) ? bce_logits_grad(val, (float)((msg >> (o - 1)) & 1), kb) : 0.f;
+                        }
+                        gsm[r * GS + o] = (i < nt * NO) ? val : 0.f;
                     }
                 }
             }
@@ -564,6 +670,17 @@ int wm_head1_fwd(const float* x, const float* w, const float* bias, float* y, in
     return 0;
 }
 
+// wm_bn_add_relu(_mask) + wm_head1_fwd in one launch: out = relu(x + y2*scale + shift) is written once and not read back
+int wm_head1_tail_fwd(const float* x, const float* y2, const float* scale, const float* shift, const float* w, const float* bias,
+                      float* out, void* mask, float* y, int B, int T, hipStream_t stream) {
+    if ((T & 3) || B <= 0 || !y2 || !out) return (int)hipErrorInvalidValue;
+    const int T4 = T / 4, grid = B * ((T4 + 255) / 256);
+    if (mask) hipLaunchKernelGGL(head1_tail_fwd_kernel<true>, dim3(grid), dim3(256), 0, stream, x, y2, scale, shift, out, (unsigned*)mask, w, bias, y, T4);
+    else hipLaunchKernelGGL(head1_tail_fwd_kernel<false>, dim3(grid), dim3(256), 0, stream, x, y2, scale, shift, out, (unsigned*)nullptr, w, bias, y, T4);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
 // partial: >= 1024*65 floats.  dwb: [65] = dw[64] followed by db[1] (two separate tensors on the host side).
 int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int accumulate, hipStream_t stream) {
@@ -581,41 +698,111 @@ int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, floa
     return 0;
 }
 
-// NO = 1 + message_bits, 1 <= NO <= 64 (message ids are int64: at most 63 bits).  1 and 17 run exact-width instantiations.
-int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, hipStream_t stream) {
-    if (NO < 1 || NO > 64) return (int)hipErrorInvalidValue;
-    const int grid = B * ((T + 255) / 256);
-    if (NO == 17) hipLaunchKernelGGL(headN_fwd_kernel<17>, dim3(grid), dim3(256), 0, stream, x, w, bias, y, T);
-    else if (NO == 1) hipLaunchKernelGGL(headN_fwd_kernel<1>, dim3(grid), dim3(256), 0, stream, x, w, bias, y, T);
-    else {
-        const size_t lds = (size_t)256 * (NO | 1) * sizeof(float);
+}  // extern "C"
+
+namespace {
+struct HeadNFwd {
+    const float *x, *y2, *scale, *shift, *w, *bias;
+    float *out, *y, *partial;
+    unsigned* mask;
+    const long long* message;
+    int BL, R, T, NO;
+};
+template <int NOC, bool TAIL, bool LOSS>
+int launch_headN_fwd(const HeadNFwd& a, hipStream_t stream) {
+    const size_t lds = (size_t)256 * (NOC > 0 ? NOC : (a.NO | 1)) * sizeof(float);
+    if constexpr (NOC == 0) {                                   // up to 65 KB of staging rows
         static wm::DevOnce done;
         if (!wm::dev_done(done)) {
-            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_fwd_any_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 65 * (int)sizeof(float)));
+            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_fwd_kernel<NOC, TAIL, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 65 * (int)sizeof(float)));
             wm::dev_mark(done);
         }
-        const unsigned magic = (unsigned)((0x100000000ull + NO - 1) / NO);
-        hipLaunchKernelGGL(headN_fwd_any_kernel, dim3(grid), dim3(256), lds, stream, x, w, bias, y, T, NO, magic);
     }
+    const unsigned magic = (unsigned)((0x100000000ull + a.NO - 1) / a.NO);
+    hipLaunchKernelGGL((headN_fwd_kernel<NOC, TAIL, LOSS>), dim3(a.R * ((a.T + 255) / 256)), dim3(256), lds, stream, a.x, a.y2, a.scale,
+                       a.shift, a.out, a.mask, a.w, a.bias, a.y, a.message, a.BL, a.partial, a.T, a.NO, magic);
     WM_CHECK_LAUNCH();
+    return 0;
+}
+// 1 and 17 run exact-width instantiations
+template <bool TAIL, bool LOSS>
+int launch_headN_fwd_width(const HeadNFwd& a, hipStream_t stream) {
+    if (a.NO == 17) return launch_headN_fwd<17, TAIL, LOSS>(a, stream);
+    if (a.NO == 1) return launch_headN_fwd<1, TAIL, LOSS>(a, stream);
+    return launch_headN_fwd<0, TAIL, LOSS>(a, stream);
+}
+}  // namespace
+
+extern "C" {
+
+// NO = 1 + message_bits, 1 <= NO <= 64 (message ids are int64: at most 63 bits)
+int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, hipStream_t stream) {
+    if (NO < 1 || NO > 64 || B <= 0 || T <= 0) return (int)hipErrorInvalidValue;
+    const HeadNFwd a{x, nullptr, nullptr, nullptr, w, bias, nullptr, y, nullptr, nullptr, nullptr, 0, B, T, NO};
+    return launch_headN_fwd_width<false, false>(a, stream);
+}
+
+// The Detector head with what surrounds it (see headN_fwd_kernel): y2 != NULL -- the ResBlock tail in front (out, optional mask);
+// message != NULL -- both BCE terms behind (partial: >= 2 * R * ceil(T / 256) floats; finished in fp64 and a fixed order with
+// wm_bce_fwd's scales; NO == 1 leaves bce_out untouched, as wm_bce_fwd does)
+int wm_headN_tail_fwd(const float* x, const float* y2, const float* scale, const float* shift, const float* w, const float* bias,
+                      const long long* message, int B, float* partial, float* loc_out, float* bce_out, float* out, void* mask,
+                      float* logits, int R, int T, int NO, hipStream_t stream) {
+    if (NO < 1 || NO > 64 || R <= 0 || T <= 0) return (int)hipErrorInvalidValue;
+    if (y2 && (!scale || !shift || !out)) return (int)hipErrorInvalidValue;
+    if (message && (B < 0 || B > R || !partial || !loc_out || (NO > 1 && !bce_out))) return (int)hipErrorInvalidValue;
+    const HeadNFwd a{x, y2, scale, shift, w, bias, out, logits, partial, y2 ? (unsigned*)mask : nullptr, message, B, R, T, NO};
+    const int rc = y2 ? (message ? launch_headN_fwd_width<true, true>(a, stream) : launch_headN_fwd_width<true, false>(a, stream))
+                      : (message ? launch_headN_fwd_width<false, true>(a, stream) : launch_headN_fwd_width<false, false>(a, stream));
+    if (rc || !message) return rc;
+    const int grid = R * ((T + 255) / 256);
+    WM_TRY((hipError_t)wm::launch_sum_scale2(partial, grid, 1.0 / ((double)R * T), loc_out, stream));
+    if (NO > 1) WM_TRY((hipError_t)wm::launch_sum_scale2(partial + grid, grid, 1.0 / ((double)B * T * (NO - 1)), bce_out, stream));
     return 0;
 }
 
 }  // extern "C"
 
 namespace {
-// NOC, NT: see headN_bwd_kernel.  LDS: x tile [64][257], g tile [256][32*NT+1], weights [32*NT][64] -- 145.25 KB at NT = 2
-template <int NOC, int NT>
-int launch_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, int grid, int B, int T, int NO,
-                     hipStream_t stream) {
+// NOC, NT, DL: see headN_bwd_kernel.  LDS: x tile [64][257], g tile [256][32*NT+1], weights [32*NT][64] -- 145.25 KB at NT = 2
+struct HeadNBwd {
+    const float *g, *x, *w;
+    float *dx, *partial;
+    const long long* message;           // DL: g = logits, with the three below
+    const float *g_loc, *g_bce;
+    int BL, R, T, NO;
+};
+template <int NOC, int NT, bool DL>
+int launch_headN_bwd(const HeadNBwd& a, int grid, hipStream_t stream) {
     constexpr size_t lds = (size_t)(64 * 257 + 256 * (32 * NT + 1) + 32 * NT * 64) * sizeof(float);
     static wm::DevOnce done;
     if (!wm::dev_done(done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<NOC, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<NOC, NT, DL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         wm::dev_mark(done);
     }
-    const unsigned magic = NO > 1 ? (unsigned)((0x100000000ull + NO - 1) / NO) : 0u;
-    hipLaunchKernelGGL((headN_bwd_kernel<NOC, NT>), dim3(grid), dim3(256), lds, stream, g, x, w, dx, partial, B, T, NO, magic);
+    const unsigned magic = a.NO > 1 ? (unsigned)((0x100000000ull + a.NO - 1) / a.NO) : 0u;
+    hipLaunchKernelGGL((headN_bwd_kernel<NOC, NT, DL>), dim3(grid), dim3(256), lds, stream, a.g, a.x, a.w, a.dx, a.partial, a.R, a.T, a.NO,
+                       magic, a.message, a.g_loc, a.g_bce, a.BL);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+template <bool DL>
+int headN_bwd(const HeadNBwd& a, float* dw, float* db, int accumulate, hipStream_t stream) {
+    const int NO = a.NO;
+    if (NO < 1 || NO > 64) return (int)hipErrorInvalidValue;
+    const int ntiles = a.R * ((a.T + 255) / 256);
+    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
+    int rc;
+    if (NO == 17) rc = launch_headN_bwd<17, 1, DL>(a, grid, stream);
+    else if (NO == 1) rc = launch_headN_bwd<1, 1, DL>(a, grid, stream);
+    else if (NO <= 32) rc = launch_headN_bwd<0, 1, DL>(a, grid, stream);
+    else rc = launch_headN_bwd<0, 2, DL>(a, grid, stream);
+    if (rc) return rc;
+    const int n = NO * 64 + NO;
+    // partial rows are [NO*64 weights | NO biases]; reduce the two pieces with matching row stride
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((NO * 64 + 63) / 64), dim3(256), 0, stream, (const float*)a.partial, grid, n, NO * 64, dw, accumulate);
+    WM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, stream, (const float*)a.partial + NO * 64, grid, n, NO, db, accumulate);
     WM_CHECK_LAUNCH();
     return 0;
 }
@@ -626,22 +813,18 @@ extern "C" {
 // partial: >= 256*(NO*64+NO) floats (one row per workgroup, at most one workgroup per CU)
 int wm_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int NO, int accumulate, hipStream_t stream) {
-    if (NO < 1 || NO > 64) return (int)hipErrorInvalidValue;
-    const int ntiles = B * ((T + 255) / 256);
-    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    int rc;
-    if (NO == 17) rc = launch_headN_bwd<17, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
-    else if (NO == 1) rc = launch_headN_bwd<1, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
-    else if (NO <= 32) rc = launch_headN_bwd<0, 1>(g, x, w, dx, partial, grid, B, T, NO, stream);
-    else rc = launch_headN_bwd<0, 2>(g, x, w, dx, partial, grid, B, T, NO, stream);
-    if (rc) return rc;
-    const int n = NO * 64 + NO;
-    // partial rows are [NO*64 weights | NO biases]; reduce the two pieces with matching row stride
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((NO * 64 + 63) / 64), dim3(256), 0, stream, (const float*)partial, grid, n, NO * 64, dw, accumulate);
-    WM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial + NO * 64, grid, n, NO, db, accumulate);
-    WM_CHECK_LAUNCH();
-    return 0;
+    const HeadNBwd a{g, x, w, dx, partial, nullptr, nullptr, nullptr, 0, B, T, NO};
+    return headN_bwd<false>(a, dw, db, accumulate, stream);
+}
+
+// wm_bce_bwd + wm_headN_bwd in one launch: the gradient of g_loc * loc + g_bce * bce w.r.t. the logits [R,T,NO] is formed while
+// the logits are staged (rows < B carry message[row] and the label 1); no dlogits tensor
+int wm_headN_bwd_bce(const float* logits, const long long* message, const float* g_loc, const float* g_bce, const float* x,
+                     const float* w, float* dx, float* partial, float* dw, float* db, int B, int R, int T, int NO, int accumulate,
+                     hipStream_t stream) {
+    if (!message || !g_loc || !g_bce || B < 0 || B > R) return (int)hipErrorInvalidValue;
+    const HeadNBwd a{logits, x, w, dx, partial, message, g_loc, g_bce, B, R, T, NO};
+    return headN_bwd<true>(a, dw, db, accumulate, stream);
 }
 
 }  // extern "C"

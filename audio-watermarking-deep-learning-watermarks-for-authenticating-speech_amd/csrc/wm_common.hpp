@@ -118,6 +118,58 @@ __device__ __forceinline__ double block_sum_d(double v, double* scratch) {
 
 __device__ __forceinline__ float sigmoidf_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// softplus(-|x|) = log1p(e^-|x|) on the hardware transcendentals: u = e^-|x| in (0, 1]; a cubic series below 0.01 (error
+// < 3e-9 absolute), log(1 + u) above (the rounding of 1 + u costs <= 6e-6 relative there).  libm's log1pf/expf pair made
+// the 139 M-element BCE pass VALU-bound (0.7 ms at B = 256).
+__device__ __forceinline__ float softplus_neg_abs(float x) {
+    const float u = __expf(-fabsf(x));
+    return (u < 0.01f) ? u * fmaf(u, fmaf(u, 0.33333334f, -0.5f), 1.0f) : __logf(1.0f + u);
+}
+// BCEWithLogits of one element (csrc/losses.hip, and the Detector head's forward in csrc/small_convs.hip)
+__device__ __forceinline__ float bce_logits(float x, float y) { return fmaxf(x, 0.f) - x * y + softplus_neg_abs(x); }
+// its derivative times k: the element of d(loss)/d(logits) that wm_bce_bwd writes and headN_bwd_kernel forms on load
+__device__ __forceinline__ float bce_logits_grad(float x, float y, float k) {
+    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-x));     // as in the LSTM gates: error <= 3e-8
+    return k * (sg - y);
+}
+
+// out[0] = (float)(scale * sum_i partial[i]) in fp64 and a fixed order, one workgroup (csrc/losses.hip)
+int launch_sum_scale2(const float* partial, int n, double scale, float* out, hipStream_t stream);
+
+#ifndef WM_STREAM_NT
+#define WM_STREAM_NT 1      // nontemporal loads / stores on the frame streams: 0.59 -> 0.57 ms (bn_add_relu), 0.34 -> 0.32 ms (sums pass) at B = 256
+#endif
+// frame-sized operands that are read / written once per launch (1 GB per frame at B = 256: far beyond L2 + Infinity Cache)
+__device__ __forceinline__ float4 stream_load(const float4* p) {
+#if WM_STREAM_NT
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ void stream_store(float4* p, const float4& v) {
+#if WM_STREAM_NT
+    __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ float stream_load(const float* p) {
+#if WM_STREAM_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ void stream_store(float* p, float v) {
+#if WM_STREAM_NT
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+
 // ELU (alpha = 1) with a cheap expm1: Taylor to the 6th order on (-0.35, 0] (error < 4e-7 of the value), exp(v) - 1 below
 __device__ __forceinline__ float elu1(float v) {
     const float p = v * (1.f + v * (0.5f + v * (0.16666667f + v * (0.041666668f + v * (0.0083333338f + v * 0.0013888889f)))));

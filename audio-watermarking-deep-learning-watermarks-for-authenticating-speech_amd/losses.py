@@ -106,6 +106,17 @@ def detection_losses(logits, message):
     return ops.BCEFn.apply(logits, message)
 
 
+def detect_with_losses(detector, x, message, input_grad_rows=None):
+    """(logits, loc_loss, bce) for x = cat([s_w, s]): the Detector's one-node form where it has one and it applies
+    (modules.Detector.forward_with_losses), else detector(x) followed by detection_losses."""
+    fused = getattr(detector, "forward_with_losses", None)
+    res = fused(x, message, input_grad_rows) if fused is not None else None
+    if res is not None:
+        return res
+    logits = detector(x, input_grad_rows=input_grad_rows)
+    return (logits,) + tuple(detection_losses(logits, message))
+
+
 def l1_to_zero(delta):
     """F.l1_loss(delta, zeros_like(delta)), py/main16.py:266."""
     return ops.L1Fn.apply(delta)

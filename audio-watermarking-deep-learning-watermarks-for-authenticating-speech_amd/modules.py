@@ -40,12 +40,15 @@ def _rb_args(m):
             n1.running_mean, n1.running_var, n1.num_batches_tracked, n2.running_mean, n2.running_var, n2.num_batches_tracked)
 
 
+def _hooked(*modules):
+    return any(m._forward_hooks or m._forward_pre_hooks for m in modules)
+
+
 def resblock_pair(m1, m2, x):
     """m2(m1(x)) for two ResBlocks in a row (py/main16.py:135-136, :178-179).  In a training step on the fused path the pair is
     ONE tape node (ops.ResBlockPairFn: the second block's backward also does the first block's ReLU backward and BatchNorm sums);
     otherwise -- inference, no gradients wanted, odd clip lengths, any of the knobs off, forward hooks on the blocks -- two calls."""
-    hooked = m1._forward_hooks or m2._forward_hooks or m1._forward_pre_hooks or m2._forward_pre_hooks
-    if m1.training and m2.training and not hooked and ops.pair_node_applies(x):
+    if m1.training and m2.training and not _hooked(m1, m2) and ops.pair_node_applies(x):
         return ops.ResBlockPairFn.apply(x, *_rb_args(m1), *_rb_args(m2), True)
     return m2(m1(x))
 
@@ -82,8 +85,10 @@ class Generator(nn.Module):
             vec = ops.EmbedFn.apply(self.embedding.weight, message.to(torch.int64))
         ct = self.decoder[0]
         x = ops.ConvT7Fn.apply(x, vec, ct.weight, ct.bias)
-        x = self.decoder[1](x)
-        return self.decoder[2](x)                                               # delta (B,1,T)
+        rb, head = self.decoder[1], self.decoder[2]
+        if rb.training and not _hooked(rb, head) and ops.tail_in_head_applies(x):
+            return ops.ResBlockHead1Fn.apply(x, *_rb_args(rb), head.weight, head.bias)   # the block's tail rides in the head's kernel
+        return head(rb(x))                                                      # delta (B,1,T)
 
 
 class _HeadN(nn.Conv1d):
@@ -106,6 +111,19 @@ class Detector(nn.Module):
         the train step feeds [watermarked; clean] (py/main16.py:249) and the clean half is data."""
         x = self.model[0](x) if input_grad_rows is None else self.model[0](x, input_grad_rows)
         return self.model[3](resblock_pair(self.model[1], self.model[2], x))
+
+    def forward_with_losses(self, x, message, input_grad_rows=None):
+        """(logits, loc, bce) = (self(x), *detection_losses(self(x), message)) as one tape node behind the stem (ops.DetectorTailFn), or
+        None where that node does not apply: then the caller takes the two calls.  It applies in a training step on the fused path
+        (resblock_pair's conditions), with no forward hooks from model.1 to the Detector itself and x = [watermarked; clean]."""
+        m1, m2, head = self.model[1], self.model[2], self.model[3]
+        ok = (m1.training and m2.training and not _hooked(self, self.model, m1, m2, head) and ops.tail_in_head_applies(x)
+              and ops.pair_node_applies(x) and 1 <= head.weight.shape[0] <= 64 and isinstance(message, torch.Tensor) and message.is_cuda
+              and message.dtype == torch.int64 and message.dim() == 1 and x.shape[0] == 2 * message.shape[0])
+        if not ok:
+            return None
+        x = self.model[0](x) if input_grad_rows is None else self.model[0](x, input_grad_rows)
+        return ops.DetectorTailFn.apply(x, message.contiguous(), *_rb_args(m1), *_rb_args(m2), head.weight, head.bias)
 
 
 def load_state_dict_strip_prefix(model, state_dict, prefix="_orig_mod."):

@@ -316,6 +316,20 @@ def set_lstm_bwd_wave_specialised(on: bool):
     set_switch("lstm_bwd_ws", on)
 
 
+# The ResBlock in front of a head (decoder.1 -> Conv1d(64,1,1), model.2 -> Conv1d(64,1+bits,1)) leaves its tail -- BN2 + residual add +
+# ReLU -- to the head's forward kernel, and the Detector head also sums both BCE terms and forms their gradient on load in its
+# backward (wm_head1_tail_fwd, wm_headN_tail_fwd, wm_headN_bwd_bce).  WM_TAIL_IN_HEAD=0/1 sets the default ("1" = on, else off).
+# Measured at B = 256: -0.7 ms of 48.6 per step.
+_HEADS = {"tail_in_head": os.environ.get("WM_TAIL_IN_HEAD", "1") == "1"}
+
+
+def set_tail_in_head(on: bool):
+    """1 (default): ResBlockHead1Fn / DetectorTailFn where they apply (training-mode blocks, no forward hooks, no side-stream weight
+    gradients); 0: every ResBlock ends in wm_bn_add_relu(_mask) and the losses run wm_bce_fwd / wm_bce_bwd.  Same results bit for bit,
+    except the two BCE sums (fp32 partial sums grouped differently)."""
+    _HEADS["tail_in_head"] = bool(on)
+
+
 def set_gconv_f16x3(on: bool):
     """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
     two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
@@ -411,14 +425,16 @@ def pack_w64(w: torch.Tensor, kw: int, mode: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ ResBlock
-def _resblock_fwd(x, params, training, want_grad):
+def _resblock_fwd(x, params, training, want_grad, tail=True):
     """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for params = (w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2).
-    Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx."""
+    Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx.
+    tail=False (training mode only): stop in front of the tail -- (None, saved) with mask = None; the head kernel that follows forms
+    out = relu(x + y2 * cst[4] + cst[5]) and the mask (ResBlockHead1Fn, DetectorTailFn)."""
     w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = params
     x = _frames(x, "ResBlock input", 64)
     B, _, T = x.shape
     dev, st = x.device, _stream()
-    out = torch.empty_like(x)
+    out = torch.empty_like(x) if tail else None
     cst = _f32(8, 64, device=dev)       # sc1 sh1 mean1 is1 sc2 sh2 mean2 is2
     sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
     if training:
@@ -454,6 +470,8 @@ def _resblock_fwd(x, params, training, want_grad):
         _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, None, B, T, 1, 0)
         # saved (mean, invstd) for an eval-mode backward = running statistics
         mu1.copy_(rm1); is1.copy_(torch.rsqrt(rv1 + BN_EPS)); mu2.copy_(rm2); is2.copy_(torch.rsqrt(rv2 + BN_EPS))
+    if not tail:
+        return None, (x, y1, y2, None, cst, w1, w2, g1, g2)
     if want_grad:
         # the backward needs only the SIGN of `out`: one bit per element, written beside it (a frame pass less in backward)
         mask = torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=dev)
@@ -479,46 +497,52 @@ class ResBlockFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, g_out):
-        x, y1, y2, mask, cst, w1, w2, g1, g2 = ctx.saved_tensors
-        sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
-        g_out = g_out.contiguous()
-        B, _, T = x.shape
-        dev, st = x.device, _stream()
-        ev = 0 if ctx.training else 1
-        n = float(B * T)
-        if _CONV["bf16x6"] and _CONV["fused_bwd"] and T % 64 == 0 and not all(g is not None for g in ctx.gdst):
-            dx, grads, _ = _resblock_bwd_fused(ctx.saved_tensors, ctx.training, g_out)
-            return (dx,) + grads + (None,) * 7
-        (dw1, db1, dw2, db2), acc, launch = _wgrad_dst(ctx.gdst, dev, w1.shape, (64,), w2.shape, (64,))
-        part = _f32(max(B, 1) * 128, device=dev)
-        dz2 = torch.empty_like(x)
-        lib.wm_relu_bwd_reduce_mask(_p(g_out), _p(mask), _p(y2), _p(dz2), _p(part), None, B, T, st)
-        k2 = _f32(4, 64, device=dev)          # A, B (hi), B (lo), C  -- B is handed over as hi + lo words
-        dg2, dbe2 = _f32(64, device=dev), _f32(64, device=dev)
-        lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev, None, 0, None, st)
-        # conv2: data gradient (+ ReLU mask + BN1-backward reductions in the epilogue) and weight gradient
-        dz1 = torch.empty_like(x)
-        stats = _f32(NCU * 128, device=dev)
-        _conv3(dz2, y2, w2, 1, k2[0], k2[1], k2[3], None, y1, sc1, sh1, dz1, stats, B, T, 3, 1)
+        return _resblock_bwd(ctx.saved_tensors, ctx.training, ctx.gdst, g_out) + (None,) * 7
 
-        def wgrad(dz, y, k, xin, sc, sh, xpro, dw, db):
-            wpart = _f32(2 * NCU * (3 * 4096 + 64), device=dev)
-            if _CONV["bf16x6"]:
-                lib.wm_wgrad64_bf(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
-                                  B, T, 3, xpro, 3 if acc else 0, _stream())
-            else:
-                lib.wm_wgrad64(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
-                               B, T, 3, 3, xpro, 0, 1 if acc else 0, _stream())
-        launch((dz2, y2, k2, y1, cst), lambda: wgrad(dz2, y2, k2, y1, sc1, sh1, 1, dw2, db2))
-        k1 = _f32(4, 64, device=dev)
-        dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
-        lib.wm_bn_bwd_finalize(_p(stats), NCU, n, _p(g1), _p(mu1), _p(is1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(dg1), _p(dbe1), 0, ev, None, 0, None, st)
-        # conv1: data gradient + residual path, weight gradient
-        dx = torch.empty_like(x)
-        _conv3(dz1, y1, w1, 1, k1[0], k1[1], k1[3], None, dz2, None, None, dx, None, B, T, 3, 2)
-        launch((dz1, y1, k1, x), lambda: wgrad(dz1, y1, k1, x, None, None, 0, dw1, db1))
-        g1_, g2_ = ((None, None),) * 2 if acc else ((dw1, db1), (dw2, db2))     # (dw / db stay bound: the queued launches read them later)
-        return (dx,) + g1_ + (dg1, dbe1) + g2_ + (dg2, dbe2) + (None,) * 7
+
+def _resblock_bwd(saved, training, gdst, g_out):
+    """Backward of one ResBlock: (dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2).  The fused path where it applies, else one launch per
+    product; gdst = the four weight-gradient destinations of _gdst (all None: fresh tensors, launched in line)."""
+    x, y1, y2, mask, cst, w1, w2, g1, g2 = saved
+    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
+    g_out = g_out.contiguous()
+    B, _, T = x.shape
+    dev, st = x.device, _stream()
+    ev = 0 if training else 1
+    n = float(B * T)
+    if _CONV["bf16x6"] and _CONV["fused_bwd"] and T % 64 == 0 and not all(g is not None for g in gdst):
+        dx, grads, _ = _resblock_bwd_fused(saved, training, g_out)
+        return (dx,) + grads
+    (dw1, db1, dw2, db2), acc, launch = _wgrad_dst(gdst, dev, w1.shape, (64,), w2.shape, (64,))
+    part = _f32(max(B, 1) * 128, device=dev)
+    dz2 = torch.empty_like(x)
+    lib.wm_relu_bwd_reduce_mask(_p(g_out), _p(mask), _p(y2), _p(dz2), _p(part), None, B, T, st)
+    k2 = _f32(4, 64, device=dev)          # A, B (hi), B (lo), C  -- B is handed over as hi + lo words
+    dg2, dbe2 = _f32(64, device=dev), _f32(64, device=dev)
+    lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev, None, 0, None, st)
+    # conv2: data gradient (+ ReLU mask + BN1-backward reductions in the epilogue) and weight gradient
+    dz1 = torch.empty_like(x)
+    stats = _f32(NCU * 128, device=dev)
+    _conv3(dz2, y2, w2, 1, k2[0], k2[1], k2[3], None, y1, sc1, sh1, dz1, stats, B, T, 3, 1)
+
+    def wgrad(dz, y, k, xin, sc, sh, xpro, dw, db):
+        wpart = _f32(2 * NCU * (3 * 4096 + 64), device=dev)
+        if _CONV["bf16x6"]:
+            lib.wm_wgrad64_bf(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
+                              B, T, 3, xpro, 3 if acc else 0, _stream())
+        else:
+            lib.wm_wgrad64(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
+                           B, T, 3, 3, xpro, 0, 1 if acc else 0, _stream())
+    launch((dz2, y2, k2, y1, cst), lambda: wgrad(dz2, y2, k2, y1, sc1, sh1, 1, dw2, db2))
+    k1 = _f32(4, 64, device=dev)
+    dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
+    lib.wm_bn_bwd_finalize(_p(stats), NCU, n, _p(g1), _p(mu1), _p(is1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(dg1), _p(dbe1), 0, ev, None, 0, None, st)
+    # conv1: data gradient + residual path, weight gradient
+    dx = torch.empty_like(x)
+    _conv3(dz1, y1, w1, 1, k1[0], k1[1], k1[3], None, dz2, None, None, dx, None, B, T, 3, 2)
+    launch((dz1, y1, k1, x), lambda: wgrad(dz1, y1, k1, x, None, None, 0, dw1, db1))
+    g1_, g2_ = ((None, None),) * 2 if acc else ((dw1, db1), (dw2, db2))     # (dw / db stay bound: the queued launches read them later)
+    return (dx,) + g1_ + (dg1, dbe1) + g2_ + (dg2, dbe2)
 
 
 def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
@@ -698,6 +722,98 @@ class HeadNFn(torch.autograd.Function):
         dw, db = torch.empty_like(w), _f32(NO, device=x.device)
         lib.wm_headN_bwd(_p(g), _p(x), _p(w), _p(dx), _p(part), _p(dw), _p(db), B, T, NO, 0, _stream())
         return dx, dw, db
+
+
+# ------------------------------------------------------------------------------------------ last ResBlock + head
+def tail_in_head_applies(x) -> bool:
+    """the switch and what both nodes below ask of their input (the caller adds: training-mode blocks, no forward hooks)"""
+    return _HEADS["tail_in_head"] and x.is_cuda and x.dim() == 3 and not _ASYNC["on"]
+
+
+def _tail_mask(x, want_grad):
+    B, _, T = x.shape
+    return torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=x.device) if want_grad else None
+
+
+class ResBlockHead1Fn(GradAwareFunction):
+    """decoder.1 -> decoder.2 (py/main16.py:145-146) in training mode as one tape node: the block's tail is formed inside the head's
+    forward kernel (wm_head1_tail_fwd), so its output frame is written once and not read back.  Backward = Head1Fn's, then ResBlockFn's."""
+
+    @staticmethod
+    def forward(ctx, x, *args):
+        params, hw, hb = args[:14], args[14], args[15]
+        want = wants_grad(ctx)
+        _, saved = _resblock_fwd(x, params, True, want, tail=False)
+        x, _, y2, _, cst = saved[:5]
+        B, _, T = x.shape
+        out, mask = torch.empty_like(x), _tail_mask(x, want)
+        y = _f32(B, 1, T, device=x.device)
+        lib.wm_head1_tail_fwd(_p(x), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(out), _p(mask), _p(y), B, T, _stream())
+        if want:
+            ctx.save_for_backward(*(saved[:3] + (mask,) + saved[4:] + (out, hw)))
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = ctx.saved_tensors
+        out, hw = sv[9], sv[10]
+        B, _, T = out.shape
+        dout = torch.empty_like(out)
+        part = _f32(1024 * 65, device=out.device)
+        dhw, dhb = torch.empty_like(hw), _f32(1, device=out.device)
+        lib.wm_head1_bwd(_p(g.contiguous()), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
+        return _resblock_bwd(sv[:9], True, (None,) * 4, dout) + (None,) * 6 + (dhw, dhb)
+
+
+class DetectorTailFn(GradAwareFunction):
+    """model.1 -> model.2 -> model.3 (py/main16.py:178-180) with both BCE terms (:252-264) as one tape node, for the train step on
+    the fused path (pair_node_applies).  Forward: ResBlockPairFn's, except that model.2's tail, the head and the two loss sums are one
+    launch (wm_headN_tail_fwd) -> (logits, loc, bce).  Backward: the head's backward forms the losses' gradient from the logits while
+    it loads them (wm_headN_bwd_bce), then ResBlockPairFn's backward.  A gradient arriving on `logits` takes the unfused route:
+    wm_bce_bwd's tensor plus that gradient through wm_headN_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, message, *args):
+        p1, p2, hw, hb = args[:14], args[14:28], args[28], args[29]
+        want = wants_grad(ctx)
+        mid, first = _resblock_fwd(x, p1, True, want)
+        _, second = _resblock_fwd(mid, p2, True, want, tail=False)
+        y2, cst = second[2], second[4]
+        R, _, T = mid.shape
+        NO, B, dev = hw.shape[0], message.shape[0], mid.device
+        out, mask = torch.empty_like(mid), _tail_mask(mid, want)
+        logits = _f32(R, T, NO, device=dev)
+        part = _f32(2 * R * ((T + 255) // 256), device=dev)
+        losses = torch.zeros(2, dtype=torch.float32, device=dev)
+        lib.wm_headN_tail_fwd(_p(mid), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(message), B, _p(part), _p(losses[0]), _p(losses[1]),
+                              _p(out), _p(mask), _p(logits), R, T, NO, _stream())
+        ctx.set_materialize_grads(False)
+        if want:
+            ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + (out, hw, logits, message)))
+        return logits, losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loc, g_bce):
+        sv = ctx.saved_tensors
+        s1_, s2_, (out, hw, logits, message) = sv[:9], sv[9:18], sv[18:]
+        R, T, NO = logits.shape
+        dev, st = logits.device, _stream()
+        gl = g_loc.contiguous().float().reshape(1) if g_loc is not None else torch.zeros(1, device=dev)
+        gb = g_bce.contiguous().float().reshape(1) if g_bce is not None else torch.zeros(1, device=dev)
+        dout = torch.empty_like(out)
+        part = _f32(NCU * (NO * 64 + NO), device=dev)
+        dhw, dhb = torch.empty_like(hw), _f32(NO, device=dev)
+        if g_logits is None:
+            lib.wm_headN_bwd_bce(_p(logits), _p(message), _p(gl), _p(gb), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb),
+                                 message.shape[0], R, T, NO, 0, st)
+        else:
+            d = torch.empty_like(logits)
+            lib.wm_bce_bwd(_p(logits), _p(message), _p(gl), _p(gb), _p(d), message.shape[0], R, T, NO, st)
+            d += g_logits
+            lib.wm_headN_bwd(_p(d), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), R, T, NO, 0, st)
+        dmid, grads2, fout = _resblock_bwd_fused(s2_, True, dout, fold=(s1_[3], s1_[2]))
+        dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout)
+        return (dx, None) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (dhw, dhb)
 
 
 # ------------------------------------------------------------------------------------------ LSTM

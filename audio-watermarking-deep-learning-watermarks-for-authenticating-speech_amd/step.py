@@ -24,8 +24,7 @@ def forward_losses(generator, detector, s, message, codec=None):
     s_w = s + delta                                                    # :248
     if codec is not None:
         s_w = codec(s_w)                                               # main15c: perceptual_postprocess(s + delta)
-    logits = detector(torch.cat([s_w, s], dim=0), input_grad_rows=s.shape[0])                    # :249-250
-    loc, bce = L.detection_losses(logits, message)                     # :252-264
+    logits, loc, bce = L.detect_with_losses(detector, torch.cat([s_w, s], dim=0), message, input_grad_rows=s.shape[0])   # :249-264
     l1 = L.l1_to_zero(delta)                                           # :266
     mel = _mel(s, s_w)                                                 # :267
     loud = _loud(s, s_w)                                               # :268

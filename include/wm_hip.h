@@ -183,6 +183,27 @@ int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, floa
 int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, wm_stream_t stream);
 int wm_headN_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int NO, int accumulate, wm_stream_t stream);
+/* The heads with the ResBlock tail in front of them (the last block of each net, py/main16.py:145-146, :179-180): the kernel forms
+ * out = relu(x + y2*scale + shift) itself -- wm_bn_add_relu's expression, so `out` is bit-identical -- stores it once (it is the saved
+ * input of the head's backward and nothing else) and never reads it back; y / logits are bit-identical to wm_head1_fwd(out) /
+ * wm_headN_fwd(out).  mask (optional): the sign bits of `out` in wm_bn_add_relu_mask's layout, bits at t >= T zero; NULL = none
+ * (no gradient wanted).  x, y2, out: [R,64,T]; scale, shift: [64].  wm_head1_tail_fwd needs y2 and T % 4 == 0.
+ * wm_headN_tail_fwd: y2 == NULL = no tail (v = x, `out` and `mask` unused): the plain head, for what follows.
+ *   message != NULL ([B] int64, rows [0, B) of the R are the watermarked ones): also both BCE terms of wm_bce_fwd, summed from the
+ *   logits while they are in registers -- one fp32 sum pair per workgroup into partial (>= 2 * R * ceil(T / 256) floats), finished in
+ *   fp64 and a fixed order with wm_bce_fwd's scales (no atomics: bit-reproducible; against wm_bce_fwd on the same logits the two sums
+ *   differ by fp32 rounding, the grouping is another).  NO == 1 leaves bce_out untouched, as wm_bce_fwd does. */
+int wm_head1_tail_fwd(const float* x, const float* y2, const float* scale, const float* shift, const float* w, const float* bias,
+                      float* out, void* mask, float* y, int B, int T, wm_stream_t stream);
+int wm_headN_tail_fwd(const float* x, const float* y2, const float* scale, const float* shift, const float* w, const float* bias,
+                      const long long* message, int B, float* partial, float* loc_out, float* bce_out, float* out, void* mask,
+                      float* logits, int R, int T, int NO, wm_stream_t stream);
+/* wm_bce_bwd + wm_headN_bwd in one launch: in place of g it takes the logits [R,T,NO], message [B] and the device scalars g_loc,
+ * g_bce, and forms d(g_loc*loc + g_bce*bce)/d(logits) while it stages the logits -- wm_bce_bwd's expressions, so dx, dw, db are
+ * bit-identical to the pair -- and the [R,T,NO] gradient tensor is never written.  partial, accumulate: as wm_headN_bwd. */
+int wm_headN_bwd_bce(const float* logits, const long long* message, const float* g_loc, const float* g_bce, const float* x,
+                     const float* w, float* dx, float* partial, float* dw, float* db, int B, int R, int T, int NO, int accumulate,
+                     wm_stream_t stream);
 
 /* ---- nn.LSTM(64,64,batch_first=True) :138,:152-154 ---------------------------------------------------------- */
 int wm_lstm_xproj(const float* x, const float* w_ih, const float* b_ih, const float* b_hh, float* xp, int B, int T,
