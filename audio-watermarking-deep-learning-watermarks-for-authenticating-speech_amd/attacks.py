@@ -7,6 +7,8 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
 
   Distortion   per-clip gain and white Gaussian noise at a set SNR: one wm_distort call (ops.DistortFn), differentiable
   Lowpass      the biquad low-pass alone (no clamp, no 16-bit grid): ops.biquad, its backward the same launch with reverse=True
+  Resampled    down to another rate and back (8 kHz telephony, say), every row by itself: two wm_resample_rows launches
+               (ops.ResampleRowsFn), the backward of each the same launch with the transposed table
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
@@ -189,6 +191,36 @@ class Lowpass(torch.nn.Module):
 
     def extra_repr(self):
         return f"cutoff={self.cutoff}, sample_rate={self.sample_rate}"
+
+
+class Resampled(torch.nn.Module):
+    """y = up(down(x))[..., :T] along the last axis of (B, 1, T), (C, N) or (N,), every row by itself: down is sample_rate -> rate, up is
+    rate -> sample_rate, both the sinc resampler of ops.resample_table (torchaudio's default design) without mixdown.  The output has the
+    input's shape (ceil(sample_rate * ceil(rate * T / sample_rate) / rate) >= T: the cut is always possible); rate == sample_rate returns
+    x.  CUDA: two launches of wm_resample_rows, differentiable through the same two launches with the transposed tables
+    (ops.ResampleRowsFn); CPU: the same float32 tables through F.conv1d, differentiable by autograd."""
+
+    def __init__(self, rate, sample_rate=SAMPLE_RATE):
+        super().__init__()
+        ops.resample_table(sample_rate, rate)                                     # bad rates fail here
+        ops.resample_table(rate, sample_rate)
+        self.rate, self.sample_rate = int(rate), int(sample_rate)
+
+    def forward(self, x):
+        x = _time_rows(x, "x")
+        if self.rate == self.sample_rate:
+            return x
+        T = x.shape[-1]
+        rows = x.to(torch.float32).reshape(-1, T)
+        if x.is_cuda:
+            y = ops.ResampleRowsFn.apply(ops.ResampleRowsFn.apply(rows, self.sample_rate, self.rate), self.rate, self.sample_rate, T)
+        else:
+            from .inference import _resample_rows_host
+            y = _resample_rows_host(_resample_rows_host(rows, self.sample_rate, self.rate), self.rate, self.sample_rate, T)
+        return y.reshape(x.shape)
+
+    def extra_repr(self):
+        return f"rate={self.rate}, sample_rate={self.sample_rate}"
 
 
 @torch.no_grad()

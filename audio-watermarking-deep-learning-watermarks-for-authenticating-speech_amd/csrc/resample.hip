@@ -19,6 +19,10 @@
 //   up[m*Q + i] = the sum above with xmono = delta (0 outside [0, Nd));   out[c][o] = x[c][o] + up[o],
 // with the same two kernels around the same tap loops (filter_tile / filter_sample below), so `up` is wm_resample's result bit for bit.
 // Its tile kernel leaves the results in LDS and walks the rows of x / out (and up) through them: each is read / written once, coalesced.
+//
+// wm_resample_rows is the filter alone on a batch: x (rows, N) -> y (rows, L), every row by itself (no mixdown, no padding, any L), again the
+// same two kernels around the same tap loops, tiles numbered per row from period 0 of that row.  With the transposed table of
+// ops.resample_adjoint_table the same launch on (dy, rows, L -> N) is the resampler's adjoint: one tap loop, two tables.
 #include <type_traits>
 #include "wm_common.hpp"
 using namespace wm;
@@ -198,6 +202,57 @@ __global__ __launch_bounds__(kThreads) void resample_cache_kernel(const float* _
     }
 }
 
+// ---- wm_resample_rows: x (rows, N) -> y (rows, L), every row alone.  A tile is (row, tile in that row) and starts at period m0 = tile-in-row * M
+// of ITS row, so a sample sits where wm_resample of that row alone would put it; the last tile of a row stages and filters only the periods
+// the row still has (rounded up to kR).  Outside [0, N) of its own row a window reads zero by predicate: a neighbour's samples are never read.
+
+__global__ __launch_bounds__(kThreads) void resample_rows_tile_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                                      const int* __restrict__ first, float* __restrict__ y, long long N,
+                                                                      int P, int Q, int width, int W, long long L, int M,
+                                                                      long long row_tiles, long long tiles, int xvec, int yvec) {
+    extern __shared__ __align__(16) float smem[];
+    const Tile t = tile_of(smem, M, P, Q, width, W);
+    const float* ys = t.ys;
+    const int tid = threadIdx.x;
+    const long long periods = (L + Q - 1) / Q;
+    load_table(t, taps, first, P, Q, width, W, tid);
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long row = tile / row_tiles;
+        const long long m0 = (tile - row * row_tiles) * M;
+        const long long left = periods - m0;                            // > 0: row_tiles = ceil(periods / M)
+        const int Mt = left < M ? (int)((left + kR - 1) / kR) * kR : M;  // periods of this tile, a multiple of kR, <= M
+        const float* xr = x + row * N;
+        float* yr = y + row * L;
+        __syncthreads();                    // the previous tile's ys / xs are no longer read (first pass: nothing pending)
+        stage_window(t.xs, xr, 1, N, m0 * P - width, Mt * P + 2 * width, xvec, 1.0, tid);
+        __syncthreads();
+        filter_tile(t, Mt, P, Q, W, tid);
+        __syncthreads();
+        const long long o0 = m0 * Q;        // a multiple of 4
+        for (int q = tid; q < (Mt * Q) / 4; q += kThreads) {
+            const long long o = o0 + 4ll * q;
+            if (o >= L) break;
+            const f32x4 s = *reinterpret_cast<const f32x4*>(ys + 4 * q);
+            if (yvec && o + 4 <= L) {
+                *reinterpret_cast<f32x4*>(yr + o) = s;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (o + e < L) yr[o + e] = s[e];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void resample_rows_cache_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                                       const int* __restrict__ first, float* __restrict__ y, long long N,
+                                                                       int P, int Q, int width, int W, long long L, long long total) {
+    for (long long e = (long long)blockIdx.x * kThreads + threadIdx.x; e < total; e += (long long)gridDim.x * kThreads) {
+        const long long row = e / L;
+        const float* xr = x + row * N;
+        y[e] = filter_sample(taps, first, e - row * L, P, Q, width, W, [&](long long n) { return (n >= 0 && n < N) ? xr[n] : 0.f; });
+    }
+}
+
 // ---- wm_resample_add: the way back.  up = delta resampled to the recording's rate, out[c] = x[c] + up for every channel.
 // x and out carry no __restrict__: out may be x itself.  Every thread reads the elements of x it is going to write before it writes them and
 // no other thread touches them, which is all that in-place operation needs.
@@ -308,6 +363,39 @@ int wm_resample(const float* x, const float* taps, const int* first, float* y, i
     const int yvec = ((uintptr_t)y % 16 == 0);
     hipLaunchKernelGGL(resample_tile_kernel, dim3(grid), dim3(kThreads), (size_t)p.lds, stream, x, taps, first, y, C, N, P, Q, width, W, L,
                        total, p.M, tiles, xvec, yvec, 1.0 / (double)C);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// x (rows, N) -> y (rows, L), both contiguous: y[r][m*Q + i] = sum_k taps[i][k] * x[r][m*P + first[i] + k - width], x[r][.] = 0 outside [0, N).
+// L is any number of outputs per row.  taps [Q][W], first [Q] (int32).
+int wm_resample_rows(const float* x, const float* taps, const int* first, float* y, long long rows, long long N, long long L, int P, int Q,
+                     int width, int W, hipStream_t stream) {
+    if (rows < 0 || N < 0 || L < 0 || P <= 0 || Q <= 0 || width < 0 || W <= 0 || W > 2 * width + P) return (int)hipErrorInvalidValue;
+    if ((long long)P + Q > (1ll << 30) || (long long)Q * W > (1ll << 30)) return (int)hipErrorInvalidValue;
+    if (rows > (1ll << 40) || N > (1ll << 40) || L > (1ll << 40) || (N > 0 && rows > (1ll << 60) / N) || (L > 0 && rows > (1ll << 60) / L))
+        return (int)hipErrorInvalidValue;    // rows * N and rows * L (and the tile count) stay 64-bit counts
+    if (rows == 0 || L == 0) return 0;
+    if ((!x && N > 0) || !taps || !first || !y) return (int)hipErrorInvalidValue;
+    const Plan p = make_plan(P, Q, width, W);
+    if (p.M == 0) {
+        const long long total = rows * L;
+        const long long blocks = (total + kThreads - 1) / kThreads;
+        const int grid = (int)(blocks < (1ll << 20) ? blocks : (1ll << 20));
+        hipLaunchKernelGGL(resample_rows_cache_kernel, dim3(grid), dim3(kThreads), 0, stream, x, taps, first, y, N, P, Q, width, W, L, total);
+        WM_CHECK_LAUNCH();
+        return 0;
+    }
+    const long long periods = (L + Q - 1) / Q;
+    const long long row_tiles = (periods + p.M - 1) / p.M;
+    const long long tiles = rows * row_tiles;
+    const long long cap = 8ll * kNumCU;
+    const int grid = (int)(tiles < cap ? tiles : cap);
+    // row r starts at x + r*N / y + r*L: on the 16-byte grid for every row only when the base is and the row length is a multiple of 4
+    const int xvec = ((uintptr_t)x % 16 == 0) && (rows == 1 || N % 4 == 0);
+    const int yvec = ((uintptr_t)y % 16 == 0) && (rows == 1 || L % 4 == 0);
+    hipLaunchKernelGGL(resample_rows_tile_kernel, dim3(grid), dim3(kThreads), (size_t)p.lds, stream, x, taps, first, y, N, P, Q, width, W, L,
+                       p.M, row_tiles, tiles, xvec, yvec);
     WM_CHECK_LAUNCH();
     return 0;
 }

@@ -27,13 +27,29 @@ def _as_channels(waveform):
     return x.to(torch.float32)
 
 
-def resample(waveform, orig_freq, new_freq):
+def _resample_rows_host(x, orig_freq, new_freq, length=None):
+    """CPU twin of ops.resample_rows: every row of the float32 (rows, N) tensor by itself through the float32 `dense` table as one strided
+    F.conv1d per row (a row's samples do not depend on its neighbours or on their number); the first `length` samples of each, all
+    ceil(new * N / orig) by default.  Plain torch operations: autograd differentiates it."""
+    from . import ops
+    tab = ops.resample_table(orig_freq, new_freq)
+    P, width = tab["P"], tab["width"]
+    n = ops.resample_length(x.shape[1], orig_freq, new_freq) if length is None else length
+    padded = F.pad(x, (width, width + P))
+    weight = tab["dense"][:, None, :]
+    # (1, Q, N // P + 1): [phase][period] per row
+    return torch.stack([F.conv1d(row[None, None], weight, stride=P).transpose(1, 2).reshape(-1)[:n] for row in padded]).contiguous()
+
+
+def resample(waveform, orig_freq, new_freq, mixdown=True):
     """torchaudio.functional.resample(waveform, orig_freq, new_freq) with its documented defaults (sinc_interp_hann,
     lowpass_filter_width=6, rolloff=0.99), restated from the published description (ops.resample_table), preceded by the mono
     mixdown every file-level entry point of the reference applies first (py/main16.py:717-720): a (C, N) or (N,) waveform
     becomes (1, ceil(new * N / orig)).  A CUDA tensor goes to the HIP kernel (ops.resample); a CPU tensor goes through the same
     float32 table as one strided F.conv1d -- the only CPU arithmetic here, it is what lets load_audio read a 48 kHz file on a
     machine without a GPU.  Equal rates return the waveform unchanged.
+    mixdown=False filters every channel by itself, as torchaudio.functional.resample does: (C, N) -> (C, L), (N,) -> (1, L)
+    (ops.resample_rows on CUDA, the same conv1d per channel on the CPU).
     PARITY WITH TORCHAUDIO UNPINNED: torchaudio is absent from this image; tests/test_resample_cpu.py pins it on the first
     machine that has it."""
     from . import ops
@@ -41,6 +57,8 @@ def resample(waveform, orig_freq, new_freq):
     if tab["K"] == 1:
         return waveform
     x = _as_channels(waveform)
+    if not mixdown:
+        return ops.resample_rows(x, orig_freq, new_freq) if x.is_cuda else _resample_rows_host(x, orig_freq, new_freq)
     if x.is_cuda:
         return ops.resample(x, orig_freq, new_freq)
     # channels added in float64, one rounding to float32 (as the kernel does): the mean's error is an ulp of the mean, also where channels cancel

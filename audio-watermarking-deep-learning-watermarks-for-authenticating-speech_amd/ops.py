@@ -1289,6 +1289,107 @@ def resample_add(x, delta, orig_freq, delta_freq=16000, out=None, want_up=True):
     return out, up
 
 
+def resample_adjoint_table(orig_freq, new_freq):
+    """Host table (cached) with which wm_resample_rows is the ADJOINT of the orig -> new resampler.  Write A for the (L, N) matrix of one
+    row, A[m*Q + i][m*P + j - width] = dense[i][j].  Shifting the input index by P shifts the output index by Q with the same coefficients,
+    so dx[n] = sum_o A[o][n] * dy[o] is itself a polyphase filter: P phases (n = m*P + p), stride Q through dy,
+        dx[m*P + p] = sum_s c[p][s] * dy[m*Q + s],   c[p][s] = dense[s mod Q][-(s div Q)*P + p + width]   (0 outside dense),
+    the float32 values of `dense` rearranged, nothing rounded again.  Returned in resample_table's layout with P' = Q, Q' = P:
+    taps' (P, W') and first' (P,) int32 with taps'[p][k] = c[p][first'[p] + k - width'], every c outside that run exactly 0.0.
+    width' is the smallest that keeps every run inside the K' = 2*width' + P' taps of a phase, so the kernels' clamp of first' to
+    [0, 2*width' + P' - W'] moves no phase (asserted); W' is made odd where K' allows, as resample_table does."""
+    orig_freq, new_freq = _rate(orig_freq, "orig_freq"), _rate(new_freq, "new_freq")
+    key = (orig_freq, new_freq, "adjoint")
+    if key in _RESAMPLE_HOST:
+        return _RESAMPLE_HOST[key]
+    tab = resample_table(orig_freq, new_freq)
+    if tab["K"] == 1:                # equal rates: the identity is its own adjoint
+        _RESAMPLE_HOST[key] = tab
+        return tab
+    P, Q, width, K, dense = tab["P"], tab["Q"], tab["width"], tab["K"], tab["dense"]
+    # column j of dense belongs to the adjoint phase p = (j - width) mod P at the period offset d = (j - width - p) / P; its row i is s = i - d*Q
+    nz = dense != 0
+    rows = torch.arange(Q)[:, None]
+    j = torch.arange(K)
+    p_of = (j - width) % P
+    d_of = (j - width - p_of) // P
+    far = 1 << 40                                                             # beyond every s: a column without a non-zero tap never wins
+    col_lo = torch.where(nz, rows, far).min(dim=0).values - d_of * Q          # (K,): lowest / highest s with a non-zero tap, per column
+    col_hi = torch.where(nz, rows, -far).max(dim=0).values - d_of * Q
+    lo = torch.full((P,), far, dtype=torch.int64).scatter_reduce(0, p_of, col_lo, "amin")
+    hi = torch.full((P,), -far, dtype=torch.int64).scatter_reduce(0, p_of, col_hi, "amax")
+    assert bool((lo <= hi).all()), "an input phase no output reads"
+    Pa, Qa = Q, P
+    wa = max(int(-lo.min()), int(hi.max()) - Pa + 1, 0)
+    Ka = 2 * wa + Pa
+    W = int((hi - lo + 1).max())
+    if W % 2 == 0 and W < Ka:
+        W += 1
+    first = torch.minimum(lo + wa, torch.tensor(Ka - W))
+    assert W <= Ka and int(first.min()) >= 0 and int(first.max()) <= 2 * wa + Pa - W, "the kernel would clamp a phase of the adjoint table"
+    s = first[:, None] + torch.arange(W)[None, :] - wa                        # (P, W)
+    i = s % Q
+    jj = -((s - i) // Q) * P + torch.arange(P)[:, None] + width
+    inside = (jj >= 0) & (jj < K)
+    taps = torch.where(inside, dense[i, jj.clamp(0, K - 1)], torch.zeros(())).contiguous()
+    assert int((taps != 0).sum()) == int(nz.sum()), "the adjoint table lost a tap"
+    out = {"P": Pa, "Q": Qa, "width": wa, "K": Ka, "W": W, "taps": taps, "first": first.to(torch.int32)}
+    _RESAMPLE_HOST[key] = out
+    return out
+
+
+def _resample_rows_launch(x, tab, dkey, L):
+    rows, N = x.shape
+    if dkey not in _RESAMPLE_DEV:
+        _RESAMPLE_DEV[dkey] = (tab["taps"].to(x.device), tab["first"].to(x.device))
+    taps, first = _RESAMPLE_DEV[dkey]
+    y = _f32(rows, L, device=x.device)
+    lib.wm_resample_rows(_p(x), _p(taps), _p(first), _p(y), rows, N, L, tab["P"], tab["Q"], tab["width"], tab["W"], _stream())
+    return y
+
+
+def _rows_length(N, orig_freq, new_freq, length):
+    full = resample_length(N, orig_freq, new_freq)
+    if length is None:
+        return full
+    if isinstance(length, bool) or not isinstance(length, int) or not 0 <= length <= full:
+        raise ValueError(f"length: expected an int in [0, {full}] (what {N} samples give), got {length!r}")
+    return length
+
+
+def resample_rows(x, orig_freq, new_freq, length=None):
+    """Sinc resampling of every row of a CUDA fp32 (rows, N) tensor by itself, one launch of wm_resample_rows: (rows, L) with
+    L = resample_length(N, orig, new), or its first `length` samples.  No mixdown: row r is ops.resample(x[r:r+1], orig, new)[0] bit for
+    bit.  Equal rates return x (x[:, :length] when cut)."""
+    tab = resample_table(orig_freq, new_freq)
+    x = _chk(x, "x", 2)
+    L = _rows_length(x.shape[1], orig_freq, new_freq, length)
+    if tab["K"] == 1:
+        return x if L == x.shape[1] else x[:, :L]
+    return _resample_rows_launch(x, tab, (int(orig_freq), int(new_freq), x.device), L)
+
+
+class ResampleRowsFn(torch.autograd.Function):
+    """y = A x per row (resample_rows); dx = A^T dy, the same launch with resample_adjoint_table on (dy, rows, L -> N).  Nothing is saved
+    but the rates and the lengths."""
+
+    @staticmethod
+    def forward(ctx, x, orig_freq, new_freq, length=None):
+        ctx.rates, ctx.n = (int(orig_freq), int(new_freq)), x.shape[1]
+        return resample_rows(x, orig_freq, new_freq, length)
+
+    @staticmethod
+    def backward(ctx, dy):
+        orig, new = ctx.rates
+        dy = _chk(dy, "dy", 2)
+        tab = resample_adjoint_table(orig, new)
+        if tab["K"] == 1:
+            dx = torch.nn.functional.pad(dy, (0, ctx.n - dy.shape[1]))
+        else:
+            dx = _resample_rows_launch(dy, tab, (orig, new, dy.device, "adjoint"), ctx.n)
+        return dx, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- biquad + 16-bit PCM codec
 # The reference's 16-bit save path (py/main15.py:850-867: 7 kHz biquad low-pass -> clamp -> x32767 -> int16) and main15c's
 # perceptual_postprocess (round(lowpass_biquad(x, 16000, 7000) * 32767) / 32767 on s_w inside the train / validation step) as one

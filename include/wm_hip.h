@@ -368,6 +368,21 @@ int wm_resample(const float* x, const float* taps, const int* first, float* y, i
 int wm_resample_add(const float* d, const float* taps, const int* first, const float* x, float* out, float* up, int C, long long N,
                     long long Nd, int P, int Q, int width, int W, wm_stream_t stream);
 
+/* The filter alone on a batch, every row by itself: the resampling attack of the training graph and its backward, no mixdown, no padding.
+ *     y[r][m*Q + i] = sum_{k<W} taps[i][k] * x[r][m*P + first[i] + k - width]      0 <= r < rows,  0 <= m*Q + i < L
+ *   x (rows, N), y (rows, L), both contiguous; rows * N and rows * L are 64-bit counts.  Outside [0, N) of ITS OWN row a window reads zero BY
+ *   PREDICATE: a neighbouring row's samples are never read.  L is any number of outputs per row, not tied to ceil(Q*N/P): fewer cuts the
+ *   row short, samples whose window lies past N are sums of zeros.  taps [Q][W] / first [Q]: a compact table as for wm_resample.
+ * Row r is the single chain fmaf(taps[i][k], x, acc), k = 0..W-1, of wm_resample: it equals wm_resample of that row alone with C = 1 bit for bit,
+ * whatever tile, workgroup or kernel computed it (tiles are numbered per row from period 0 of that row; LDS kernel or one-thread-per-sample
+ * kernel as wm_resample_plan(P, Q, width, W) says).  16-byte accesses where every row start is on the 16-byte grid (base aligned and
+ * N % 4 == 0 for x, L % 4 == 0 for y, or rows == 1), 4-byte accesses otherwise.  No atomics: bit-reproducible.
+ * THE ADJOINT is the same launch: with the table of the pair transposed (ops.resample_adjoint_table: P' = Q, Q' = P, the same float32 values
+ * rearranged) on (dy, rows, L -> N) it computes dx[r][n] = sum_o A[o][n] * dy[r][o], A the (L, N) matrix of one row above.
+ * rows == 0 or L == 0 returns 0 without a launch. */
+int wm_resample_rows(const float* x, const float* taps, const int* first, float* y, long long rows, long long N, long long L, int P, int Q,
+                     int width, int W, wm_stream_t stream);
+
 /* ---- 16-bit save path and main15c codec: biquad section + clamp + 16-bit quantiser in one launch -----------------------
  * replaces the host-only `lowpass_biquad(waveform, sample_rate, cutoff_freq=7000)` -> clamp(-1, 1) -> * 32767 -> .to(torch.int16) of the
  * reference's save_audio (py/main15.py:850-867), and `perceptual_postprocess(x) = round(lowpass_biquad(x, 16000, 7000) * 32767) / 32767`
