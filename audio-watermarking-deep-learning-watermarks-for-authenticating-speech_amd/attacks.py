@@ -1,14 +1,17 @@
 """Channel distortions between s + delta and the Detector, and the loop that tells how detection moves under them.
 
 The reference README's "Robustness Testing" section promises a watermark that survives compression, resampling, volume changes and
-additive noise; it ships no code for the last two.  Here they are modules on (B, 1, T), (C, N) or (N,) that go wherever codec.PcmCodec
-goes -- the `codec=` argument of forward_losses / train_step / eval_forward / evaluate_batches takes any of them, and chains are plain
+additive noise; it ships no code for the last two, and no codec to train against.  Here they are modules on (B, 1, T), (C, N) or (N,)
+that go wherever codec.PcmCodec goes -- the `codec=` argument of forward_losses / train_step / eval_forward / evaluate_batches takes any of them, and chains are plain
 torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already works as `codec=`:
 
   Distortion   per-clip gain and white Gaussian noise at a set SNR: one wm_distort call (ops.DistortFn), differentiable
   Lowpass      the biquad low-pass alone (no clamp, no 16-bit grid): ops.biquad, its backward the same launch with reverse=True
   Resampled    down to another rate and back (8 kHz telephony, say), every row by itself: two wm_resample_rows launches
                (ops.ResampleRowsFn), the backward of each the same launch with the transposed table
+  TransformCodec   a STAND-IN for lossy compression: lapped MDCT, per-band quantiser at a per-row SNR, bandwidth cut, synthesis -- one
+               wm_mdct_codec launch (ops.MdctCodecFn), its backward the same launch with the quantiser off.  The signal path MP3 / AAC
+               share, not an encoder: parity with a real one is unmeasured
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
@@ -221,6 +224,125 @@ class Resampled(torch.nn.Module):
 
     def extra_repr(self):
         return f"rate={self.rate}, sample_rate={self.sample_rate}"
+
+
+def row_snr_db(seed, draw, rows, snr_db):
+    """TransformCodec's per-row quality for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the counter
+    Distortion draws a row's parameters from -- the word Distortion leaves unused, so the two never share a number -- mapped onto the pair
+    snr_db as fmaf(high - low, u, low)"""
+    lo, hi = (np.float32(v) for v in snr_db)
+    o = philox4x32_10((_PARAM_Q & 0xFFFFFFFF, _PARAM_Q >> 32, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
+    return (np.float64(hi - lo) * _unit(o[3]) + np.float64(lo)).astype(np.float32)
+
+
+def code_entropy_kbps(codes, band, kcut, hop, sample_rate):
+    """An ESTIMATE of the bitrate the int16 codes (rows, F, hop) of a TransformCodec call would cost: per band index (the `band`
+    coefficients b * band .. below kcut) the first-order entropy H_b of the codes pooled over all rows and frames, band * H_b bits per frame,
+    plus 8 bits per band per frame for the step; sample_rate / hop frames per second.  kbit/s per row-second.  No entropy coder is run and
+    no real codec allocates bits this way: the figure relates snr_db to a bitrate, no more."""
+    if codes.dim() != 3 or codes.shape[2] != hop or codes.numel() == 0:
+        raise ValueError(f"codes: expected (rows, frames, {hop}) with at least one frame, got shape {tuple(codes.shape)}")
+    nb = kcut // band
+    sym = codes[:, :, :kcut].reshape(-1, nb, band).permute(1, 0, 2).reshape(nb, -1).to(torch.int64) + 32768     # (band index, pooled)
+    per = sym.shape[1]
+    keyed = (sym + 65536 * torch.arange(nb, device=sym.device).view(nb, 1)).reshape(-1)
+    vals, counts = torch.unique(keyed, return_counts=True)
+    p = counts.double() / per
+    H = torch.zeros(nb, dtype=torch.float64, device=sym.device).index_add_(0, vals // 65536, -p * torch.log2(p))
+    bits_per_frame = float((band * H + 8.0).sum())
+    return bits_per_frame * sample_rate / hop / 1000.0
+
+
+class TransformCodec(torch.nn.Module):
+    """A STAND-IN for lossy compression on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the signal path MP3 / AAC-like
+    codecs share -- lapped MDCT at hop `hop`, per band of `band` coefficients a uniform quantiser whose step sits snr_db below the band's
+    own level (noise shaped like the spectrum, weak coefficients fall into the dead zone; never finer than the 16-bit grid), an optional
+    cut of everything above bandwidth_hz, synthesis with overlap-add (wm_mdct_codec in include/wm_hip.h has the definition).  It is not an
+    MP3 or AAC encoder -- no psychoacoustic model, no bit reservoir, no entropy coder -- and PARITY WITH A REAL ENCODER IS UNMEASURED.
+    snr_db: a number fixes the quality, a pair draws one value per row, reproducible from (seed, draw, row0 + r) (row_snr_db); 0..60.
+    Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
+    pieces draws what the whole batch would.  `last_snr_db`: the per-row values of the last call (a CPU tensor).
+    grad "straight_through": the quantiser passes the gradient unchanged, the cut is kept | "dead_zone": coefficients coded 0 pass none
+    (ops.MdctCodecFn; the step's dependence on x is not differentiated).  CUDA tensors run the kernel, one launch each way; CPU tensors a
+    float32 numpy restatement of the definition (forward only)."""
+
+    def __init__(self, snr_db=(10, 30), bandwidth_hz=None, hop=256, band=8, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
+        super().__init__()
+        if grad not in ops.MDCT_GRAD_MODES:
+            raise ValueError(f"grad must be one of {ops.MDCT_GRAD_MODES}, got {grad!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed: expected an int, got {seed!r}")
+        self.snr_db = _pair(snr_db, "snr_db")
+        if not 0.0 <= self.snr_db[0] <= self.snr_db[1] <= 60.0:
+            raise ValueError(f"snr_db: expected values in [0, 60], got {snr_db!r}")
+        self.kcut = ops.mdct_kcut(hop, band, bandwidth_hz, sample_rate)           # bad hops, bands and bandwidths fail here
+        self.hop, self.band, self.bandwidth_hz, self.sample_rate = hop, band, bandwidth_hz, sample_rate
+        self.floor_step = ops.mdct_default_floor_step(hop)
+        self.seed, self.grad = seed, grad
+        self.last_snr_db = None
+        self.reset()
+
+    def reset(self, draw=0):
+        if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
+            raise ValueError(f"draw: expected an int in [0, 2^32), got {draw!r}")
+        self.draw = draw
+        return self
+
+    def _rows(self, x, row0):
+        x = _time_rows(x, "x")
+        rows = x.numel() // x.shape[-1]
+        if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 <= 2 ** 32 - rows:
+            raise ValueError(f"row0: expected an int with 0 <= row0 and row0 + rows <= 2^32, got {row0!r}")
+        return x, torch.from_numpy(row_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
+
+    def forward(self, x, row0=0):
+        x, snr = self._rows(x, row0)
+        self.draw = (self.draw + 1) % 2 ** 32
+        if x.is_cuda:
+            y = ops.MdctCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.hop, self.band, self.kcut, self.floor_step, self.grad)
+        else:
+            y = self._host(x.detach().to(torch.float32), snr)[0]
+        self.last_snr_db = snr
+        return y
+
+    def _host(self, x, snr):
+        """(y, int16 codes (rows, F, hop)) of a CPU tensor: the definition in float32 numpy, dense matrices"""
+        M, band, n, f32 = self.hop, self.band, x.shape[-1], np.float32
+        x2 = x.reshape(-1, n).numpy()
+        rows, F = x2.shape[0], ops.mdct_frames(n, M)
+        j, k = np.arange(2 * M, dtype=np.float64), np.arange(M, dtype=np.float64)
+        w = np.sin(np.pi * (j + 0.5) / (2 * M)).astype(f32)
+        C = np.cos(np.pi / M * np.outer(k + 0.5, j + 0.5 + M / 2)).astype(f32)
+        xp = np.zeros((rows, (F + 1) * M), dtype=f32)
+        xp[:, M:M + n] = x2
+        X = (np.stack([xp[:, f * M:(f + 2) * M] for f in range(F)], axis=1) * w) @ C.T
+        X[:, :, self.kcut:] = 0
+        P = (X.reshape(rows, F, M // band, band) ** 2).mean(axis=3, dtype=f32)
+        scale = (f32(10) ** (-snr.numpy() / f32(20))).astype(f32).reshape(rows, 1, 1)
+        step = np.repeat(np.maximum(np.sqrt(f32(12) * P) * scale, f32(self.floor_step)), band, axis=2)
+        q = np.rint(X / step)
+        yf = f32(2.0 / M) * w * ((q * step) @ C)
+        out = np.zeros_like(xp)
+        for f in range(F):
+            out[:, f * M:(f + 2) * M] += yf[:, f]
+        return torch.from_numpy(np.ascontiguousarray(out[:, M:M + n])).reshape(x.shape), torch.from_numpy(q.astype(np.int16))
+
+    @torch.no_grad()
+    def estimate_kbps(self, x, row0=0):
+        """An ESTIMATE of the bitrate this setting costs on x, in kbit/s per row-second: code_entropy_kbps of the codes the current draw
+        gives (the draw is not advanced).  First-order entropy per band index plus 8 bits per band per frame for the step; no entropy
+        coder is run.  It relates snr_db to a bitrate and says nothing about what an MP3 / AAC encoder would spend."""
+        x, snr = self._rows(x, row0)
+        if x.is_cuda:
+            codes = ops.mdct_codec(x.detach().to(torch.float32), snr.to(x.device), hop=self.hop, band=self.band, kcut=self.kcut,
+                                   floor_step=self.floor_step, codes_out=True)[1]
+        else:
+            codes = self._host(x.detach().to(torch.float32), snr)[1]
+        return code_entropy_kbps(codes, self.band, self.kcut, self.hop, self.sample_rate)
+
+    def extra_repr(self):
+        return (f"snr_db={self.snr_db}, bandwidth_hz={self.bandwidth_hz}, hop={self.hop}, band={self.band}, "
+                f"sample_rate={self.sample_rate}, seed={self.seed}, grad={self.grad!r}")
 
 
 @torch.no_grad()

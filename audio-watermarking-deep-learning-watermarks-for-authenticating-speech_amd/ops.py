@@ -1578,3 +1578,125 @@ class DistortFn(torch.autograd.Function):
         lib.wm_distort_bwd(_p(g), _p(x), _p(stat), _p(dx), _p(DistortFn._scratch(*ctx.key[:2], x.device)), *ctx.key, int(ctx.through),
                            _stream())
         return dx, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------- transform-codec stand-in
+# Lapped MDCT -> per-band quantiser -> bandwidth cut -> synthesis (wm_mdct_codec, csrc/mdct_codec.hip): the signal path lossy codecs share,
+# as a step of the graph.  A stand-in for compression, not an MP3 / AAC encoder: parity with a real encoder is unmeasured.
+MDCT_HOPS = (128, 256, 512)
+MDCT_BANDS = (4, 8, 16, 32)
+MDCT_GRAD_MODES = ("straight_through", "dead_zone")
+
+
+def mdct_default_floor_step(hop):
+    """2^-15 * sqrt(hop / 2): the coefficient step whose time-domain noise equals the 16-bit grid's (synthesis scales coefficient variance
+    by 2 / hop)"""
+    import math
+    return 2.0 ** -15 * math.sqrt(hop / 2.0)
+
+
+def mdct_frames(n, hop):
+    """F = ceil(n / hop) + 1: the frames of a row of n samples"""
+    return -(-int(n) // int(hop)) + 1
+
+
+def mdct_plan(n, hop):
+    """(frames a workgroup transforms, workgroups per row) wm_mdct_codec runs a row of n samples with: a function of (n, hop) alone"""
+    import ctypes
+    frames, wgs = ctypes.c_int(0), ctypes.c_longlong(0)
+    lib.wm_mdct_codec_plan(int(n), int(hop), ctypes.addressof(frames), ctypes.addressof(wgs), None)
+    return frames.value, wgs.value
+
+
+def mdct_kcut(hop, band, bandwidth_hz=None, sample_rate=16000):
+    """The first coefficient the bandwidth cut zeroes: floor(bandwidth_hz * 2 hop / sample_rate) rounded down to a multiple of `band`
+    (coefficient k sits at (k + 1/2) sample_rate / (2 hop) Hz); None: hop, no cut.  A cut below one band, or above Nyquist, is refused."""
+    import math
+    if hop not in MDCT_HOPS:
+        raise ValueError(f"hop must be one of {MDCT_HOPS}, got {hop!r}")
+    if band not in MDCT_BANDS:
+        raise ValueError(f"band must be one of {MDCT_BANDS}, got {band!r}")
+    if bandwidth_hz is None:
+        return hop
+    for v, name in ((bandwidth_hz, "bandwidth_hz"), (sample_rate, "sample_rate")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+    if 2.0 * bandwidth_hz > sample_rate:
+        raise ValueError(f"bandwidth_hz must not lie above half the sample rate, got {bandwidth_hz} Hz at {sample_rate} Hz")
+    kcut = int(math.floor(bandwidth_hz * 2 * hop / sample_rate)) // band * band
+    if kcut < band:
+        raise ValueError(f"bandwidth_hz {bandwidth_hz} Hz keeps less than one band of {band} coefficients at hop {hop}")
+    return kcut
+
+
+def mdct_codec(x, snr_db, *, hop=256, band=8, kcut=None, bandwidth_hz=None, sample_rate=16000, floor_step=None, quantise=True,
+               codes_out=False, mask_in=None):
+    """One launch of wm_mdct_codec along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows): MDCT analysis at hop
+    `hop`, coefficients k >= kcut (given, or mdct_kcut(hop, band, bandwidth_hz, sample_rate); neither: hop, no cut) and those where mask_in
+    holds 0 set to zero, the per-band quantiser at the per-row SNR snr_db
+    (a (rows,) fp32 CUDA tensor, values in [0, 60]; ignored with quantise=False, where None is allowed) with floor_step (None:
+    mdct_default_floor_step(hop)), synthesis with overlap-add.  codes_out: also returns the int16 codes, (rows, mdct_frames(n, hop), hop),
+    as (y, codes).  mask_in: an int16 tensor of that shape.  A stand-in for lossy compression; parity with MP3 / AAC is unmeasured."""
+    import math
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    if kcut is not None and bandwidth_hz is not None:
+        raise ValueError("give kcut or bandwidth_hz, not both")
+    derived = mdct_kcut(hop, band, bandwidth_hz, sample_rate)                    # hop and band from their sets
+    if kcut is None:
+        kcut = derived
+    if isinstance(kcut, bool) or not isinstance(kcut, int) or kcut % band or not band <= kcut <= hop:
+        raise ValueError(f"kcut: expected a multiple of band = {band} in [{band}, {hop}], got {kcut!r}")
+    if floor_step is None:
+        floor_step = mdct_default_floor_step(hop)
+    if isinstance(floor_step, bool) or not isinstance(floor_step, (int, float)) or not math.isfinite(floor_step) or floor_step <= 0:
+        raise ValueError(f"floor_step must be a positive finite number, got {floor_step!r}")
+    if codes_out and not quantise:
+        raise ValueError("codes_out needs quantise=True: the linear map has no codes")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    F = mdct_frames(n, hop)
+    if snr_db is None and not quantise:
+        snr_db = torch.zeros(rows, dtype=torch.float32, device=x.device)
+    snr_db = _chk(snr_db, "snr_db", 1)
+    if snr_db.shape[0] != rows or snr_db.device != x.device:
+        raise ValueError(f"snr_db: expected {rows} values on {x.device}, got shape {tuple(snr_db.shape)} on {snr_db.device}")
+    if mask_in is not None:
+        mask_in = _chk(mask_in, "mask_in", None, torch.int16)
+        if mask_in.numel() != rows * F * hop or mask_in.device != x.device:
+            raise ValueError(f"mask_in: expected {rows} x {F} x {hop} int16 values on {x.device}, got shape {tuple(mask_in.shape)}")
+    y = torch.empty_like(x)
+    codes = torch.empty(rows, F, hop, dtype=torch.int16, device=x.device) if codes_out else None
+    lib.wm_mdct_codec(_p(x), _p(y), _p(codes), _p(mask_in), _p(snr_db), rows, n, hop, band, kcut, float(floor_step), int(bool(quantise)),
+                      _stream())
+    return (y, codes) if codes_out else y
+
+
+class MdctCodecFn(torch.autograd.Function):
+    """y = synthesis(Q(cut(analysis(x)))) per row (mdct_codec) on the tape.  With the quantiser off the map A = synthesis . cut . analysis is
+    symmetric, so the backward is the same launch with quantise=False on dy:
+      grad "straight_through": dx = A dy -- the quantiser is taken for the identity, the bandwidth cut is kept, nothing is saved;
+      grad "dead_zone":        dx = A_mask dy -- coefficients whose forward code was 0 pass no gradient; the forward's int16 codes are saved
+                               and handed to the backward launch as mask_in.
+    The step follows the band's own energy and so depends on x; that dependence is NOT differentiated (the step is a constant of the
+    backward pass, as the rounding is)."""
+
+    @staticmethod
+    def forward(ctx, x, snr_db, hop, band, kcut, floor_step, grad):
+        if grad not in MDCT_GRAD_MODES:
+            raise ValueError(f"grad must be one of {MDCT_GRAD_MODES}, got {grad!r}")
+        ctx.cfg = (hop, band, kcut, floor_step)
+        ctx.dead = grad == "dead_zone" and ctx.needs_input_grad[0]
+        if ctx.dead:
+            y, codes = mdct_codec(x, snr_db, hop=hop, band=band, kcut=kcut, floor_step=floor_step, codes_out=True)
+            ctx.save_for_backward(codes)
+            return y
+        return mdct_codec(x, snr_db, hop=hop, band=band, kcut=kcut, floor_step=floor_step)
+
+    @staticmethod
+    def backward(ctx, g):
+        hop, band, kcut, floor_step = ctx.cfg
+        mask = ctx.saved_tensors[0] if ctx.dead else None
+        dx = mdct_codec(g.contiguous(), None, hop=hop, band=band, kcut=kcut, floor_step=floor_step, quantise=False, mask_in=mask)
+        return dx, None, None, None, None, None, None

@@ -444,6 +444,36 @@ int wm_distort(const float* x, float* y, float* stat, float* scratch, long long 
 int wm_distort_bwd(const float* dy, const float* x, const float* stat, float* dx, float* scratch, long long rows, long long n,
                    long long row0, long long seed, long long draw, int through, wm_stream_t stream);
 
+/* ---- transform-codec stand-in: lapped MDCT, per-band quantiser, bandwidth cut, synthesis -- forward and adjoint in one entry point ----
+ * the "compression" of the reference README's "Robustness Testing" section as a step of the graph (the reference ships no code for it).
+ * It is the signal path lossy codecs share, NOT an MP3 or AAC encoder: parity with a real encoder is unmeasured.
+ * x (rows, n) fp32, rows >= 1, 1 <= n <= 2^34, every row on its own:
+ *   Frames.    hop M in {128, 256, 512}; window w[j] = sin(pi (j + 1/2) / (2M)), j < 2M; the row is extended by zeros; F = ceil(n / M) + 1 frames,
+ *              frame f holds samples (f-1)M .. (f+1)M - 1, zero outside [0, n).
+ *   Analysis.  X_f[k] = sum_j w[j] x_f[j] cos(pi/M (j + 1/2 + M/2)(k + 1/2)), k < M; coefficients k >= kcut are set to 0 (kcut a multiple of band,
+ *              band <= kcut <= M); where mask_in (optional, (rows, F, M) int16) holds 0 the coefficient is set to 0 as well.
+ *   Quantiser  (quantise != 0).  Bands are `band` consecutive coefficients, band in {4, 8, 16, 32}; in frame f, band b:
+ *              P = mean of X^2 over the band (one fmaf chain in rising k, divided by band)
+ *              step = max(sqrt(12 P) * 10^(-snr_db_r / 20), floor_step)        q = rint(X / step), ties to even        Xq = q * step
+ *              snr_db (rows,) fp32 on the device, 0 <= snr_db_r <= 60 (values outside are clamped to that range, NaN to 0); floor_step > 0.
+ *              |q| <= sqrt(band / 12) * 10^3 < 32767: codes_out (optional, (rows, F, M) int16) receives q (0 for k >= kcut).
+ *              quantise == 0: Xq = X, the linear map A = synthesis . cut/mask . analysis alone (snr_db is not read; codes_out must be null).
+ *   Synthesis. y_f[j] = (2/M) w[j] sum_k Xq_f[k] cos(same argument), overlap-added; y[t] is returned for t < n.
+ * With the quantiser off and kcut = M this is the identity (Princen-Bradley), and A is symmetric with or without cut and mask: the backward
+ * pass of y = A x is the same launch on dy.  "straight-through" gradient: dx = A dy; "dead zone": dx = A_mask dy with the forward's codes as
+ * mask_in (coefficients coded 0 pass nothing).  The step's own dependence on x is not differentiated.
+ * One launch; the spectrum stays in LDS (csrc/mdct_codec.hip: fold to DCT-IV, fp32 MFMA).  A workgroup transforms W = 32 or 64 consecutive
+ * frames of one row and owns the W - 1 hops between them; the frame two workgroups share is computed by both, each coefficient in one fixed
+ * order that knows neither the frame's column nor W.  wm_mdct_codec_plan (host-only, both outputs are HOST pointers, stream unused): W and
+ * the workgroups per row for (n, M) -- the W with the fewest padded frames, 32 at M = 512.
+ * No atomics, no scratch: a sample's bits depend on its row's data and the scalars only -- never on the grid or on the other rows of the launch.
+ * x, y, snr_db may start at any multiple of 4 bytes, the int16 arrays of 2.  IN PLACE IS REFUSED.
+ * hipErrorInvalidValue before any launch: rows or n < 1, n > 2^34, M / band / kcut outside the sets above, a non-finite or non-positive
+ * floor_step, a null x, y or snr_db, a misaligned pointer, codes_out without quantise, overlapping input and output. */
+int wm_mdct_codec_plan(long long n, int M, int* frames_per_workgroup, long long* workgroups_per_row, wm_stream_t stream);
+int wm_mdct_codec(const float* x, float* y, void* codes_out, const void* mask_in, const float* snr_db, long long rows, long long n, int M,
+                  int band, int kcut, float floor_step, int quantise, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
