@@ -12,10 +12,18 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
   TransformCodec   a STAND-IN for lossy compression: lapped MDCT, per-band quantiser at a per-row SNR, bandwidth cut, synthesis -- one
                wm_mdct_codec launch (ops.MdctCodecFn), its backward the same launch with the quantiser off.  The signal path MP3 / AAC
                share, not an encoder: parity with a real one is unmeasured
+  Convolved    a long convolutive channel: every row convolved with a given impulse response, or with one drawn per row from a bank of
+               measured ones -- one wm_fir_rows launch (ops.FirRowsFn), its backward the same launch with reverse=True.  echo_ir
+               makes the two-tap response of a plain echo
+  Reverb       the same launch with SYNTHETIC room responses drawn on the device per row (wm_rir_synth) at a per-row RT60 and
+               direct-to-reverberant ratio: exponentially decaying Gaussian noise, not a room simulation -- survival in real rooms
+               is unmeasured
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
-and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws."""
+and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws.  The counters (word 0, word 1, row, draw)
+of the four families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
+parameters (~0 - 1, ~0), the taps of a synthetic response (k >> 2, ~0 - 1)."""
 from __future__ import annotations
 
 import math
@@ -23,6 +31,7 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import ops
 from .codec import SAMPLE_RATE, _time_rows
@@ -31,6 +40,8 @@ from .losses import postprocess
 NOISE_GRAD_MODES = ("through", "detached")
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _PARAM_Q = 0xFFFFFFFFFFFFFFFF        # the counter words (q low, q high) of a row's parameters: no sample has them (n <= 2^34)
+_PARAM2_Q = 0xFFFFFFFFFFFFFFFE       # the same for Reverb's and Convolved's parameters
+_RIR_HIGH = 0xFFFFFFFE               # the second counter word of a synthetic response's taps (the first is k >> 2 < 2^12)
 
 
 def philox4x32_10(counter, key):
@@ -62,9 +73,14 @@ def _key(seed):
 def normal_noise(seed, draw, row, n):
     """z(seed, draw, row, t) for t < n as a float64 array: counter (q low, q high, row, draw) with q = t >> 2, key (seed low, seed high);
     words (o0, o1) give sqrt(-2 ln u(o0)) * (cos, sin)(2 pi u(o1)) for samples 4q and 4q+1, (o2, o3) the same for 4q+2 and 4q+3."""
+    return _normals(seed, draw, row, n, None)
+
+
+def _normals(seed, draw, row, n, high):
+    """normal_noise with the second counter word replaced by `high` (None: q's own high word)"""
     n = int(n)
     q = np.arange((n + 3) // 4, dtype=np.uint64)
-    o = philox4x32_10((q, q >> np.uint64(32), int(row), int(draw)), _key(seed))
+    o = philox4x32_10((q, q >> np.uint64(32) if high is None else high, int(row), int(draw)), _key(seed))
     z = np.empty((len(q), 4), dtype=np.float64)
     for p in (0, 1):
         rad, th = np.sqrt(-2.0 * np.log(_unit(o[2 * p]))), 2.0 * math.pi * _unit(o[2 * p + 1])
@@ -343,6 +359,193 @@ class TransformCodec(torch.nn.Module):
     def extra_repr(self):
         return (f"snr_db={self.snr_db}, bandwidth_hz={self.bandwidth_hz}, hop={self.hop}, band={self.band}, "
                 f"sample_rate={self.sample_rate}, seed={self.seed}, grad={self.grad!r}")
+
+
+def _param2_words(seed, draw, rows):
+    return philox4x32_10((_PARAM2_Q & 0xFFFFFFFF, _PARAM2_Q >> 32, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
+
+
+def row_reverb_params(seed, draw, rows, rt60, drr_db):
+    """Reverb's (rt60, drr_db) of rows `rows` (an int array of row0 + r), two float32 arrays: words o0 and o1 of the counter
+    (0xFFFFFFFE, 0xFFFFFFFF, row, draw) -- next to Distortion's parameter counter, met by nothing else -- mapped onto the pairs as
+    fmaf(high - low, u, low) in float32"""
+    o = _param2_words(seed, draw, rows)
+
+    def affine(pair, u):
+        lo, hi = (np.float32(v) for v in pair)
+        return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
+    return affine(rt60, _unit(o[0])), affine(drr_db, _unit(o[1]))
+
+
+def row_bank_index(seed, draw, rows, entries):
+    """Convolved's choice among `entries` responses for rows `rows`: floor(u(o2) * entries) of the same counter, an int64 array"""
+    return np.floor(_unit(_param2_words(seed, draw, rows)[2]) * int(entries)).astype(np.int64)
+
+
+def rir_taps(seed, draw, row, rt60, drr_db, K, sample_rate):
+    """The synthetic response wm_rir_synth gives row `row` (= row0 + r), restated in float64: e[0] = 0, e[k] = z_k exp(-k c) with
+    c = 3 ln 10 / (rt60 * sample_rate) and z_k the normal of "sample" k of the counter (k >> 2, 0xFFFFFFFE, row, draw);
+    h[0] = 1 / sqrt(1 + w), h[k] = sqrt(w / sum e^2) e[k] / sqrt(1 + w), w = 10^(-drr_db / 10).  rt60 and drr_db enter as float32 values,
+    drr_db clamped to [-100, 100]; K = 1, sum e^2 = 0, rt60 not > 0 or a non-finite drr_db give {1, 0, ...}."""
+    K = int(K)
+    rt60, drr_db = float(np.float32(rt60)), float(np.float32(drr_db))
+    h = np.zeros(K, dtype=np.float64)
+    h[0] = 1.0
+    if K == 1 or not rt60 > 0.0 or not math.isfinite(drr_db):
+        return h
+    c = 3.0 * math.log(10.0) / (rt60 * float(np.float32(sample_rate)))
+    e = _normals(seed, draw, row, K, _RIR_HIGH) * np.exp(-np.arange(K, dtype=np.float64) * c)
+    e[0] = 0.0
+    E = float(np.sum(e * e))
+    if not E > 0.0:
+        return h
+    w = 10.0 ** (-min(max(drr_db, -100.0), 100.0) / 10.0)
+    h = math.sqrt(w / E) * e / math.sqrt(1.0 + w)
+    h[0] = 1.0 / math.sqrt(1.0 + w)
+    return h
+
+
+def echo_ir(delay_s, gain_db, sample_rate=SAMPLE_RATE):
+    """The response of one echo `delay_s` seconds behind the direct sound and gain_db against it, at unit energy:
+    {1, 0, ..., 0, g} / sqrt(1 + g^2) with g = 10^(gain_db / 20) at tap round(delay_s * sample_rate).  A float32 tensor for Convolved."""
+    for v, name in ((delay_s, "delay_s"), (gain_db, "gain_db"), (sample_rate, "sample_rate")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if sample_rate <= 0:
+        raise ValueError(f"sample_rate must be positive, got {sample_rate!r}")
+    d = int(round(delay_s * sample_rate))
+    if not 1 <= d < ops.FIR_MAX_TAPS:
+        raise ValueError(f"delay_s: the echo must fall on a tap in [1, {ops.FIR_MAX_TAPS - 1}], got tap {d} ({delay_s!r} s at {sample_rate} Hz)")
+    g = 10.0 ** (gain_db / 20.0)
+    h = torch.zeros(d + 1, dtype=torch.float64)
+    h[0], h[d] = 1.0 / math.sqrt(1.0 + g * g), g / math.sqrt(1.0 + g * g)
+    return h.to(torch.float32)
+
+
+def _conv_rows_host(rows2d, h):
+    """H x per row of a (rows, n) float32 CPU tensor, h (K,) or (rows, K): F.conv1d with one group per row, which autograd differentiates"""
+    rows, K = rows2d.shape[0], h.shape[-1]
+    w = (h.expand(rows, K) if h.dim() == 1 else h).flip(-1).reshape(rows, 1, K)
+    return F.conv1d(F.pad(rows2d.unsqueeze(0), (K - 1, 0)), w, groups=rows)[0]
+
+
+def _check_seed_draw(seed=0, draw=0):
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"seed: expected an int, got {seed!r}")
+    if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
+        raise ValueError(f"draw: expected an int in [0, 2^32), got {draw!r}")
+
+
+def _rows_of(x, row0):
+    x = _time_rows(x, "x")
+    rows = x.numel() // x.shape[-1]
+    if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 <= 2 ** 32 - rows:
+        raise ValueError(f"row0: expected an int with 0 <= row0 and row0 + rows <= 2^32, got {row0!r}")
+    return x, rows
+
+
+class Convolved(torch.nn.Module):
+    """y = h * x, causal and cut to the input's length, for every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): lag 0 stays at
+    lag 0, so per-sample labels stay aligned.  h: a (K,) impulse response for all rows, or an (R, K) bank of (measured) responses, of which
+    row r takes entry floor(u * R), u drawn from (seed, draw, row0 + r) (row_bank_index); K <= 16384.  normalize: every response is
+    scaled to unit energy first (a response of zero energy is refused).  Every forward uses the next `draw`; reset(draw) rewinds; `row0`
+    (forward's argument) numbers the first row, so that a batch cut into pieces draws what the whole batch would.  `last_index`: the bank
+    entries of the last call (a CPU tensor; None without a bank).  h is a constant: no gradient flows to it.
+    CUDA tensors run wm_fir_rows, one launch each way (ops.FirRowsFn); CPU tensors F.conv1d in float32, differentiable by autograd."""
+
+    def __init__(self, h, normalize=False, seed=0):
+        super().__init__()
+        if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2) or h.numel() == 0 or not 1 <= h.shape[-1] <= ops.FIR_MAX_TAPS:
+            raise ValueError(f"h: expected a (K,) or (R, K) tensor with 1 <= K <= {ops.FIR_MAX_TAPS}, got "
+                             f"{tuple(h.shape) if isinstance(h, torch.Tensor) else type(h).__name__}")
+        if not isinstance(normalize, bool):
+            raise ValueError(f"normalize: expected a bool, got {normalize!r}")
+        _check_seed_draw(seed)
+        h = h.detach().to(torch.float64)
+        if not bool(torch.isfinite(h).all()):
+            raise ValueError("h: expected finite taps")
+        if normalize:
+            energy = h.pow(2).sum(dim=-1, keepdim=True)
+            if not bool((energy > 0).all()):
+                raise ValueError("h: a response of zero energy cannot be normalised")
+            h = h / energy.sqrt()
+        self.register_buffer("h", h.to(torch.float32).contiguous())
+        self.normalize, self.seed = normalize, seed
+        self.last_index = None
+        self.reset()
+
+    def reset(self, draw=0):
+        _check_seed_draw(draw=draw)
+        self.draw = draw
+        return self
+
+    def forward(self, x, row0=0):
+        x, rows = _rows_of(x, row0)
+        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        h = self.h if self.h.device == x.device else self.h.to(x.device)
+        self.last_index = None
+        if h.dim() == 2:
+            self.last_index = torch.from_numpy(row_bank_index(self.seed, draw, row0 + np.arange(rows), h.shape[0]))
+            h = h[self.last_index.to(x.device)]                                   # gathered on the device: per-row taps
+        x32 = x.to(torch.float32)
+        if x.is_cuda:
+            return ops.FirRowsFn.apply(x32.reshape(rows, -1), h).reshape(x.shape)
+        return _conv_rows_host(x32.reshape(rows, -1), h).reshape(x.shape)
+
+    def extra_repr(self):
+        return f"h={tuple(self.h.shape)}, normalize={self.normalize}, seed={self.seed}"
+
+
+class Reverb(torch.nn.Module):
+    """Synthetic reverberation on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the row convolved (causal, cut to the
+    input's length, lag 0 at lag 0) with a response of `taps` samples drawn for it -- a direct tap followed by Gaussian noise whose
+    amplitude falls 60 dB in rt60 seconds, at a direct-to-reverberant energy ratio of drr_db and unit total energy (wm_rir_synth in
+    include/wm_hip.h has the definition; rir_taps restates it).  It is NOT a room simulation -- no geometry, no early reflections, no
+    frequency-dependent decay -- and A WATERMARK'S SURVIVAL IN REAL ROOMS IS UNMEASURED; measured responses go through Convolved.
+    rt60, drr_db: a number fixes the value, a pair draws one per row, reproducible from (seed, draw, row0 + r) (row_reverb_params).
+    Every forward uses the next `draw` (fresh parameters and responses); reset(draw) rewinds; `row0` (forward's argument) numbers the
+    first row, so that a batch cut into pieces draws what the whole batch would.  `last_params`: the (rows, 2) {rt60, drr_db} of the last
+    call (a CPU tensor); `last_ir`: its (rows, taps) responses (on x's device).  The responses are constants of the graph.
+    CUDA tensors run wm_rir_synth and wm_fir_rows (ops.FirRowsFn, one launch each way); CPU tensors rir_taps and F.conv1d in float32,
+    differentiable by autograd."""
+
+    def __init__(self, rt60=(0.1, 0.4), drr_db=(0, 12), taps=2048, sample_rate=SAMPLE_RATE, seed=0):
+        super().__init__()
+        _check_seed_draw(seed)
+        self.rt60, self.drr_db = _pair(rt60, "rt60"), _pair(drr_db, "drr_db")
+        if not self.rt60[0] > 0.0:
+            raise ValueError(f"rt60: expected positive values, got {rt60!r}")
+        if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= ops.FIR_MAX_TAPS:
+            raise ValueError(f"taps: expected an int in [1, {ops.FIR_MAX_TAPS}], got {taps!r}")
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
+            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+        self.taps, self.sample_rate, self.seed = taps, sample_rate, seed
+        self.last_params = self.last_ir = None
+        self.reset()
+
+    def reset(self, draw=0):
+        _check_seed_draw(draw=draw)
+        self.draw = draw
+        return self
+
+    def forward(self, x, row0=0):
+        x, rows = _rows_of(x, row0)
+        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        rt60, drr = row_reverb_params(self.seed, draw, row0 + np.arange(rows), self.rt60, self.drr_db)
+        self.last_params = torch.from_numpy(np.stack([rt60, drr], axis=1))
+        x32 = x.to(torch.float32)
+        if x.is_cuda:
+            h = ops.rir_synth(self.last_params.to(x.device), self.taps, self.sample_rate, self.seed, draw, row0)
+            y = ops.FirRowsFn.apply(x32.reshape(rows, -1), h)
+        else:
+            h = torch.from_numpy(np.stack([rir_taps(self.seed, draw, row0 + r, rt60[r], drr[r], self.taps, self.sample_rate)
+                                           for r in range(rows)]).astype(np.float32))
+            y = _conv_rows_host(x32.reshape(rows, -1), h)
+        self.last_ir = h
+        return y.reshape(x.shape)
+
+    def extra_repr(self):
+        return f"rt60={self.rt60}, drr_db={self.drr_db}, taps={self.taps}, sample_rate={self.sample_rate}, seed={self.seed}"
 
 
 @torch.no_grad()

@@ -206,6 +206,52 @@ __global__ __launch_bounds__(kThreads) void distort_apply_kernel(const float* __
     }
 }
 
+// Synthetic room responses (wm_rir_synth): one workgroup per row.  Tap k takes the normal of "sample" k from the counter
+// (k >> 2, 0xFFFFFFFE, row0 + r, draw) -- normal_quad with q = 0xFFFFFFFE00000000 | (k >> 2), a high word no sample has -- times
+// exp(-k c), the exponent and its argument in fp64, the product in fp32.  E = sum e^2 in the order of the sums above: lane i takes the
+// quads i, i + 256, ... in rising order into four fmaf chains, (c0 + c1) + (c2 + c3), the wave butterfly, waves 0 + 1 + 2 + 3.  The
+// unscaled taps wait in h itself (a lane reads back only what it wrote); the scalars are formed in fp64 and rounded once.
+__global__ __launch_bounds__(kThreads) void rir_synth_kernel(const float* __restrict__ params, float* __restrict__ h, long long rows, int K,
+                                                             float sample_rate, Rng g) {
+    __shared__ float red[kThreads / kWave];
+    const int tid = threadIdx.x;
+    const long long qhi = (long long)0xFFFFFFFE00000000ull;
+    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+        const float rt60 = params[2 * r], drr = params[2 * r + 1];
+        float* __restrict__ hr = h + r * K;
+        const bool ok = rt60 > 0.f && __builtin_isfinite(drr);       // the same for the whole workgroup
+        const double c = ok ? 6.907755278982137 / ((double)rt60 * (double)sample_rate) : 0.0;      // 3 ln 10
+        float ch[4] = {0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+            for (int q = tid; 4 * q < K; q += kThreads) {
+                float z[4];
+                normal_quad(g, qhi | (long long)q, (unsigned)(g.row0 + r), z);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int k = 4 * q + e;
+                    if (k >= K) continue;
+                    const float ev = k ? z[e] * (float)exp(-(double)k * c) : 0.f;
+                    hr[k] = ev;
+                    ch[e] = fmaf(ev, ev, ch[e]);
+                }
+            }
+        }
+        const float E = block_sum<kThreads / kWave>((ch[0] + ch[1]) + (ch[2] + ch[3]), red);
+        const double w = ok ? exp10(-(double)fminf(fmaxf(drr, -100.f), 100.f) / 10.0) : 0.0;
+        const double s = 1.0 / sqrt(1.0 + w);
+        const float scale = (float)(sqrt(w / (double)E) * s);
+        const bool flat = !ok || !(E > 0.f) || !__builtin_isfinite(scale);        // K = 1, E = 0: the response is {1, 0, ...}
+        const float h0 = flat ? 1.f : (float)s;
+        for (int q = tid; 4 * q < K; q += kThreads) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = 4 * q + e;
+                if (k < K) hr[k] = k == 0 ? h0 : (flat ? 0.f : scale * hr[k]);
+            }
+        }
+    }
+}
+
 bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + nb && pb < pa + na;
@@ -278,6 +324,18 @@ int wm_distort_bwd(const float* dy, const float* x, const float* stat, float* dx
     const long long tiles_per_row = (n + 3 + kTile - 1) / kTile, tiles = rows * tiles_per_row;
     hipLaunchKernelGGL(distort_apply_kernel<1>, dim3(grid_for(tiles)), dim3(kThreads), 0, stream, dy, x, stat, coef, dx, n, tiles_per_row,
                        tiles, g);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+int wm_rir_synth(const float* params, float* h, long long rows, int K, float sample_rate, long long row0, long long seed, long long draw,
+                 hipStream_t stream) {
+    if (K < 1 || K > 16384 || !shape_ok(rows, K, row0, draw) || !params || !h) return (int)hipErrorInvalidValue;
+    if (!std::isfinite(sample_rate) || !(sample_rate > 0.f)) return (int)hipErrorInvalidValue;
+    if ((uintptr_t)params % 4 || (uintptr_t)h % 4) return (int)hipErrorInvalidValue;
+    if (overlap(params, (unsigned long long)rows * 8, h, (unsigned long long)rows * (unsigned long long)K * 4)) return (int)hipErrorInvalidValue;
+    const Rng g{(unsigned)((unsigned long long)seed & 0xffffffffu), (unsigned)((unsigned long long)seed >> 32), (unsigned)draw, row0};
+    hipLaunchKernelGGL(rir_synth_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, stream, params, h, rows, K, sample_rate, g);
     WM_CHECK_LAUNCH();
     return 0;
 }

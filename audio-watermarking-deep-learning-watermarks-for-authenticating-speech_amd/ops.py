@@ -1700,3 +1700,73 @@ class MdctCodecFn(torch.autograd.Function):
         mask = ctx.saved_tensors[0] if ctx.dead else None
         dx = mdct_codec(g.contiguous(), None, hop=hop, band=band, kcut=kcut, floor_step=floor_step, quantise=False, mask_in=mask)
         return dx, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------- reverb / echo
+# Per-row causal FIR convolution (wm_fir_rows, csrc/fir_rows.hip) and synthetic room responses (wm_rir_synth, csrc/distort.hip): the long
+# convolutive channel as a step of the graph.
+FIR_MAX_TAPS = 16384
+
+
+def _fir_taps(h, rows, device):
+    h = _chk(h, "h")
+    if h.dim() not in (1, 2) or h.shape[-1] < 1 or h.shape[-1] > FIR_MAX_TAPS:
+        raise ValueError(f"h: expected (K,) or (rows, K) with 1 <= K <= {FIR_MAX_TAPS}, got shape {tuple(h.shape)}")
+    if h.dim() == 2 and h.shape[0] != rows:
+        raise ValueError(f"h: expected one response, or one per row ({rows}), got shape {tuple(h.shape)}")
+    if h.device != device:
+        raise ValueError(f"h: expected a tensor on {device}, got one on {h.device}")
+    return h
+
+
+def fir_rows(x, h, reverse=False):
+    """One launch of wm_fir_rows along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows):
+    y[r][t] = sum_k h_r[k] x[r][t - k], the first n samples of the full convolution, every row from silence; h is (K,), one response for
+    all rows, or (rows, K), one per row.  reverse=True: y[r][t] = sum_k h_r[k] x[r][t + k], the transposed map (the backward pass)."""
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    h = _fir_taps(h, rows, x.device)
+    K = h.shape[-1]
+    y = torch.empty_like(x)
+    lib.wm_fir_rows(_p(x), _p(h), _p(y), rows, n, K, K if h.dim() == 2 else 0, int(bool(reverse)), _stream())
+    return y
+
+
+class FirRowsFn(torch.autograd.Function):
+    """y = H x per row (fir_rows) on the tape.  Saved for the backward: h alone; dx = H^T dy is the same launch with reverse=True.  h is a
+    CONSTANT of the graph: no gradient flows to it (a response is measured or drawn, not trained)."""
+
+    @staticmethod
+    def forward(ctx, x, h):
+        y = fir_rows(x, h)
+        ctx.save_for_backward(h)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return fir_rows(g.contiguous(), ctx.saved_tensors[0], reverse=True), None
+
+
+def rir_synth(params, taps, sample_rate=16000, seed=0, draw=0, row0=0):
+    """One launch of wm_rir_synth: (rows, taps) fp32 synthetic room responses from params, a (rows, 2) fp32 CUDA tensor of {rt60 in seconds,
+    direct-to-reverberant ratio in dB} per row -- exponentially decaying Gaussian noise behind a direct tap, unit energy, NOT a room
+    simulation.  Row r is a function of (seed, draw, row0 + r, params[r], taps, sample_rate) alone."""
+    import math
+    params = _chk(params, "params", 2)
+    if params.shape[0] < 1 or params.shape[1] != 2:
+        raise ValueError(f"params: expected (rows, 2) with at least one row, got shape {tuple(params.shape)}")
+    if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= FIR_MAX_TAPS:
+        raise ValueError(f"taps: expected an int in [1, {FIR_MAX_TAPS}], got {taps!r}")
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
+        raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+    rows = params.shape[0]
+    for v, name, top in ((draw, "draw", 2 ** 32 - 1), (row0, "row0", 2 ** 32 - rows)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top:
+            raise ValueError(f"{name}: expected an int in [0, {top}], got {v!r}")
+    seed = int(seed) & (2 ** 64 - 1)
+    h = _f32(rows, taps, device=params.device)
+    lib.wm_rir_synth(_p(params), _p(h), rows, taps, float(sample_rate), row0, seed - 2 ** 64 if seed >= 2 ** 63 else seed, draw, _stream())
+    return h

@@ -474,6 +474,45 @@ int wm_mdct_codec_plan(long long n, int M, int* frames_per_workgroup, long long*
 int wm_mdct_codec(const float* x, float* y, void* codes_out, const void* mask_in, const float* snr_db, long long rows, long long n, int M,
                   int band, int kcut, float floor_step, int quantise, wm_stream_t stream);
 
+/* ---- reverb / echo: per-row causal FIR convolution and its adjoint in one entry point; synthetic room responses ---------------------
+ * the long convolutive channel (a room, a loudspeaker-microphone path, an echo) as a step of the graph (the reference ships no code for it).
+ * x, y (rows, n) fp32, rows >= 1, 1 <= n <= 2^34, every row on its own.  h: K taps per row, 1 <= K <= 16384; row r uses h + r * h_stride,
+ * h_stride >= K for per-row responses or 0 for one response shared by all rows.
+ *   reverse == 0:  y[r][t] = sum_{k < K, k <= t} h_r[k] x[r][t - k]     the first n samples of the full convolution; lag 0 stays at lag 0
+ *   reverse != 0:  y[r][t] = sum_{k < K, t + k < n} h_r[k] x[r][t + k]  = flip(H flip(x)) by index mirroring; H is lower-triangular Toeplitz,
+ *                  so this is exactly H^T, the backward pass of the forward map.  h is a constant of both.
+ *   Samples outside [0, n) of a row's own data are zero by predicate (a neighbouring row is never read); K may exceed n.
+ *   Order.  With t = 32 T + j (mirrored t for reverse) a sample is ONE fp32 fmaf chain from +0 over d = 0, 1, .. and inside d over m = 0 .. 31 of
+ *     h[32 d + j - m] * x[32 (T - d) + m], where a tap index outside [0, K) or a sample outside the row contributes an exact zero and lag blocks
+ *     d > T (wholly before the row start) may be left out.  With finite data these zeros change nothing, so the chain is the K products
+ *     in rising d, rising m.  h = {1} hands x on bit for bit (a -0 leaves as +0).  With finite taps a sample's bits depend on its row's x, its
+ *     taps, K, n, reverse and t only -- never on the grid, the other rows of the launch, or whether h is shared: rows [0, R) in one call equal R
+ *     one-row calls, and a shared h equals the same h copied per row.
+ * One launch (csrc/fir_rows.hip: 32 x 32 Toeplitz blocks on the fp32 MFMA, x and taps in LDS).  No atomics, no scratch.  x, h, y may start at
+ * any multiple of 4 bytes.  IN PLACE IS REFUSED.
+ * hipErrorInvalidValue before any launch: rows, n or K out of range, h_stride neither 0 nor >= K, a null or misaligned pointer, y overlapping
+ * x or h. */
+int wm_fir_rows(const float* x, const float* h, float* y, long long rows, long long n, int K, long long h_stride, int reverse,
+                wm_stream_t stream);
+
+/* wm_rir_synth: h (rows, K) fp32 out, one synthetic room response per row from params (rows, 2) fp32 on the device, {rt60_s, drr_db} per row.
+ * It is exponentially decaying Gaussian noise behind a direct tap -- NOT a room simulation.  1 <= K <= 16384, sample_rate > 0.  For row r:
+ *     c = 3 ln 10 / (rt60_r * sample_rate)                 e[0] = 0,  e[k] = z_k * exp(-k c), 1 <= k < K      E = sum_k e[k]^2
+ *     w = 10^(-drr_r / 10)     a = sqrt(w / E)             h[0] = 1 / sqrt(1 + w),  h[k] = (a / sqrt(1 + w)) e[k]
+ *   so the direct-to-reverberant energy ratio is drr_db, the amplitude decays 60 dB in rt60 and the total energy is 1: white input keeps its
+ *   power.  K = 1, E = 0, rt60 not > 0 or a non-finite drr_db give h = {1, 0, ...}; drr_db is clamped to [-100, 100].
+ *   z_k: the Box-Muller normal of wm_distort for "sample" k of the counter (k >> 2, 0xFFFFFFFE, row0 + r, draw), key (seed low, seed high), the
+ *     four words used as for samples.  No other draw has that counter: wm_distort's samples have high word 0, its parameter counter both
+ *     words 0xFFFFFFFF.
+ *   Arithmetic: c, k c, exp, w, a and 1 / sqrt(1 + w) in fp64 from the fp32 inputs; exp(-k c) is rounded to fp32 and e[k] is one fp32 product; E is
+ *     added in fp32 in the order of wm_distort's sums (256 lanes over the quads i, i + 256, ..., one fmaf chain per position in the quad,
+ *     (c0 + c1) + (c2 + c3), the xor butterfly 32..1, waves 0 + 1 + 2 + 3); h[k] = (float)(a / sqrt(1 + w)) * e[k], one fp32 product.
+ *   A row's taps depend on (seed, draw, row0 + r, params_r, K, sample_rate) only: rows [0, R) in one call equal R calls with row0 = r.
+ * hipErrorInvalidValue before any launch: rows or K out of range, row0 or draw out of range (as wm_distort), a non-finite or non-positive
+ * sample_rate, a null or misaligned pointer, params overlapping h. */
+int wm_rir_synth(const float* params, float* h, long long rows, int K, float sample_rate, long long row0, long long seed, long long draw,
+                 wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
