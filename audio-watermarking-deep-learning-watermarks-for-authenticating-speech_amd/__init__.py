@@ -6,7 +6,7 @@ from .losses import (MultiScaleMelLoss, TFLoudnessLoss, clamp_peak, detection_lo
 from .step import LOSS_WEIGHTS, forward_losses, train_step, eval_forward
 from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
-from .attacks import Convolved, Distortion, Lowpass, Resampled, Reverb, TransformCodec, echo_ir, evaluate_robustness
+from .attacks import Convolved, Distortion, Lowpass, Resampled, Reverb, TimeWarp, TransformCodec, echo_ir, evaluate_robustness
 from . import attacks
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
                         evaluate_unseen_file, generate_watermarked_audio, load_audio, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
@@ -21,5 +21,5 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "fir_lowpass", "clamp_peak", "limit_rms", "postprocess", "high_freq_penalty", "detection_losses", "l1_to_zero",
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
-           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "Convolved", "Reverb", "echo_ir", "evaluate_robustness",
+           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "Convolved", "Reverb", "TimeWarp", "echo_ir", "evaluate_robustness",
            "lib", "LIB_PATH"]

@@ -18,12 +18,17 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
   Reverb       the same launch with SYNTHETIC room responses drawn on the device per row (wm_rir_synth) at a per-row RT60 and
                direct-to-reverberant ratio: exponentially decaying Gaussian noise, not a room simulation -- survival in real rooms
                is unmeasured
+  TimeWarp     the desynchronising channel: playback at another speed (tempo and pitch together), sinusoidal wow / flutter and a cut at
+               the front, through a Hann-windowed sinc interpolator whose phase is computed per output sample -- one wm_time_warp launch
+               (ops.TimeWarpFn), its backward the same launch with adjoint=True.  No pitch-preserving stretch; survival against real
+               players and tapes is unmeasured
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
 and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws.  The counters (word 0, word 1, row, draw)
-of the four families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
-parameters (~0 - 1, ~0), the taps of a synthetic response (k >> 2, ~0 - 1)."""
+of the six families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
+parameters (~0 - 1, ~0), the taps of a synthetic response (k >> 2, ~0 - 1), TimeWarp's speed / shift / flutter (~0 - 2, ~0) and its
+flutter phase (~0 - 3, ~0)."""
 from __future__ import annotations
 
 import math
@@ -41,6 +46,8 @@ NOISE_GRAD_MODES = ("through", "detached")
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _PARAM_Q = 0xFFFFFFFFFFFFFFFF        # the counter words (q low, q high) of a row's parameters: no sample has them (n <= 2^34)
 _PARAM2_Q = 0xFFFFFFFFFFFFFFFE       # the same for Reverb's and Convolved's parameters
+_WARP_Q = 0xFFFFFFFFFFFFFFFD         # TimeWarp's speed, shift, flutter rate and flutter depth
+_WARP_PHASE_Q = 0xFFFFFFFFFFFFFFFC   # TimeWarp's flutter phase
 _RIR_HIGH = 0xFFFFFFFE               # the second counter word of a synthetic response's taps (the first is k >> 2 < 2^12)
 
 
@@ -546,6 +553,131 @@ class Reverb(torch.nn.Module):
 
     def extra_repr(self):
         return f"rt60={self.rt60}, drr_db={self.drr_db}, taps={self.taps}, sample_rate={self.sample_rate}, seed={self.seed}"
+
+
+def row_warp_params(seed, draw, rows, speed, shift_s, flutter_hz, flutter_depth, sample_rate):
+    """TimeWarp's (len(rows), 6) float32 parameters {a, off, d, w, phi, c} of rows `rows` (an int array of row0 + r), the rows of
+    wm_time_warp's `params`.  speed, shift_s, flutter_hz, flutter_depth: (low, high) pairs (the last two None: no flutter).  Words o0..o3
+    of the counter (0xFFFFFFFD, 0xFFFFFFFF, row, draw) -- met by nothing else -- map onto speed, shift, flutter rate and flutter depth as
+    fmaf(high - low, u, low) in float32, word o0 of (0xFFFFFFFC, 0xFFFFFFFF, row, draw) is the phase u.  From these float32 draws, in
+    float64 and rounded to float32 once each: a = speed, off = shift * sample_rate, w = rate / sample_rate, d = depth a / (2 pi w) with the
+    rounded w (0 where w or depth is 0), phi = u, c = min(1, 1 / (a (1 + depth)))."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    key = _key(seed)
+    o = philox4x32_10((_WARP_Q & 0xFFFFFFFF, _WARP_Q >> 32, rows, int(draw)), key)
+    phase = _unit(philox4x32_10((_WARP_PHASE_Q & 0xFFFFFFFF, _WARP_PHASE_Q >> 32, rows, int(draw)), key)[0])
+
+    def affine(pair, u):
+        lo, hi = (np.float32(v) for v in pair)
+        return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
+    flutter = flutter_hz is not None and flutter_depth is not None
+    a = affine(speed, _unit(o[0])).astype(np.float64)
+    shift = affine(shift_s, _unit(o[1])).astype(np.float64)
+    hz = affine(flutter_hz, _unit(o[2])).astype(np.float64) if flutter else np.zeros(len(rows))
+    depth = affine(flutter_depth, _unit(o[3])).astype(np.float64) if flutter else np.zeros(len(rows))
+    w = (hz / float(sample_rate)).astype(np.float32)
+    on = (w != 0) & (depth != 0)
+    d = np.where(on, depth * a / (2.0 * math.pi * np.where(on, w.astype(np.float64), 1.0)), 0.0)
+    c = np.minimum(1.0, 1.0 / (a * (1.0 + depth)))
+    return np.stack([a, shift * float(sample_rate), d, w.astype(np.float64), np.where(on, phase, 0.0), c], axis=1).astype(np.float32)
+
+
+def _sinpi(v):
+    """sin(pi v) of a float64 tensor, reduced to [-1/2, 1/2] first so that the argument of sin carries no rounding of pi v at large v"""
+    k = torch.round(v)
+    return torch.sin(math.pi * (v - k)) * (1.0 - 2.0 * torch.remainder(k, 2.0))
+
+
+def _warp_rows_host(x2, params, table, zeros, res):
+    """wm_time_warp's forward map on a (rows, n) float32 CPU tensor in torch ops, which autograd differentiates: positions and weights from
+    the definition (fp64 positions, float32 table, float32 weights), the taps gathered per output sample and summed in float32.  Row by
+    row, so that a row's bits do not depend on the rest of the batch."""
+    n = x2.shape[1]
+    t = torch.arange(n, dtype=torch.float64)
+    out = []
+    for xr, prm in zip(x2, params):
+        a, off, d, w, phi = (float(v) for v in prm[:5])
+        c32 = torch.tensor(1.0 if math.isnan(float(prm[5])) else min(max(float(prm[5]), 0.25), 1.0), dtype=torch.float32)
+        c = float(c32)
+        q = w * t + phi
+        p = a * t + off + d * _sinpi(2.0 * (q - torch.floor(q)))
+        H = int(math.ceil(zeros / c))
+        k = (torch.floor(p) - H)[:, None] + torch.arange(2 * H + 2, dtype=torch.float64)      # covers (p - H - 1, p + H + 1]
+        v = c * (p[:, None] - k).abs()
+        inside = (v < zeros) & (k >= 0) & (k < n)
+        s = v * res
+        i = torch.floor(s).clamp(0, zeros * res - 1)
+        f = (s - i).to(torch.float32)
+        i = i.to(torch.int64)
+        t0 = table[i]
+        W = torch.where(inside, c32 * (f * (table[i + 1] - t0) + t0), torch.zeros((), dtype=torch.float32))
+        out.append((W * xr[k.clamp(0, n - 1).to(torch.int64)]).sum(dim=-1))
+    return torch.stack(out)
+
+
+class TimeWarp(torch.nn.Module):
+    """The desynchronising channel on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): y[t] reads x at the position
+    p(t) = speed * t + shift + flutter, through a Hann-windowed sinc interpolator of `zeros` zero crossings a side whose cutoff follows the
+    speed, so a faster playback does not alias (wm_time_warp in include/wm_hip.h has the definition).  It is a speed change -- tempo and
+    pitch move together, as on a turntable or with a wrong clock --, plus sinusoidal wow / flutter, plus a cut of shift_s seconds at the
+    front (negative: silence in front).  A pitch-preserving stretch (phase vocoder, WSOLA) and a pitch shift at constant tempo are NOT
+    built, and A WATERMARK'S SURVIVAL AGAINST REAL PLAYERS AND TAPES IS UNMEASURED.
+    THE OUTPUT KEEPS THE INPUT'S LENGTH AND THE LABELS ARE NOT MOVED: where the read position leaves the row the output is silence, and that
+    silence -- like every warped sample -- is still labelled as its clip is; a per-sample localisation label stays at its output index.
+    speed in [0.5, 2], shift_s, flutter_hz in (0, sample_rate / 4], flutter_depth in [0, 0.25] (the relative peak deviation of the
+    instantaneous speed, which keeps p strictly increasing and the cutoff at 0.4 or more): a number fixes the value, a pair draws one per
+    row, reproducible from (seed, draw, row0 + r) (row_warp_params); the two flutter arguments are given together or not at all.
+    Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
+    pieces draws what the whole batch would.  `last_params`: the (rows, 6) {a, off, d, w, phi, c} of the last call (a CPU tensor).  The
+    parameters are constants of the graph.  There is no shortcut for speed 1: the kernel hands a whole-sample shift on bit for bit.
+    CUDA tensors run wm_time_warp, one launch each way (ops.TimeWarpFn); CPU tensors the same definition in torch ops (gathered taps times
+    float32 weights), differentiable by autograd."""
+
+    RES = 512
+
+    def __init__(self, speed=(0.9, 1.1), shift_s=0.0, flutter_hz=None, flutter_depth=None, zeros=16, sample_rate=SAMPLE_RATE, seed=0):
+        super().__init__()
+        _check_seed_draw(seed)
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
+            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+        self.speed, self.shift_s = _pair(speed, "speed"), _pair(shift_s, "shift_s")
+        if not 0.5 <= self.speed[0] <= self.speed[1] <= 2.0:
+            raise ValueError(f"speed: expected values in [0.5, 2], got {speed!r}")
+        if (flutter_hz is None) != (flutter_depth is None):
+            raise ValueError("flutter_hz and flutter_depth: give both or neither")
+        self.flutter_hz = None if flutter_hz is None else _pair(flutter_hz, "flutter_hz")
+        self.flutter_depth = None if flutter_depth is None else _pair(flutter_depth, "flutter_depth")
+        if self.flutter_hz is not None:
+            if not 0.0 < self.flutter_hz[0] <= self.flutter_hz[1] <= sample_rate / 4:
+                raise ValueError(f"flutter_hz: expected values in (0, sample_rate / 4 = {sample_rate / 4}], got {flutter_hz!r}")
+            if not 0.0 <= self.flutter_depth[0] <= self.flutter_depth[1] <= 0.25:
+                raise ValueError(f"flutter_depth: expected values in [0, 0.25], got {flutter_depth!r}")
+        ops.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
+        self.zeros, self.sample_rate, self.seed = zeros, sample_rate, seed
+        self.last_params = None
+        self.reset()
+
+    def reset(self, draw=0):
+        _check_seed_draw(draw=draw)
+        self.draw = draw
+        return self
+
+    def forward(self, x, row0=0):
+        x, rows = _rows_of(x, row0)
+        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        self.last_params = torch.from_numpy(row_warp_params(self.seed, draw, row0 + np.arange(rows), self.speed, self.shift_s,
+                                                            self.flutter_hz, self.flutter_depth, self.sample_rate))
+        x2 = x.to(torch.float32).reshape(rows, -1)
+        if x.is_cuda:
+            y = ops.TimeWarpFn.apply(x2, self.last_params.to(x.device), ops._time_warp_table_on(self.zeros, self.RES, x.device),
+                                     self.zeros, self.RES)
+        else:
+            y = _warp_rows_host(x2, self.last_params, ops.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
+        return y.reshape(x.shape)
+
+    def extra_repr(self):
+        return (f"speed={self.speed}, shift_s={self.shift_s}, flutter_hz={self.flutter_hz}, flutter_depth={self.flutter_depth}, "
+                f"zeros={self.zeros}, sample_rate={self.sample_rate}, seed={self.seed}")
 
 
 @torch.no_grad()

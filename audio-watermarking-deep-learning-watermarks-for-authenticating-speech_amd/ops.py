@@ -1770,3 +1770,89 @@ def rir_synth(params, taps, sample_rate=16000, seed=0, draw=0, row0=0):
     h = _f32(rows, taps, device=params.device)
     lib.wm_rir_synth(_p(params), _p(h), rows, taps, float(sample_rate), row0, seed - 2 ** 64 if seed >= 2 ** 63 else seed, draw, _stream())
     return h
+
+
+# ---------------------------------------------------------------------------------------------- speed change / wow and flutter
+# Time warp through a windowed-sinc interpolator (wm_time_warp, csrc/time_warp.hip): the output reads the input at a position that
+# advances `speed` samples per sample, wobbles sinusoidally and starts a cut in.  The desynchronising channel as a step of the graph.
+TIME_WARP_MAX_TABLE = 128 * 1024 // 4           # floats
+
+
+def _time_warp_dims(zeros, res):
+    for v, name, lo, hi in ((zeros, "zeros", 4, 32), (res, "res", 64, 1024)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{name}: expected an int in [{lo}, {hi}], got {v!r}")
+    if res & (res - 1):
+        raise ValueError(f"res: expected a power of two, got {res}")
+    if zeros * res + 2 > TIME_WARP_MAX_TABLE:
+        raise ValueError(f"zeros * res + 2 = {zeros * res + 2} floats is above the {TIME_WARP_MAX_TABLE} (128 KiB) a table may take")
+
+
+_TIME_WARP_HOST = {}     # (zeros, res) -> the table (a CPU tensor)
+_TIME_WARP_DEV = {}      # (zeros, res, device) -> the same on the device
+
+
+def time_warp_table(zeros=16, res=512):
+    """The interpolator's half response, a (zeros * res + 2,) fp32 CPU tensor (cached; do not write to it): sinc(v) * 0.5 (1 + cos(pi v /
+    zeros)) at v = i / res, a Hann-windowed sinc with `zeros` zero crossings at `res` points each, computed in float64.  Entry 0 is exactly
+    1, the entries at the other multiples of res and the last two exactly 0, so that a whole-sample shift is the identity."""
+    _time_warp_dims(zeros, res)
+    if (zeros, res) not in _TIME_WARP_HOST:
+        import numpy as np
+        v = np.arange(zeros * res + 2, dtype=np.float64) / res
+        tab = np.sinc(v) * 0.5 * (1.0 + np.cos(np.pi * v / zeros))
+        tab[res::res] = 0.0                      # the zero crossings, exactly
+        tab[0] = 1.0
+        tab[-2:] = 0.0
+        _TIME_WARP_HOST[(zeros, res)] = torch.from_numpy(tab.astype(np.float32))
+    return _TIME_WARP_HOST[(zeros, res)]
+
+
+def _time_warp_table_on(zeros, res, device):
+    key = (zeros, res, str(device))
+    if key not in _TIME_WARP_DEV:
+        _TIME_WARP_DEV[key] = time_warp_table(zeros, res).to(device)
+    return _TIME_WARP_DEV[key]
+
+
+def time_warp(x, params, table=None, adjoint=False, zeros=16, res=512):
+    """One launch of wm_time_warp along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows):
+    y[r][t] = sum_k W(p_r(t) - k) x[r][k] with p_r(t) = a t + off + d sinpi(2 frac(w t + phi)) from params, a (rows, 6) fp32 CUDA tensor of
+    {a, off, d, w, phi, c} per row, and W the table's interpolated value at cutoff c (include/wm_hip.h has the definition).  table: the
+    (zeros * res + 2,) fp32 half response, None for time_warp_table(zeros, res).  adjoint=True: the transposed map (the backward pass),
+    defined for increasing p."""
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    _time_warp_dims(zeros, res)
+    params = _chk(params, "params", 2)
+    if tuple(params.shape) != (rows, 6):
+        raise ValueError(f"params: expected ({rows}, 6), one {{a, off, d, w, phi, c}} per row, got shape {tuple(params.shape)}")
+    table = _time_warp_table_on(zeros, res, x.device) if table is None else _chk(table, "table", 1)
+    if table.shape[0] != zeros * res + 2:
+        raise ValueError(f"table: expected zeros * res + 2 = {zeros * res + 2} values, got shape {tuple(table.shape)}")
+    for t, name in ((params, "params"), (table, "table")):
+        if t.device != x.device:
+            raise ValueError(f"{name}: expected a tensor on {x.device}, got one on {t.device}")
+    y = torch.empty_like(x)
+    lib.wm_time_warp(_p(x), _p(params), _p(table), _p(y), rows, n, zeros, res, int(bool(adjoint)), _stream())
+    return y
+
+
+class TimeWarpFn(torch.autograd.Function):
+    """y = W x per row (time_warp) on the tape.  Saved for the backward: params and the table alone; dx = W^T dy is the same launch with
+    adjoint=True.  params and the table are CONSTANTS of the graph: no gradient flows to them (a speed is drawn, not trained)."""
+
+    @staticmethod
+    def forward(ctx, x, params, table, zeros, res):
+        y = time_warp(x, params, table, zeros=zeros, res=res)
+        ctx.save_for_backward(params, table)
+        ctx.dims = (zeros, res)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        params, table = ctx.saved_tensors
+        return time_warp(g.contiguous(), params, table, adjoint=True, zeros=ctx.dims[0], res=ctx.dims[1]), None, None, None, None

@@ -513,6 +513,40 @@ int wm_fir_rows(const float* x, const float* h, float* y, long long rows, long l
 int wm_rir_synth(const float* params, float* h, long long rows, int K, float sample_rate, long long row0, long long seed, long long draw,
                  wm_stream_t stream);
 
+/* ---- speed change, wow / flutter and a cut at the front: time warp through a windowed-sinc interpolator, and its adjoint ---------------
+ * the desynchronising channel (the reference ships no code for it): the output reads the input at a position that advances `a` input
+ * samples per output sample, wobbles sinusoidally and starts `off` samples in.  The output keeps the input's length.
+ * x, y (rows, n) fp32, rows >= 1, 1 <= n <= 2^34, every row on its own.  params (rows, 6) fp32 on the device, {a, off, d, w, phi, c} per row:
+ *   a speed, off start position in samples, d / w / phi flutter depth in samples / rate in cycles per sample / phase in cycles, c the
+ *   anti-alias cutoff relative to Nyquist, clamped to [1/4, 1] (NaN: 1); c32 the clamped fp32 value, c the same number in fp64.
+ * tab: zeros * res + 2 fp32 values from the caller, the half response at `res` points per zero crossing over `zeros` zero crossings
+ *   (Z = zeros in 4..32, R = res a power of two in 64..1024, (Z R + 2) * 4 <= 128 KiB).
+ *   p(t) = fma(a, t, off) + d * sinpi(2 * frac(fma(w, t, phi)))      in fp64 from the fp32 parameters and the integer t, frac(v) = v - floor(v);
+ *                                                                    d == 0: the first fma alone
+ *   W(u):  v = c * |u|,  s = v * R,  i = floor(s)  (all fp64),  f = (float)(s - i);   W = c32 * fmaf(f, tab[i + 1] - tab[i], tab[i])   in fp32
+ *   adjoint == 0:  y[r][t] = sum over k in [0, n) with c |p(t) - k| < Z  of  W(p(t) - k) * x[r][k]      u = p(t) - k is one fp64 subtraction,
+ *                  ONE fp32 fmaf chain from +0 in rising k
+ *   adjoint != 0:  y[r][k] = sum over t in [0, n) with c |p(t) - k| < Z  of  W(p(t) - k) * x[r][t]      the transposed map with the identical
+ *                  fp32 weights, ONE fp32 fmaf chain from +0 in rising t: a gather, never a scatter
+ *   The predicate is v < Z on the fp64 v of W, so i <= Z R - 1.  Samples outside [0, n) of a row's own data are never read (a neighbouring
+ *   row is never touched).
+ *   The adjoint is DEFINED FOR p STRICTLY INCREASING with 0 < a and all parameters finite: the terms of one sample are then one interval of
+ *   t, found from the bracket (k -+ (Z / c + 1 + |d|) - off) / a by bisection on p and left at the first p(t) - k > Z / c + 1, and at
+ *   most 4096 terms are taken (Z / c <= 128: a slope of p of 1 / 15 or more never has as many).  A row with a <= 0 or a non-finite
+ *   parameter gets zeros from the adjoint, and for p not increasing terms may be missing.  The forward map follows the formulas for any
+ *   parameters.  WHATEVER params HOLDS -- NaN, infinities, a <= 0 -- every access stays inside x, y, params and tab, and a sample costs
+ *   a bounded number of steps: only the values of such a row are unspecified.
+ *   With a = 1, integer off, d = 0, c = 1 and a table whose entries at multiples of R are exactly {1, 0, 0, ...}, y is x shifted by off bit
+ *   for bit (a -0 leaves as +0), zeros where the shift runs out of the row.
+ *   A sample's bits depend on its row's data, its row's parameters, tab, n and its index only -- never on the grid or on the other rows
+ *   of the launch; two launches give identical bits.
+ * One launch (csrc/time_warp.hip: the table in LDS, one lane per output sample), stateless, enqueue-only.  No atomics, no scratch.  x, params,
+ * tab, y may start at any multiple of 4 bytes.  IN PLACE IS REFUSED.
+ * hipErrorInvalidValue before any launch: rows, n, zeros or res out of range, a table above 128 KiB, a null or misaligned pointer, y
+ * overlapping x, params or tab. */
+int wm_time_warp(const float* x, const float* params, const float* tab, float* y, long long rows, long long n, int zeros, int res,
+                 int adjoint, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
