@@ -85,11 +85,21 @@ __global__ void l1_bwd_kernel(const float* __restrict__ x, const float* __restri
     dx[i] = v > 0.f ? k : (v < 0.f ? -k : 0.f);
 }
 
-__global__ __launch_bounds__(256) void sum_scale2_kernel(const float* __restrict__ partial, int n, double scale, float* out) {
-    __shared__ double scratch[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-    s = block_sum_d<4>(s, scratch);
+// out[0] = (float)(scale * sum(partial[0..n))): fp64, fixed order.  One 1024-thread block, element i into accumulator
+// (i >> 10) & 3 of thread i & 1023: at the 32 256 partials of the B = 256 BCE sums that is 8 dependent adds per chain (it was
+// one chain of 126 per thread in a 256-thread block), then the 16 waves' sums in wave order.
+__global__ __launch_bounds__(1024) void sum_scale2_kernel(const float* __restrict__ partial, int n, double scale, float* out) {
+    __shared__ double scratch[16];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int i = threadIdx.x;
+    for (; i + 3072 < n; i += 4096) {
+        const float v0 = partial[i], v1 = partial[i + 1024], v2 = partial[i + 2048], v3 = partial[i + 3072];
+        s0 += (double)v0; s1 += (double)v1; s2 += (double)v2; s3 += (double)v3;
+    }
+    if (i < n) s0 += (double)partial[i];
+    if (i + 1024 < n) s1 += (double)partial[i + 1024];
+    if (i + 2048 < n) s2 += (double)partial[i + 2048];
+    const double s = block_sum_d<16>((s0 + s1) + (s2 + s3), scratch);
     if (threadIdx.x == 0) out[0] = (float)(s * scale);
 }
 
@@ -111,7 +121,7 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 
 namespace wm {
 int launch_sum_scale2(const float* partial, int n, double scale, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(256), 0, stream, partial, n, scale, out);
+    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(1024), 0, stream, partial, n, scale, out);
     WM_CHECK_LAUNCH();
     return 0;
 }
@@ -126,10 +136,10 @@ int wm_bce_fwd(const float* logits, const long long* message, float* partial, fl
     const int chunks = (T * NO + 4095) / 4096, grid = chunks * R;
     hipLaunchKernelGGL(bce_fwd_kernel, dim3(chunks, R), dim3(256), 0, stream, logits, message, B, R, T, NO, partial);
     WM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, grid, 1.0 / ((double)R * T), loc_out);
+    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(1024), 0, stream, (const float*)partial, grid, 1.0 / ((double)R * T), loc_out);
     WM_CHECK_LAUNCH();
     if (NO > 1) {
-        hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial + grid, grid,
+        hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(1024), 0, stream, (const float*)partial + grid, grid,
                            1.0 / ((double)B * T * (NO - 1)), bce_out);
         WM_CHECK_LAUNCH();
     }
@@ -150,7 +160,7 @@ int wm_l1_fwd(const float* x, float* partial, float* out, long long n, hipStream
     const int grid = 256;
     hipLaunchKernelGGL(abs_sum_kernel, dim3(grid), dim3(256), 0, stream, x, (size_t)n, partial);
     WM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, grid, 1.0 / (double)n, out);
+    hipLaunchKernelGGL(sum_scale2_kernel, dim3(1), dim3(1024), 0, stream, (const float*)partial, grid, 1.0 / (double)n, out);
     WM_CHECK_LAUNCH();
     return 0;
 }

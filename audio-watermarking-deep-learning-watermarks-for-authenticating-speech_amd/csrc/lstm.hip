@@ -1496,14 +1496,15 @@ __global__ __launch_bounds__(256) void lstm_wgrad_bf_kernel(const float* __restr
     out[256 * 128 + tid] = (red[tid] + red[256 + tid]) + (red[512 + tid] + red[768 + tid]);
 }
 
-__global__ void lstm_wgrad_reduce_kernel(const float* __restrict__ partial, int nparts, float* dw_ih, float* dw_hh,
-                                         float* db_ih, float* db_hh, int accumulate) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr int stride = 256 * 128 + 256;
-    if (i >= stride) return;
-    double sd = 0.0;
-    for (int p = 0; p < nparts; ++p) sd += (double)partial[(size_t)p * stride + i];
-    const float s = (float)sd;
+// per-clip (or per-workgroup) slabs [nparts][256*128 + 256] -> the four gradients.  Block = 64 columns x 8 part-groups
+// (column_sum_d), 516 blocks: at B = 256 every thread adds 32 slabs, four loads in flight, coalesced over the column.
+constexpr int kWgradSlab = 256 * 128 + 256;
+__global__ __launch_bounds__(512) void lstm_wgrad_reduce_kernel(const float* __restrict__ partial, int nparts, float* dw_ih,
+                                                                float* dw_hh, float* db_ih, float* db_hh, int accumulate) {
+    __shared__ double sq[8][64];
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);            // kWgradSlab % 64 == 0: every column is valid
+    const float s = (float)column_sum_d<8>(partial, nparts, (size_t)kWgradSlab, i, true, sq);
+    if (threadIdx.x >= 64) return;
     if (i < 256 * 128) {
         const int n = gate_row(i >> 7), j = i & 127;
         float* dst = (j < 64) ? dw_ih + n * 64 + j : dw_hh + n * 64 + (j - 64);
@@ -1514,6 +1515,7 @@ __global__ void lstm_wgrad_reduce_kernel(const float* __restrict__ partial, int 
         db_hh[n] = accumulate ? db_hh[n] + s : s;
     }
 }
+static_assert(kWgradSlab % 64 == 0, "lstm_wgrad_reduce_kernel: whole 64-column blocks");
 
 }  // namespace
 
@@ -1611,8 +1613,7 @@ int wm_lstm_bwd_wgrad(float* gates, const float* cst, const float* dh_out, const
     }
     hipLaunchKernelGGL(lstm_bwd_ws_kernel, dim3(B), dim3(512), lds, stream, gates, cst, dh_out, w_hh, x, h, partial, T);
     WM_CHECK_LAUNCH();
-    constexpr int n = 256 * 128 + 256;
-    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const float*)partial, B,
+    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3(kWgradSlab / 64), dim3(512), 0, stream, (const float*)partial, B,
                        dw_ih, dw_hh, db_ih, db_hh, accumulate);
     WM_CHECK_LAUNCH();
     return 0;
@@ -1659,8 +1660,7 @@ int wm_lstm_wgrad(const float* da, const float* x, const float* h, float* partia
         hipLaunchKernelGGL(lstm_wgrad_kernel, dim3(grid), dim3(256), lds, stream, da, x, h, partial, B, T);
     }
     WM_CHECK_LAUNCH();
-    constexpr int n = 256 * 128 + 256;
-    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const float*)partial, grid,
+    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3(kWgradSlab / 64), dim3(512), 0, stream, (const float*)partial, grid,
                        dw_ih, dw_hh, db_ih, db_hh, accumulate);
     WM_CHECK_LAUNCH();
     return 0;

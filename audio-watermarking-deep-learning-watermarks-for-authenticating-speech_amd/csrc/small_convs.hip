@@ -64,10 +64,8 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const float* __restrict__
     extern __shared__ __align__(16) float smem[];
     float* gs = smem;                                // [64][GS]
     float* ss = gs + 64 * GS;                        // [NT + 40]: s[t0 - 3 + i]; zero padded so that B-operand reads stay in range
-    float* ws = ss + NT + 40;                        // [64][8]
-    float* dsp = ws + 512;                           // [4][NT] partial ds of the four channel groups
+    float* dsp = ss + NT + 40;                       // [4][NT] partial ds of the four channel groups (16-byte aligned: 17192 floats in)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    for (int i = tid; i < 512; i += 256) ws[i] = ((i & 7) < 7) ? w[(i >> 3) * 7 + (i & 7)] : 0.f;
     const int tilesPerClip = (T + NT - 1) / NT, ntiles = B * tilesPerClip;
     f32x16 acc[2];
 #pragma unroll
@@ -144,18 +142,20 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const float* __restrict__
         }
         // ---- ds (Detector stem: gradient w.r.t. the watermarked half of the batch)
         if (ds && b < nds) {
-            const int cg = wave, tq = lane;                       // 16 channels x 4 samples per thread
+            // 16 channels x 4 samples per thread.  The channel is the same in every lane of a wave, so the seven taps come
+            // from w through the scalar cache into scalar registers: three LDS reads per channel (the g row) instead of five
+            const int cg = __builtin_amdgcn_readfirstlane(wave), tq = lane;
             float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
 #pragma unroll 4
             for (int cc = 0; cc < 16; ++cc) {
                 const int co = cg * 16 + cc;
-                const float4 ga = *reinterpret_cast<const float4*>(gs + co * GS + 4 * tq);         // t0+4tq-4 .. -1
-                const float4 gb4 = *reinterpret_cast<const float4*>(gs + co * GS + 4 * tq + 4);    // t0+4tq   .. +3
-                const float4 gc = *reinterpret_cast<const float4*>(gs + co * GS + 4 * tq + 8);     // t0+4tq+4 .. +7
-                const float4 w0 = *reinterpret_cast<const float4*>(ws + co * 8), w1 = *reinterpret_cast<const float4*>(ws + co * 8 + 4);
+                const f32x4 ga = lds_read4(gs + co * GS + 4 * tq);          // t0+4tq-4 .. -1
+                const f32x4 gb4 = lds_read4(gs + co * GS + 4 * tq + 4);     // t0+4tq   .. +3
+                const f32x4 gc = lds_read4(gs + co * GS + 4 * tq + 8);      // t0+4tq+4 .. +7
+                const float* wc = w + co * 7;
                 // gv[i] = g[co][t0 + 4tq - 3 + i], i = 0..9 ;  ds[t] = sum_j g[t + 3 - j] w[j]
                 const float gv[10] = {ga.y, ga.z, ga.w, gb4.x, gb4.y, gb4.z, gb4.w, gc.x, gc.y, gc.z};
-                const float wj[7] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z};
+                const float wj[7] = {wc[0], wc[1], wc[2], wc[3], wc[4], wc[5], wc[6]};
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
                     o0 = fmaf(gv[6 - j], wj[j], o0); o1 = fmaf(gv[7 - j], wj[j], o1);
@@ -191,36 +191,23 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const float* __restrict__
     for (int i = tid; i < 512; i += 256) out[i] = red[i];
 }
 
-// out[i] (+)= sum_p partial[p*stride + i],  i < count.  Block = 64 outputs x 4 quarters of the slab list (fp64, fixed
-// order: bit-reproducible); launch with 256 threads and ceil(count / 64) blocks.
+// out[i] (+)= sum_p partial[p*stride + i],  i < count.  Block = 64 outputs x 4 part-groups of the slab list (column_sum_d:
+// fp64, fixed order, bit-reproducible); launch with 256 threads and ceil(count / 64) blocks.
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, int nparts, int stride, int count,
                                                               float* __restrict__ out, int accumulate) {
     __shared__ double sq[4][64];
-    const int il = threadIdx.x & 63, grp = threadIdx.x >> 6, i = blockIdx.x * 64 + il;
-    const int per = (nparts + 3) / 4, p0 = grp * per, p1 = min(p0 + per, nparts);
-    double s0 = 0.0, s1 = 0.0;
-    if (i < count) {
-        int p = p0;
-        for (; p + 1 < p1; p += 2) {
-            s0 += (double)partial[(size_t)p * stride + i];
-            s1 += (double)partial[(size_t)(p + 1) * stride + i];
-        }
-        if (p < p1) s0 += (double)partial[(size_t)p * stride + i];
-    }
-    sq[grp][il] = s0 + s1;
-    __syncthreads();
-    if (grp == 0 && i < count) {
-        const float s = (float)((sq[0][il] + sq[1][il]) + (sq[2][il] + sq[3][il]));
-        out[i] = accumulate ? out[i] + s : s;
-    }
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float s = (float)column_sum_d<4>(partial, nparts, (size_t)stride, i, i < count, sq);
+    if (threadIdx.x < 64 && i < count) out[i] = accumulate ? out[i] + s : s;
 }
-// stem partial [nparts][64][8] -> dw[64][7], db[64]
-__global__ void stem_reduce_kernel(const float* __restrict__ partial, int nparts, float* dw, float* db, int accumulate) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 512) return;
-    double sd = 0.0;
-    for (int p = 0; p < nparts; ++p) sd += (double)partial[(size_t)p * 512 + i];
-    const float s = (float)sd;
+// stem partial [nparts][64][8] -> dw[64][7], db[64].  nparts reaches 2 x NCU = 512 slabs: 8 blocks of 64 columns x 16
+// part-groups (<= 32 slabs per thread, four at a time), where one thread per column used to walk all of them.
+__global__ __launch_bounds__(1024) void stem_reduce_kernel(const float* __restrict__ partial, int nparts, float* dw, float* db,
+                                                           int accumulate) {
+    __shared__ double sq[16][64];
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);            // grid = 8: i < 512
+    const float s = (float)column_sum_d<16>(partial, nparts, (size_t)512, i, true, sq);
+    if (threadIdx.x >= 64) return;
     const int co = i >> 3, j = i & 7;
     float* dst = (j < 7) ? dw + co * 7 + j : db + co;
     *dst = accumulate ? *dst + s : s;
@@ -640,14 +627,14 @@ int wm_stem_fwd(const float* s, const float* w, const float* bias, float* y, int
 }
 
 #ifndef WM_STEM_WGS_PER_CU
-#define WM_STEM_WGS_PER_CU 2      // 75 KB of LDS per workgroup: two fit a CU, one's matrix phase runs under the other's loads / ds phase
+#define WM_STEM_WGS_PER_CU 2      // 71 KB of LDS per workgroup: two fit a CU, one's matrix phase runs under the other's loads / ds phase
 #endif
 // partial: >= 512*512 floats of scratch.  ds may be NULL (Generator stem: the clip is data); only clips [0, nds) get a ds row
 // (Detector stem: the clean half of [watermarked; clean] needs no input gradient).
 int wm_stem_bwd(const float* g, const float* s, const float* w, float* ds, float* partial, float* dw, float* db, int B,
                 int T, int nds, int accumulate, hipStream_t stream) {
     if (T & 3) return (int)hipErrorInvalidValue;
-    constexpr size_t lds = (size_t)(64 * 264 + 296 + 512 + 4 * 256) * sizeof(float);
+    constexpr size_t lds = (size_t)(64 * 264 + 296 + 4 * 256) * sizeof(float);
     static wm::DevOnce attr_done;
     if (!wm::dev_done(attr_done)) {
         WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -657,7 +644,7 @@ int wm_stem_bwd(const float* g, const float* s, const float* w, float* ds, float
     const int grid = ntiles < WM_STEM_WGS_PER_CU * kNumCU ? ntiles : WM_STEM_WGS_PER_CU * kNumCU;
     hipLaunchKernelGGL(stem_bwd_kernel, dim3(grid), dim3(256), lds, stream, g, s, w, ds, partial, B, T, nds);
     WM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stem_reduce_kernel, dim3(2), dim3(256), 0, stream, (const float*)partial, grid, dw, db, accumulate);
+    hipLaunchKernelGGL(stem_reduce_kernel, dim3(8), dim3(1024), 0, stream, (const float*)partial, grid, dw, db, accumulate);
     WM_CHECK_LAUNCH();
     return 0;
 }

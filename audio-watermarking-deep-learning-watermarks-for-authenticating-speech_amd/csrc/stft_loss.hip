@@ -203,15 +203,6 @@ __global__ void ola_gather_kernel(const float* __restrict__ gframes, float* __re
     dsig[i] = accumulate ? dsig[i] + acc : acc;
 }
 
-// out[0] = scale * sum(partial[0..n))   (double accumulation, one block)
-__global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ partial, int n, double scale, float* out) {
-    __shared__ double scratch[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
-    s = block_sum_d<4>(s, scratch);
-    if (threadIdx.x == 0) out[0] = (float)(s * scale);
-}
-
 template <int LOGN, int MODE>
 int launch_stft(const StftArgs& p, int B, hipStream_t stream) {
     constexpr int N = 1 << LOGN, NB = N / 2 + 1;
@@ -236,8 +227,8 @@ int wm_mel_loss(const float* clean, const float* wm, const float* fb, const int*
     StftArgs p{clean, wm, dsig ? gframes : nullptr, partial, fb, klo, khi, mlo, (float)(1.0 / count), 0.f, 0, T, F, hop};
     int rc = launch_stft<10, MODE_MEL>(p, B, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, B * F, 1.0 / count, loss_out);
-    WM_CHECK_LAUNCH();
+    rc = wm::launch_sum_scale2(partial, B * F, 1.0 / count, loss_out, stream);     // fp64, fixed order (csrc/losses.hip)
+    if (rc) return rc;
     if (dsig) {
         hipLaunchKernelGGL(ola_gather_kernel, dim3((B * T + 255) / 256), dim3(256), 0, stream, (const float*)gframes, dsig, N, hop, F, T, B * T, 0);
         WM_CHECK_LAUNCH();
@@ -253,8 +244,8 @@ int wm_loud_loss(const float* clean, const float* wm, float thresh, float* gfram
     StftArgs p{clean, wm, dsig ? gframes : nullptr, partial, nullptr, nullptr, nullptr, nullptr, (float)(1.0 / count), thresh, 0, T, F, hop};
     int rc = launch_stft<11, MODE_LOUD>(p, B, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, B * F, 1.0 / count, loss_out);
-    WM_CHECK_LAUNCH();
+    rc = wm::launch_sum_scale2(partial, B * F, 1.0 / count, loss_out, stream);     // fp64, fixed order (csrc/losses.hip)
+    if (rc) return rc;
     if (dsig) {
         hipLaunchKernelGGL(ola_gather_kernel, dim3((B * T + 255) / 256), dim3(256), 0, stream, (const float*)gframes, dsig, N, hop, F, T, B * T, 0);
         WM_CHECK_LAUNCH();
@@ -271,8 +262,8 @@ int wm_hf_penalty(const float* delta, int kcut, float* gframes, float* partial, 
     StftArgs p{delta, nullptr, dsig ? gframes : nullptr, partial, nullptr, nullptr, nullptr, nullptr, (float)(1.0 / count), 0.f, kcut, T, F, hop};
     int rc = launch_stft<9, MODE_HF>(p, B, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, B * units, 1.0 / count, loss_out);
-    WM_CHECK_LAUNCH();
+    rc = wm::launch_sum_scale2(partial, B * units, 1.0 / count, loss_out, stream);     // fp64, fixed order (csrc/losses.hip)
+    if (rc) return rc;
     if (dsig) {
         hipLaunchKernelGGL(ola_gather_kernel, dim3((B * T + 255) / 256), dim3(256), 0, stream, (const float*)gframes, dsig, N, hop, F, T, B * T, 0);
         WM_CHECK_LAUNCH();

@@ -30,6 +30,14 @@ inline void dev_mark(DevOnce& d) {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// One 16-byte-aligned ds_read_b128 that stays one.  hipcc narrows a plain float4 LDS load of which not every component is used
+// and merges it with its neighbours: the stem backward's three quads per channel became ds_read_b64 at addresses = 4 (mod 8)
+// plus ds_read2_b32.  With the reads kept whole and aligned (and the taps out of LDS) the Detector's stem_bwd launch went from
+// 0.77 to 0.62 ms.  p points into LDS; the explicit address space keeps the volatile access a DS
+// instruction (through a generic pointer it becomes a flat load).
+typedef const volatile __attribute__((address_space(3))) f32x4 lds_f32x4_t;
+__device__ __forceinline__ f32x4 lds_read4(const float* p) { return *(lds_f32x4_t*)p; }
+
 constexpr int kWave = 64;
 constexpr int kNumCU = 256;          // MI355X: 8 XCD x 32 CU
 
@@ -116,6 +124,39 @@ __device__ __forceinline__ double block_sum_d(double v, double* scratch) {
     return r;
 }
 
+// Column sum of the partial-slab reductions (stem / head / LSTM weight gradients): sum_p partial[p*stride + i] in fp64.
+// A block of NG*64 threads owns 64 consecutive columns i (coalesced over i); part-group g = threadIdx.x >> 6 adds the slabs
+// [g*per, (g+1)*per), per = ceil(nparts / NG), slab p0 + k into accumulator k & 3 (four independent chains, four loads in
+// flight), and thread (0, i) adds the NG group sums from LDS in increasing g.  The grouping depends on nparts alone:
+// bit-reproducible.  Every thread of the block calls it (one barrier inside); the total is returned where g == 0.
+template <int NG>
+__device__ __forceinline__ double column_sum_d(const float* __restrict__ partial, int nparts, size_t stride, int i, bool valid,
+                                               double (&sq)[NG][64]) {
+    const int il = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const int per = (nparts + NG - 1) / NG, p0 = grp * per, p1 = min(p0 + per, nparts);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (valid) {
+        const float* col = partial + i;
+        int p = p0;
+        for (; p + 3 < p1; p += 4) {
+            const float v0 = col[(size_t)p * stride], v1 = col[(size_t)(p + 1) * stride];
+            const float v2 = col[(size_t)(p + 2) * stride], v3 = col[(size_t)(p + 3) * stride];
+            s0 += (double)v0; s1 += (double)v1; s2 += (double)v2; s3 += (double)v3;
+        }
+        if (p < p1) s0 += (double)col[(size_t)p * stride];
+        if (p + 1 < p1) s1 += (double)col[(size_t)(p + 1) * stride];
+        if (p + 2 < p1) s2 += (double)col[(size_t)(p + 2) * stride];
+    }
+    sq[grp][il] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    double s = 0.0;
+    if (grp == 0) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) s += sq[g][il];
+    }
+    return s;
+}
+
 __device__ __forceinline__ float sigmoidf_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // softplus(-|x|) = log1p(e^-|x|) on the hardware transcendentals: u = e^-|x| in (0, 1]; a cubic series below 0.01 (error
@@ -133,7 +174,7 @@ __device__ __forceinline__ float bce_logits_grad(float x, float y, float k) {
     return k * (sg - y);
 }
 
-// out[0] = (float)(scale * sum_i partial[i]) in fp64 and a fixed order, one workgroup (csrc/losses.hip)
+// out[0] = (float)(scale * sum_i partial[i]) in fp64 and a fixed order, one 1024-thread workgroup (csrc/losses.hip)
 int launch_sum_scale2(const float* partial, int n, double scale, float* out, hipStream_t stream);
 
 #ifndef WM_STREAM_NT
