@@ -12,6 +12,8 @@ from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_wa
                         evaluate_unseen_file, generate_watermarked_audio, load_audio, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
                         save_audio,
                         save_audio_float)
+from .quality import stoi
+from . import quality
 from . import checkpoint
 from . import main14b_2
 from . import distributed
@@ -22,4 +24,5 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
            "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "Convolved", "Reverb", "TimeWarp", "echo_ir", "evaluate_robustness",
+           "stoi", "quality",
            "lib", "LIB_PATH"]

@@ -681,14 +681,22 @@ class TimeWarp(torch.nn.Module):
 
 
 @torch.no_grad()
-def evaluate_robustness(generator, detector, batches, attacks, device="cuda", message_bits=16, messages=None):
+def evaluate_robustness(generator, detector, batches, attacks, device="cuda", message_bits=16, messages=None, quality=()):
     """How detection moves under distortions: {name: {"watermarked_prob", "clean_prob", "bit_accuracy", "delta_rms"}} for every entry of
     `attacks` (name -> module on (B, 1, T)) and for "none", the undistorted signal.  Eval mode, no_grad; the Generator runs once per batch,
     every attack is applied to BOTH s + delta and s (the false-positive side: what an attack does to clean audio is half of the answer),
     as one call on their concatenation, and the Detector runs once per attack on the result.  The per-batch reductions are eval_forward's
     and the per-clip values of all batches are pooled and averaged once, as evaluate_batches does (a ragged last batch weighs by its
-    clips).  `messages` (optional list, one tensor per batch) replaces the random draw."""
+    clips).  `messages` (optional list, one tensor per batch) replaces the random draw.
+    `quality=("stoi",)` adds what the attack does to the speech itself, three more keys in every row ("none" included), from ONE
+    ops.stoi call per attack on the same 2B rows against the clean s: "stoi" (the attacked watermarked half), "stoi_attack_only" (the
+    attacked clean half: the gap between the two is what the watermark adds under that attack) and "stoi_rows", the clips pooled --
+    clips with fewer than 30 spectral frames have no score and are left out, not averaged in as the sentinel 1e-5 (NaN when none is
+    left).  STOI assumes time-aligned signals: under TimeWarp it is low by construction and says nothing.  The default, quality=(), is
+    the call as it was."""
     from .step import _eval_reductions
+    from .quality import check_metrics
+    quality = check_metrics(quality)
     if "none" in attacks:
         raise ValueError('attacks: the name "none" is taken by the undistorted row')
     generator.eval(); detector.eval()
@@ -696,6 +704,7 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
             "delta_rms": "delta_rms"}
     named = [("none", None)] + list(attacks.items())
     acc = OrderedDict((name, {k: [] for k in keys}) for name, _ in named)
+    stoi_acc = OrderedDict((name, ([], [])) for name, _ in named)
     for bi, s in enumerate(batches):
         s = s.to(device)
         message = (messages[bi].to(device) if messages is not None else
@@ -703,8 +712,22 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
         delta = postprocess(generator(s, message))
         both = torch.cat([s + delta, s], dim=0)
         for name, attack in named:
-            out = _eval_reductions(detector(both if attack is None else attack(both)), message, delta)
+            attacked = both if attack is None else attack(both)
+            out = _eval_reductions(detector(attacked), message, delta)
             for k, src in keys.items():
                 acc[name][k].append(out[src])
-    return OrderedDict((name, {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in a.items()})
-                       for name, a in acc.items())
+            if "stoi" in quality:
+                B = s.shape[0]
+                d, kept = ops.stoi(torch.cat([s, s], dim=0), attacked, SAMPLE_RATE)
+                scored = (kept[:B] > 30) | torch.isnan(d[:B])                      # the mask is decided on s: one for both halves
+                stoi_acc[name][0].append(d[:B][scored])
+                stoi_acc[name][1].append(d[B:][scored])
+    res = OrderedDict((name, {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in a.items()})
+                      for name, a in acc.items())
+    if "stoi" in quality:
+        for name, (wm_half, clean_half) in stoi_acc.items():
+            pooled = torch.cat(wm_half) if wm_half else torch.empty(0)
+            res[name]["stoi"] = float(pooled.double().mean()) if pooled.numel() else math.nan
+            res[name]["stoi_attack_only"] = float(torch.cat(clean_half).double().mean()) if pooled.numel() else math.nan
+            res[name]["stoi_rows"] = int(pooled.numel())
+    return res

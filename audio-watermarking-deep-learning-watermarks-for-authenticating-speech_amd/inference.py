@@ -347,12 +347,15 @@ def _embed_native(waveform, generator, message_bits, device, messages, max_batch
     return wm.cpu(), up.cpu(), original.cpu()
 
 
-def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None, native_rate=False):
+def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None, native_rate=False,
+                               stoi=False):
     """py/main16.py:977-1066 with one batched Generator call; same result dict.  A path is loaded (and resampled) by
     load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz.
     `native_rate=True`: a path is read by read_audio (its channels, its rate), an in-memory (C, N) waveform is at `orig_freq`; the three
     waveforms come back at that rate with all channels (embed_waveform), `output_file` is written at that rate with all channels, the
-    metrics are taken at that rate (SI-SNR over the channel rows) and the dict gains "sample_rate"."""
+    metrics are taken at that rate (SI-SNR over the channel rows) and the dict gains "sample_rate".
+    `stoi=True` adds metrics["stoi"]: STOI (quality.stoi) of the watermarked against the original waveform, the whole recording as ONE
+    row per channel at the rate the waveforms come back at, averaged over the channels; one upload, one wm_stoi call."""
     if native_rate:
         if isinstance(input_file, (str, os.PathLike)):
             waveform, rate = read_audio(input_file)
@@ -373,9 +376,18 @@ def generate_watermarked_audio(input_file, generator, output_file=None, message_
         save_audio_float(wm, output_file, rate)           # :1051-1055 stores the float waveform as is
     result = {"watermarked_waveform": wm, "delta_waveform": delta, "original_waveform": orig,
               "metrics": {"watermark_rms": watermark_rms, "si_snr_db": si_snr, "power_ratio_db": power_ratio_db}}
+    if stoi:
+        result["metrics"]["stoi"] = _stoi_whole(orig, wm, rate, device)
     if native_rate:
         result["sample_rate"] = rate
     return result
+
+
+def _stoi_whole(original, processed, rate, device):
+    """STOI of a whole (C, N) recording against its original, every channel as one row (the long-row path of wm_stoi), mean over channels"""
+    from . import ops
+    d, _ = ops.stoi(_as_channels(original).to(device), _as_channels(processed).to(device), rate)
+    return float(d.double().mean())
 
 
 @torch.no_grad()
@@ -450,27 +462,32 @@ def _si_snr_rows(s, s_hat, eps=1e-8):
 
 @torch.no_grad()
 def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_bits=16, messages=None, max_batch=256,
-                         orig_freq=None):
+                         orig_freq=None, stoi=False):
     """py/main16.py:1263-1299 with all 1-s segments of the file as one batch: returns (mean clean detection probability,
     mean watermarked detection probability, mean SI-SNR, mean delta RMS) over the segments, or four Nones when the file
     cannot be read (:1264-1267).  A fresh random message per segment (:1287) unless `messages` is given.  Accepts a path
     or an in-memory (1,N) waveform, or a (C,N) one at `orig_freq` (see _ingest).  Per-segment reductions run on the device;
-    four scalars come back."""
+    four scalars come back.
+    `stoi=True`: a fifth element, STOI (quality.stoi) of the whole 16 kHz recording as ONE row, watermarked against original (the
+    reference's baseline variant averages pystoi over the one-second segments instead, py/main14.py:1099-1203); five Nones when the
+    file cannot be read."""
+    nout = 5 if stoi else 4
     if isinstance(filepath, (str, os.PathLike)):
         try:
             waveform, orig_freq = load_audio(filepath), None
         except Exception:
-            return None, None, None, None
+            return (None,) * nout
     else:
         waveform = filepath
     generator.eval(); detector.eval()
-    segs, _, _ = _ingest(waveform, orig_freq, device)
+    segs, remainder, _ = _ingest(waveform, orig_freq, device)
     S = segs.shape[0]
     if S == 0:
-        return (float("nan"),) * 4
+        return (float("nan"),) * nout
     if messages is None:
         messages = torch.randint(0, 2 ** message_bits, (S,), device=device)
     clean, wm, si, rms = [], [], [], []
+    whole = torch.empty(S, 1, segs.shape[2], device=device) if stoi else None       # the watermarked segments, for the one-row STOI
     for i in range(0, S, max_batch):
         seg = segs[i:i + max_batch].to(device)
         delta = generator(seg, messages[i:i + max_batch].to(device))
@@ -480,8 +497,16 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
         clean.append(p[:k]); wm.append(p[k:])
         rms.append(torch.sqrt((delta ** 2).mean(dim=[1, 2])))
         si.append(_si_snr_rows(seg, seg_w))
+        if stoi:
+            whole[i:i + k] = seg_w
     out = torch.stack([torch.cat(v).double().mean() for v in (clean, wm, si, rms)]).cpu()
-    return tuple(float(v) for v in out)
+    res = tuple(float(v) for v in out)
+    if stoi:
+        from . import ops
+        n = (S - 1) * segs.shape[2] + (remainder if remainder else segs.shape[2])     # the recording without the last segment's padding
+        d, _ = ops.stoi(segs.to(device).reshape(1, -1)[:, :n], whole.reshape(1, -1)[:, :n], SAMPLE_RATE)
+        res += (float(d[0]),)
+    return res
 
 
 @torch.no_grad()

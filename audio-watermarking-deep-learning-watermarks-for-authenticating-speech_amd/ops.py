@@ -1856,3 +1856,67 @@ class TimeWarpFn(torch.autograd.Function):
     def backward(ctx, g):
         params, table = ctx.saved_tensors
         return time_warp(g.contiguous(), params, table, adjoint=True, zeros=ctx.dims[0], res=ctx.dims[1]), None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------- STOI
+# Short-time objective intelligibility of rows at 10 kHz (wm_stoi, csrc/stoi.hip; the definition is in include/wm_hip.h): the quality
+# column of the evaluation side.  Nothing is differentiated: a measure, not a loss.
+def stoi_plan(rows, n):
+    """bytes of scratch one wm_stoi launch on (rows, n) needs"""
+    import ctypes
+    for v, name in ((rows, "rows"), (n, "n")):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name}: expected a positive int, got {v!r}")
+    if n > 2 ** 34 or rows * n > 2 ** 46:
+        raise ValueError(f"rows = {rows}, n = {n}: a row may have 2^34 samples and a launch 2^46")
+    need = ctypes.c_longlong(0)
+    lib.wm_stoi_plan(rows, n, ctypes.addressof(need), None)
+    return need.value
+
+
+def _stoi_rows(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: expected dtype torch.float32, got {t.dtype}")
+    if t.dim() == 3 and t.shape[1] == 1:
+        rows = t.reshape(t.shape[0], t.shape[2])
+    elif t.dim() == 2:
+        rows = t
+    elif t.dim() == 1:
+        rows = t[None]
+    else:
+        raise ValueError(f"{name}: expected (B, 1, T), (C, N) or (N,), got shape {tuple(t.shape)}")
+    if rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError(f"{name}: needs at least one row of at least one sample, got shape {tuple(t.shape)}")
+    return rows.contiguous()
+
+
+def stoi(x, y, sample_rate=16000):
+    """STOI of every row of y (the processed signal) against the same row of x (the reference): float32 tensors of equal shape (B, 1, T),
+    (C, N) or (N,) at `sample_rate`.  Returns (d (rows,) float32, kept (rows,) int32) on the inputs' device: the score and the number of
+    frames that survived silent-frame removal.  CUDA tensors: one wm_stoi call, preceded by ONE resample_rows launch on x and y stacked
+    unless sample_rate == 10000.  CPU tensors: the float64 restatement of quality.stoi_rows_host (after the host resampler)."""
+    from .quality import STOI_RATE, stoi_rows_host
+    rate = _rate(sample_rate, "sample_rate")
+    xr, yr = _stoi_rows(x, "x"), _stoi_rows(y, "y")
+    if x.shape != y.shape:
+        raise ValueError(f"x and y: expected equal shapes, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if xr.device != yr.device:
+        raise ValueError(f"x and y: expected one device, got {xr.device} and {yr.device}")
+    rows = xr.shape[0]
+    if not xr.is_cuda:
+        if rate != STOI_RATE:
+            from .inference import _resample_rows_host
+            both = _resample_rows_host(torch.cat([xr, yr], dim=0), rate, STOI_RATE)
+            xr, yr = both[:rows], both[rows:]
+        return stoi_rows_host(xr, yr)
+    if rate != STOI_RATE:
+        both = resample_rows(torch.cat([xr, yr], dim=0), rate, STOI_RATE)
+        xr, yr = both[:rows], both[rows:]
+    n = xr.shape[1]
+    d = _f32(rows, device=xr.device)
+    kept = torch.empty(rows, dtype=torch.int32, device=xr.device)
+    scratch = torch.empty(stoi_plan(rows, n) // 4, dtype=torch.float32, device=xr.device)
+    lib.wm_stoi(_p(xr), _p(yr), _p(d), _p(kept), _p(scratch), rows, n, _stream())
+    return d, kept

@@ -547,6 +547,38 @@ int wm_rir_synth(const float* params, float* h, long long rows, int K, float sam
 int wm_time_warp(const float* x, const float* params, const float* tab, float* y, long long rows, long long n, int zeros, int res,
                  int adjoint, wm_stream_t stream);
 
+/* ---- STOI: short-time objective intelligibility (Taal, Hendriks, Heusdens, Jensen 2011) of a processed signal against its reference ----
+ * replaces the per-segment pystoi.stoi(clean, wm, 16000, extended=False) loop of evaluate_unseen_file (py/main14.py:1099-1203,
+ * py/main16.py:2012-2153) at the rate the measure is defined at.  x (the reference) and y (the processed signal) are (rows, n) fp32 AT
+ * 10 kHz, rows >= 1, 1 <= n <= 2^34, every row pair scored on its own.  EPS = 2^-52.  Extended STOI is not built.
+ *   1 window    w[t] = 0.5 (1 - cos(2 pi (t + 1) / 257)), t = 0..255   (numpy.hanning(258)[1:-1])
+ *   2 frames    frame f starts at 128 f for every f with 128 f < n - 256: F = max(0, ceil((n - 256) / 128)) frames (the bound is strict: a
+ *               row of exactly 256 samples has none);  xf_f[t] = w[t] x[128 f + t], the same for y
+ *   3 silence   decided on x alone: frame f is kept iff ||xf_f|| + EPS > 0.01 (max_g ||xf_g|| + EPS) -- "more than 40 dB below the loudest
+ *               frame" without the logarithm; an all-zero row keeps every frame.  K kept frames with start samples s_0 < ... < s_(K-1);
+ *               they are overlap-added at hop 128 into xs, ys of length 128 (K - 1) + 256:  xs[128 h + t] += w[t] x[s_h + t], ys with the
+ *               same s_h
+ *   4 spectra   frames of xs / ys by rule 2 again: S = K - 1 of them (the last hop has none), windowed by w again, zero-padded to 512,
+ *               one-sided DFT; bins 7..218 are used
+ *   5 bands     J = 15 third-octave bands, band b sums |X[k]|^2 over k in [lo_b, hi_b), the bins nearest to 150 * 2^((2b -+ 1) / 6) Hz on the
+ *               grid k * 10000 / 512:  (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109)
+ *               (109,138) (138,174) (174,219);  X_b[j] = sqrt(sum), the same for Y
+ *   6 segments  S < 30: d = 1e-5, the published sentinel.  Else segment m = 30..S is frames m - 30 .. m - 1; per band and segment, with the
+ *               30-vectors xi, eta:  alpha = ||xi|| / (||eta|| + EPS);  eta' = min(alpha eta, (1 + 10^(15/20)) xi);  the means of xi and
+ *               eta' are removed, each is divided by (its norm + EPS);  rho = <xi, eta'>.  d = the mean of rho over all J (S - 29) pairs
+ *   7 output    d[r] fp32 and kept[r] = K as an int.  An all-zero x or an all-zero y gives exactly d = 0.  A row with a non-finite sample
+ *               anywhere in x or y (or a frame energy beyond fp32) gives d = NaN and kept = 0, for that row only.
+ * Computed in fp32 (csrc/stoi.hip): five launches -- frame norms, the kept-frame list, band magnitudes through one complex 512-point
+ * transform per frame pair (x real, y imaginary), segment correlations, the mean -- all sized for F; K never reaches the host.  No atomics:
+ * a row's bits depend on its samples and n only, never on rows, its place in the batch or the grid; two launches give identical bits.
+ * Whatever the data holds, every index stays inside the row and every loop is capped by F.
+ * scratch: wm_stoi_plan(rows, n) BYTES (host-only query, scratch_bytes is a HOST pointer, stream unused), caller-allocated, contents
+ * unspecified before and after.  x, y, d, kept, scratch may start at any multiple of 4 bytes; inputs are borrowed.
+ * hipErrorInvalidValue before any launch: rows or n out of range, rows * n > 2^46, a null or misaligned pointer, d, kept or scratch
+ * overlapping an input or one another. */
+int wm_stoi_plan(long long rows, long long n, long long* scratch_bytes, wm_stream_t stream);
+int wm_stoi(const float* x, const float* y, float* d, int* kept, void* scratch, long long rows, long long n, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
