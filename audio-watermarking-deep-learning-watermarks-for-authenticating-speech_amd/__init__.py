@@ -1,15 +1,16 @@
 """MI355X-native watermark embed + detect hot path (drop-in for py/main16.py's Generator / Detector /
 delta post-processing / loss stack).  Import name: ``awm_amd`` (see awm_amd.py at the repo root)."""
 from .modules import Detector, Generator, ResBlock, load_state_dict_strip_prefix
-from .losses import (MultiScaleMelLoss, TFLoudnessLoss, clamp_peak, detection_losses, fir_lowpass, high_freq_penalty,
+from .losses import (MultiScaleMelLoss, TFLoudnessLoss, clamp_peak, detection_losses, detection_losses_masked, fir_lowpass, high_freq_penalty,
                      l1_to_zero, limit_rms, postprocess)
 from .step import LOSS_WEIGHTS, forward_losses, train_step, eval_forward
 from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
-from .attacks import Convolved, Distortion, Lowpass, Resampled, Reverb, TimeWarp, TransformCodec, echo_ir, evaluate_robustness
+from .attacks import (Convolved, Distortion, Lowpass, Resampled, Reverb, Splice, TimeWarp, TransformCodec, echo_ir, evaluate_localization,
+                      evaluate_robustness, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
 from . import attacks
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
-                        evaluate_unseen_file, generate_watermarked_audio, load_audio, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
+                        evaluate_unseen_file, generate_watermarked_audio, load_audio, locate_watermark, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
                         save_audio,
                         save_audio_float)
 from .quality import stoi
@@ -24,5 +25,7 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
            "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "Convolved", "Reverb", "TimeWarp", "echo_ir", "evaluate_robustness",
+           "Splice", "evaluate_localization", "row_splice_spans", "splice_rows_host", "pack_labels", "unpack_labels", "detection_losses_masked",
+           "locate_watermark",
            "stoi", "quality",
            "lib", "LIB_PATH"]

@@ -23,12 +23,20 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
                (ops.TimeWarpFn), its backward the same launch with adjoint=True.  No pitch-preserving stretch; survival against real
                players and tapes is unmeasured
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
+  Splice       the EDITING attack, and the only module here with two inputs: spans of the watermarked signal are cut out and replaced by
+               the clean signal, by silence, or by clean audio moved from elsewhere in the same row -- one wm_splice launch
+               (ops.SpliceFn) that also emits the per-sample labels "still watermarked" as a bit mask; its backward passes the
+               gradient where the label is 1.  It is the `tamper=` argument of forward_losses / train_step / eval_forward /
+               evaluate_batches, NOT a `codec=` and not a member of Sequential chains.  Rectangular cuts without a crossfade, "moved"
+               audio from the same row only; whether a model trained with it localises real edits is unmeasured
+  evaluate_localization   IoU, precision, recall and sample accuracy of the per-sample track against Splice's labels, from integer counts
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
 and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws.  The counters (word 0, word 1, row, draw)
-of the six families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
+of the seven families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
 parameters (~0 - 1, ~0), the taps of a synthetic response (k >> 2, ~0 - 1), TimeWarp's speed / shift / flutter (~0 - 2, ~0) and its
-flutter phase (~0 - 3, ~0)."""
+flutter phase (~0 - 3, ~0), and Splice's span j < 8 (~0 - 4 - 2j, ~0) with its shift (~0 - 5 - 2j, ~0), i.e. the first words
+0xFFFFFFFB down to 0xFFFFFFEC."""
 from __future__ import annotations
 
 import math
@@ -678,6 +686,241 @@ class TimeWarp(torch.nn.Module):
     def extra_repr(self):
         return (f"speed={self.speed}, shift_s={self.shift_s}, flutter_hz={self.flutter_hz}, flutter_depth={self.flutter_depth}, "
                 f"zeros={self.zeros}, sample_rate={self.sample_rate}, seed={self.seed}")
+
+
+SPLICE_KINDS = ("original", "silence", "moved")           # the `kind` of a span: 0, 1, 2
+_SPLICE_Q0 = 0xFFFFFFFB                                   # span j: first counter words _SPLICE_Q0 - 2j and _SPLICE_Q0 - 2j - 1, second word ~0
+
+
+def _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence):
+    n = int(n)
+    if not 1 <= n <= ops.SPLICE_MAX_N:
+        raise ValueError(f"n: expected 1 <= n <= 2^24 samples, got {n}")
+    if isinstance(max_spans, bool) or not isinstance(max_spans, (int, np.integer)) or not 1 <= max_spans <= ops.SPLICE_MAX_SPANS:
+        raise ValueError(f"max_spans: expected an int in [1, {ops.SPLICE_MAX_SPANS}], got {max_spans!r}")
+    if not 1 <= int(len_lo) <= int(len_hi) <= n:
+        raise ValueError(f"span lengths: expected 1 <= len_lo <= len_hi <= n = {n} samples, got {len_lo!r} and {len_hi!r}")
+    p = [np.float32(v) for v in (p_span, p_original, p_silence)]
+    if not all(0.0 <= float(v) <= 1.0 for v in p) or float(p[1]) + float(p[2]) > 1.0:
+        raise ValueError(f"probabilities: expected p_span, p_original, p_silence in [0, 1] with p_original + p_silence <= 1 (as float32 "
+                         f"values), got {p_span!r}, {p_original!r}, {p_silence!r}")
+    return n, int(max_spans), int(len_lo), int(len_hi), float(p[0]), float(p[1]), float(p[1]) + float(p[2])
+
+
+def row_splice_spans(seed, draw, rows, n, max_spans=2, p_span=0.5, len_lo=800, len_hi=6400, p_original=1 / 3, p_silence=1 / 3):
+    """The spans wm_splice draws for rows `rows` (an int array of row0 + r) of n samples: per row a list of max_spans tuples
+    (start, L, kind, shift, active), ints and a bool, kind an index into SPLICE_KINDS.  Span j takes the words o0..o3 of the counter
+    (0xFFFFFFFB - 2j, 0xFFFFFFFF, row, draw) and the first word o0' of (0xFFFFFFFA - 2j, 0xFFFFFFFF, row, draw): active iff u(o0) < p_span,
+    L = len_lo + ((v(o1) (len_hi - len_lo + 1)) >> 23), start = (v(o2) (n - L + 1)) >> 23, kind from u(o3) against p_original and
+    p_original + p_silence, shift = 1 + ((v(o0') (n - 1)) >> 23), with v(o) = o >> 9 and u = (v + 0.5) 2^-23.  The probabilities enter as
+    float32 values and are compared in float64, the products are integers: nothing is rounded.  n = 1: "moved" is reported, and acts, as
+    "original".  An inactive span keeps the geometry it drew."""
+    n, max_spans, len_lo, len_hi, p_span, t_original, t_silence = _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence)
+    rows = np.asarray(rows, dtype=np.uint64).reshape(-1)
+    key = _key(seed)
+    out = [[] for _ in rows]
+    for j in range(max_spans):
+        o = philox4x32_10(((_SPLICE_Q0 - 2 * j), 0xFFFFFFFF, rows, int(draw)), key)
+        o2 = philox4x32_10(((_SPLICE_Q0 - 2 * j - 1), 0xFFFFFFFF, rows, int(draw)), key)[0]
+        for i in range(len(rows)):
+            v = [int(o[k][i]) >> 9 for k in range(4)]
+            L = len_lo + ((v[1] * (len_hi - len_lo + 1)) >> 23)
+            start = (v[2] * (n - L + 1)) >> 23
+            u3 = (v[3] + 0.5) * 2.0 ** -23
+            kind = 0 if u3 < t_original else (1 if u3 < t_silence else 2)
+            if n == 1 and kind == 2:
+                kind = 0
+            shift = 1 + (((int(o2[i]) >> 9) * (n - 1)) >> 23)
+            out[i].append((start, L, kind, shift, bool((v[0] + 0.5) * 2.0 ** -23 < p_span)))
+    return out
+
+
+def splice_rows_host(a, b, seed, draw, row0=0, **cut):
+    """wm_splice restated in numpy: a (watermarked) and b (clean) float32 arrays (rows, n); `cut`: row_splice_spans's keywords.  Returns
+    (y float32 (rows, n), labels bool (rows, n)): spans applied in rising j, so the largest active j that holds a sample decides it;
+    y = b (original), +0 (silence) or b[(t + shift) mod n] (moved) there, and a elsewhere; samples are copied, never computed with."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 2 or a.shape != b.shape or a.size == 0:
+        raise ValueError(f"a and b: expected two (rows, n) arrays of one shape, got {a.shape} and {b.shape}")
+    rows, n = a.shape
+    y, labels = a.copy(), np.ones((rows, n), dtype=bool)
+    for r, spans in enumerate(row_splice_spans(seed, draw, int(row0) + np.arange(rows), n, **cut)):
+        for start, L, kind, shift, active in spans:
+            if not active:
+                continue
+            t = np.arange(start, start + L)
+            labels[r, t] = False
+            y[r, t] = b[r, t] if kind == 0 else (np.float32(0.0) if kind == 1 else b[r, (t + shift) % n])
+    return y, labels
+
+
+def pack_labels(labels):
+    """bool (rows, n) -> the mask layout, a uint32 array (rows, ceil(n / 32)): bit j of word w is sample 32 w + j, tail bits zero"""
+    labels = np.asarray(labels, dtype=bool)
+    if labels.ndim != 2:
+        raise ValueError(f"labels: expected a (rows, n) array, got shape {labels.shape}")
+    rows, n = labels.shape
+    W = ops.label_words(n)
+    padded = np.zeros((rows, W * 32), dtype=np.uint64)
+    padded[:, :n] = labels
+    return (padded.reshape(rows, W, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+
+
+def unpack_labels(lab, n):
+    """the mask layout ((rows, ceil(n / 32)) uint32 / int32 array or tensor) -> bool array (rows, n)"""
+    if isinstance(lab, torch.Tensor):
+        lab = lab.detach().cpu().numpy()
+    lab = np.ascontiguousarray(lab)
+    if lab.ndim != 2 or lab.dtype not in (np.uint32, np.int32) or lab.shape[1] != ops.label_words(n):
+        raise ValueError(f"lab: expected a (rows, {ops.label_words(n)}) uint32 or int32 mask for n = {n}, got {lab.dtype} {lab.shape}")
+    words = lab.view(np.uint32)
+    return (((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)) != 0).reshape(lab.shape[0], -1)[:, :int(n)]
+
+
+class Splice(torch.nn.Module):
+    """The editing attack on every row (clip or channel) of a watermarked signal, (B, 1, T), (C, N) or (N,): up to max_spans spans per row,
+    each present with probability p_span, of a length drawn uniformly from length_s (seconds; a number fixes it) at a uniform position, are
+    cut out and replaced -- with probabilities kinds = (original, silence, moved) -- by the same span of the CLEAN signal, by silence, or by
+    clean audio from elsewhere in the same row (a circular shift by 1 .. n - 1 samples).  Where spans overlap the later one wins.
+    forward(watermarked, clean, row0=0) returns (tampered, labels): tampered has the input's shape, labels is the (rows, ceil(n / 32)) int32
+    bit mask "this sample is still watermarked" (bit j of word w is sample 32 w + j, tail bits zero; unpack_labels gives booleans).
+    IT TAKES TWO INPUTS: it is not a `codec=` and does not go into torch.nn.Sequential chains; it is the `tamper=` argument of
+    forward_losses / train_step / eval_forward / evaluate_batches and evaluate_localization, where it comes last, behind any codec, so the
+    labels are exact whatever the codec did to the time axis.
+    Limits: the cuts are rectangular, with no crossfade; "moved" audio comes from the same row only; a span longer than the row is cut to
+    the row's length; WHETHER A MODEL TRAINED WITH IT LOCALISES REAL EDITS IS UNMEASURED.
+    Every forward uses the next `draw`; reset(draw) rewinds; `row0` numbers the first row, so that a batch cut into pieces draws what the
+    whole batch would (row_splice_spans restates the draw).  `last_labels`: the labels of the last call.  The gradient reaches
+    `watermarked` where the label is 1; `clean` is data.  CUDA tensors run wm_splice, one launch each way (ops.SpliceFn); CPU tensors
+    splice_rows_host (forward only)."""
+
+    def __init__(self, max_spans=2, p_span=0.5, length_s=(0.05, 0.4), kinds=(1 / 3, 1 / 3, 1 / 3), seed=0, sample_rate=SAMPLE_RATE):
+        super().__init__()
+        _check_seed_draw(seed)
+        if isinstance(max_spans, bool) or not isinstance(max_spans, int) or not 1 <= max_spans <= ops.SPLICE_MAX_SPANS:
+            raise ValueError(f"max_spans: expected an int in [1, {ops.SPLICE_MAX_SPANS}], got {max_spans!r}")
+        if isinstance(p_span, bool) or not isinstance(p_span, (int, float)) or not 0.0 <= p_span <= 1.0:
+            raise ValueError(f"p_span: expected a probability in [0, 1], got {p_span!r}")
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
+            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+        self.length_s = _pair(length_s, "length_s")
+        if not self.length_s[0] > 0.0:
+            raise ValueError(f"length_s: expected positive lengths, got {length_s!r}")
+        if (not isinstance(kinds, (tuple, list)) or len(kinds) != 3 or
+                not all(isinstance(k, (int, float)) and not isinstance(k, bool) and 0.0 <= k <= 1.0 for k in kinds) or
+                abs(sum(kinds) - 1.0) > 1e-6):
+            raise ValueError(f"kinds: expected three probabilities (original, silence, moved) that sum to 1, got {kinds!r}")
+        self.max_spans, self.p_span, self.kinds, self.seed, self.sample_rate = max_spans, float(p_span), tuple(map(float, kinds)), seed, sample_rate
+        self.len_lo = max(1, int(round(self.length_s[0] * sample_rate)))
+        self.len_hi = max(self.len_lo, int(round(self.length_s[1] * sample_rate)))
+        if self.len_hi > ops.SPLICE_MAX_N:
+            raise ValueError(f"length_s: {self.length_s[1]} s is more than the 2^24 samples a row may have")
+        # the kernel takes float32 probabilities and wants p_original + p_silence <= 1 of THOSE: step p_silence down where rounding broke it
+        po, ps = np.float32(self.kinds[0]), np.float32(self.kinds[1])
+        while float(po) + float(ps) > 1.0:
+            ps = np.nextafter(ps, np.float32(0.0))
+        self.p_original, self.p_silence = float(po), float(ps)
+        self.last_labels = None
+        self.reset()
+
+    def reset(self, draw=0):
+        _check_seed_draw(draw=draw)
+        self.draw = draw
+        return self
+
+    def cut(self, n):
+        """wm_splice's scalars for rows of n samples, row_splice_spans's keywords: the span lengths never exceed the row"""
+        hi = min(self.len_hi, int(n))
+        return dict(max_spans=self.max_spans, p_span=self.p_span, len_lo=min(self.len_lo, hi), len_hi=hi, p_original=self.p_original,
+                    p_silence=self.p_silence)
+
+    def forward(self, watermarked, clean, row0=0):
+        a, rows = _rows_of(watermarked, row0)
+        b = _time_rows(clean, "clean")
+        if a.shape != b.shape or a.device != b.device:
+            raise ValueError(f"watermarked and clean: expected equal shapes on one device, got {tuple(a.shape)} on {a.device} and "
+                             f"{tuple(b.shape)} on {b.device}")
+        n = a.shape[-1]
+        if n > ops.SPLICE_MAX_N:
+            raise ValueError(f"a row may have 2^24 samples, got {n}")
+        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        cut = self.cut(n)
+        if a.is_cuda:
+            y, lab = ops.SpliceFn.apply(a.to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous(),
+                                        tuple(cut[k] for k in ("max_spans", "p_span", "len_lo", "len_hi", "p_original", "p_silence")),
+                                        self.seed, draw, row0)
+        else:
+            y, labels = splice_rows_host(a.detach().to(torch.float32).reshape(rows, n).numpy(),
+                                         b.detach().to(torch.float32).reshape(rows, n).numpy(), self.seed, draw, row0, **cut)
+            y, lab = torch.from_numpy(y).reshape(a.shape), torch.from_numpy(pack_labels(labels).view(np.int32))
+        self.last_labels = lab
+        return y, lab
+
+    def extra_repr(self):
+        return (f"max_spans={self.max_spans}, p_span={self.p_span}, length_s={self.length_s}, kinds={self.kinds}, seed={self.seed}, "
+                f"sample_rate={self.sample_rate}")
+
+
+def _ratio(num, den):
+    return num / den if den else math.nan
+
+
+def localization_metrics(tampered_counts, clean_counts):
+    """evaluate_localization's ratios from the pooled integer counts (tp, fp, fn, tn) of the tampered watermarked half and of the clean
+    half; a ratio with a zero denominator is NaN"""
+    tp, fp, fn, tn = (int(v) for v in tampered_counts)
+    _, cfp, _, ctn = (int(v) for v in clean_counts)
+    total = tp + fp + fn + tn
+    return OrderedDict(iou=_ratio(tp, tp + fp + fn), precision=_ratio(tp, tp + fp), recall=_ratio(tp, tp + fn),
+                       sample_accuracy=_ratio(tp + tn, total), clean_false_positive_rate=_ratio(cfp, cfp + ctn),
+                       watermarked_fraction=_ratio(tp + fn, total))
+
+
+@torch.no_grad()
+def evaluate_localization(generator, detector, batches, tamper, device="cuda", message_bits=16, messages=None, threshold=0.5, codec=None):
+    """Does the per-sample track localise?  Every batch s is watermarked (s_w = s + delta, or codec(s + delta)), tampered (s_t, labels =
+    tamper(s_w, s), a Splice), and the Detector runs on cat([s_t, s]); its prediction sigmoid(logits[:, :, 0]) > threshold is scored against
+    the labels by ops.loc_counts -- integer counts per row on the device, pooled over all batches.  Eval mode, no_grad.  Returns
+      iou = tp / (tp + fp + fn), precision, recall, sample_accuracy     over the tampered watermarked half ("positive" = still watermarked)
+      clean_false_positive_rate = fp / (fp + tn)                         over the clean half, whose labels are all 0
+      watermarked_fraction                                               the share of label 1 in the tampered half
+      bit_accuracy    per clip, every bit decoded as the majority of sigmoid > 0.5 over the samples WITH LABEL 1 only, against the message;
+                      clips without such a sample are left out
+      rows            the clips pooled.
+    A ratio with a zero denominator is NaN.  `messages` (optional list, one tensor per batch) replaces the random draw.  What this
+    measures is agreement with Splice's rectangular cuts; it says nothing about edits made with a crossfade or by another tool."""
+    if not isinstance(tamper, Splice):
+        raise TypeError(f"tamper: expected an attacks.Splice, got {type(tamper).__name__}")
+    generator.eval(); detector.eval()
+    pooled = torch.zeros(2, 4, dtype=torch.int64, device=device)
+    bit_acc, rows = [], 0
+    for bi, s in enumerate(batches):
+        s = s.to(device)
+        B, T = s.shape[0], s.shape[-1]
+        message = (messages[bi].to(device) if messages is not None else
+                   torch.randint(0, 2 ** message_bits, (B,), device=device))
+        s_w = s + postprocess(generator(s, message))
+        if codec is not None:
+            s_w = codec(s_w)
+        s_t, labels = tamper(s_w, s)
+        logits = detector(torch.cat([s_t, s], dim=0))
+        counts = ops.loc_counts(logits, labels, threshold).to(torch.int64)
+        pooled += torch.stack([counts[:B].sum(dim=0), counts[B:].sum(dim=0)])
+        rows += B
+        nbits = logits.shape[-1] - 1
+        if nbits > 0:
+            keep = ((labels[:, :, None] >> torch.arange(32, device=labels.device, dtype=torch.int32)) & 1).reshape(B, -1)[:, :T].bool()
+            n1 = keep.sum(dim=1)
+            votes = ((logits[:B, :, 1:] > 0) & keep[:, :, None]).sum(dim=1)                      # sigmoid(x) > 0.5 is x > 0
+            decoded = 2 * votes > n1[:, None]
+            bits = ((message.unsqueeze(1) & (1 << torch.arange(nbits, device=logits.device))) > 0)
+            bit_acc.append((decoded == bits).float().mean(dim=1)[n1 > 0])
+    pooled = pooled.cpu().tolist()
+    res = localization_metrics(pooled[0], pooled[1])
+    acc = torch.cat(bit_acc) if bit_acc else torch.empty(0)
+    res["bit_accuracy"] = float(acc.double().mean()) if acc.numel() else math.nan
+    res["rows"] = rows
+    return res
 
 
 @torch.no_grad()

@@ -432,6 +432,61 @@ def detect_watermark(input_file, detector, detection_threshold=0.5, visualize=Fa
     return detect_waveform(waveform, detector, detection_threshold, device, orig_freq=orig_freq)
 
 
+def merge_short_runs(bits, min_len):
+    """Runs of equal values of the bool array `bits` as a list of [start, end, value] (end exclusive), after runs shorter than `min_len`
+    samples were merged into their neighbours: while there is more than one run and the shortest is shorter than min_len, the FIRST of
+    the shortest runs takes its neighbours' value (they agree: runs alternate) and the three, or two at an end, become one run."""
+    bits = np.asarray(bits, dtype=bool).reshape(-1)
+    if bits.size == 0:
+        return []
+    edges = np.flatnonzero(bits[1:] != bits[:-1]) + 1
+    starts, ends = np.concatenate([[0], edges]), np.concatenate([edges, [bits.size]])
+    runs = [[int(a), int(b), bool(bits[a])] for a, b in zip(starts, ends)]
+    while len(runs) > 1:
+        lens = [b - a for a, b, _ in runs]
+        i = int(np.argmin(lens))                                        # the first of the shortest
+        if lens[i] >= min_len:
+            break
+        lo, hi = max(i - 1, 0), min(i + 1, len(runs) - 1)
+        runs[lo:hi + 1] = [[runs[lo][0], runs[hi][1], not runs[i][2]]]
+    return runs
+
+
+@torch.no_grad()
+def locate_watermark(waveform_or_path, detector, threshold=0.5, min_len_s=0.02, device="cuda", max_batch=512, orig_freq=None):
+    """WHERE a recording is watermarked: the Detector's per-sample track, thresholded on the device, as intervals in seconds.
+    Returns {"watermarked": [(start_s, end_s), ...], "unmarked": the same, "fraction_watermarked"}: the two lists tile the recording;
+    the fraction is the share of samples whose own prediction is 1, before any merging (NaN for an empty recording).
+    The prediction sigmoid(logits[:, :, 0]) > threshold leaves the device as the packed bit mask of ops.loc_counts -- n / 8 bytes, not
+    the 4n-byte probability track detect_waveform returns -- and runs shorter than min_len_s are merged into their neighbours on the host
+    (merge_short_runs).  A path is read by load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz
+    (see _ingest; the intervals are then in seconds all the same).  The shipped checkpoints were never trained to localise: what
+    this returns for a spliced recording is whatever attacks.evaluate_localization measures, not a promise."""
+    from . import ops
+    from .attacks import unpack_labels
+    if isinstance(min_len_s, bool) or not isinstance(min_len_s, (int, float)) or not math.isfinite(min_len_s) or min_len_s < 0:
+        raise ValueError(f"min_len_s: expected a non-negative number of seconds, got {min_len_s!r}")
+    ops.loc_threshold_logit(threshold)                                  # a bad threshold fails here
+    if isinstance(waveform_or_path, (str, os.PathLike)):
+        waveform, orig_freq = load_audio(waveform_or_path), None
+    else:
+        waveform = waveform_or_path
+    detector.eval()
+    segs, _, waveform = _ingest(waveform, orig_freq, device)
+    S, n, T = segs.shape[0], waveform.shape[1], segs.shape[2]
+    if S == 0 or n == 0:
+        return {"watermarked": [], "unmarked": [], "fraction_watermarked": math.nan}
+    masks = []
+    for i in range(0, S, max_batch):
+        logits = detector(segs[i:i + max_batch].to(device))            # [s,T,1+bits]: stays on the device
+        masks.append(ops.loc_counts(logits, None, threshold, want_pred=True)[1])
+    pred = unpack_labels(torch.cat(masks, dim=0), T).reshape(-1)[:n]
+    out = {"watermarked": [], "unmarked": [], "fraction_watermarked": float(pred.mean())}
+    for a, b, v in merge_short_runs(pred, min_len_s * SAMPLE_RATE):
+        out["watermarked" if v else "unmarked"].append((a / SAMPLE_RATE, b / SAMPLE_RATE))
+    return out
+
+
 @torch.no_grad()
 def detect_prob(file_path, detector, sample_rate=SAMPLE_RATE, device="cuda", max_batch=512, orig_freq=None):
     """py/main16.py:1575-1596: average over the file's 1-s segments of each segment's mean detection probability.  The
@@ -510,11 +565,13 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
 
 
 @torch.no_grad()
-def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None, codec=None):
+def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None, codec=None, tamper=None):
     """evaluate_model (:369-423): the per-batch reductions run on the device (step.eval_forward); the per-clip values of
     all batches are pooled and averaged once, as the reference's np.mean over its extended lists does (so a ragged last
     batch weighs by its clips).  `messages` (optional list, one tensor per batch) replaces the randint draw of :381.
-    `codec` (a codec.PcmCodec): the Detector is evaluated on codec(s + delta), as in main15c's validate_one_epoch."""
+    `codec` (a codec.PcmCodec): the Detector is evaluated on codec(s + delta), as in main15c's validate_one_epoch.
+    `tamper` (an attacks.Splice): the watermarked half is spliced behind the codec (step.eval_forward); the averages are the same ones, so
+    the watermarked probability falls with the share that was cut out -- attacks.evaluate_localization scores the per-sample track."""
     from .step import eval_forward
     generator.eval(); detector.eval()
     keys = {"watermarked_prob": "prob_watermarked", "clean_prob": "prob_clean", "bit_accuracy": "bit_accuracy",
@@ -524,7 +581,8 @@ def evaluate_batches(generator, detector, batches, device="cuda", message_bits=1
         s = s.to(device)
         message = (messages[bi].to(device) if messages is not None else
                    torch.randint(0, 2 ** message_bits, (s.shape[0],), device=device))
-        out = eval_forward(generator, detector, s, message, codec=codec)
+        extra = {} if tamper is None else {"tamper": tamper}
+        out = eval_forward(generator, detector, s, message, codec=codec, **extra)
         for k, src in keys.items():
             acc[k].append(out[src])
     return {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in acc.items()}

@@ -106,6 +106,13 @@ def detection_losses(logits, message):
     return ops.BCEFn.apply(logits, message)
 
 
+def detection_losses_masked(logits, message, labels):
+    """(loc_loss, bce) against per-sample labels: `labels` is the (B, ceil(T / 32)) int32 bit mask "still watermarked" of the watermarked
+    half (attacks.Splice's second output), the clean half has target 0.  loc averages over all 2B * T samples; bce over the samples whose
+    label is 1, since the message can only be decoded where the watermark still is (ops.MaskedBCEFn)."""
+    return ops.MaskedBCEFn.apply(logits, message, labels)
+
+
 def detect_with_losses(detector, x, message, input_grad_rows=None):
     """(logits, loc_loss, bce) for x = cat([s_w, s]): the Detector's one-node form where it has one and it applies
     (modules.Detector.forward_with_losses), else detector(x) followed by detection_losses."""

@@ -1920,3 +1920,134 @@ def stoi(x, y, sample_rate=16000):
     scratch = torch.empty(stoi_plan(rows, n) // 4, dtype=torch.float32, device=xr.device)
     lib.wm_stoi(_p(xr), _p(yr), _p(d), _p(kept), _p(scratch), rows, n, _stream())
     return d, kept
+
+
+# ---------------------------------------------------------------------------------------------- splice attack and localisation
+# wm_splice / wm_splice_bwd, wm_bce_masked_fwd / _bwd and wm_loc_score (csrc/splice.hip; the definitions are in include/wm_hip.h).  Labels
+# travel as bit masks: (rows, ceil(n / 32)) int32 tensors, bit j of word w = sample 32 w + j, 1 = "still watermarked", tail bits zero.
+SPLICE_MAX_SPANS = 8
+SPLICE_MAX_N = 2 ** 24
+
+
+def label_words(n):
+    """words per row of a label mask over n samples"""
+    return (int(n) + 31) // 32
+
+
+def _lab(lab, rows, n, name="lab"):
+    lab = _chk(lab, name, 2, torch.int32)
+    if tuple(lab.shape) != (rows, label_words(n)):
+        raise ValueError(f"{name}: expected a ({rows}, {label_words(n)}) int32 mask for {rows} rows of {n} samples, got shape {tuple(lab.shape)}")
+    return lab
+
+
+class SpliceFn(torch.autograd.Function):
+    """wm_splice on the tape: spans of the watermarked rows `a` replaced by the clean rows `b` (as they are, silenced, or moved within the
+    row), with the spans drawn in the kernel from (seed, draw, row0 + r).  cut = (max_spans, p_span, len_lo, len_hi, p_original,
+    p_silence), the lengths in samples.  Returns (y, lab): y like a, lab the (rows, ceil(n / 32)) int32 label mask, not differentiable.
+    Saved for the backward: lab alone.  da = wm_splice_bwd(dy, lab); b is data and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, cut, seed, draw, row0):
+        a, b = _chk(a, "a"), _chk(b, "b")
+        if a.shape != b.shape or a.device != b.device:
+            raise ValueError(f"a and b: expected equal shapes on one device, got {tuple(a.shape)} on {a.device} and {tuple(b.shape)} on {b.device}")
+        if a.dim() < 1 or a.numel() == 0:
+            raise ValueError(f"a: needs at least one row of at least one sample, got shape {tuple(a.shape)}")
+        n = a.shape[-1]
+        rows = a.numel() // n
+        max_spans, p_span, len_lo, len_hi, p_original, p_silence = cut
+        seed = int(seed) & (2 ** 64 - 1)
+        y = torch.empty_like(a)
+        lab = torch.empty(rows, label_words(n), dtype=torch.int32, device=a.device)
+        lib.wm_splice(_p(a), _p(b), _p(y), _p(lab), rows, n, int(row0), seed - 2 ** 64 if seed >= 2 ** 63 else seed, int(draw), int(max_spans),
+                      float(p_span), int(len_lo), int(len_hi), float(p_original), float(p_silence), _stream())
+        ctx.save_for_backward(lab)
+        ctx.mark_non_differentiable(lab)
+        return y, lab
+
+    @staticmethod
+    def backward(ctx, g, _glab):
+        (lab,) = ctx.saved_tensors
+        g = _chk(g, "grad")
+        n = g.shape[-1]
+        da = torch.empty_like(g)
+        lib.wm_splice_bwd(_p(g), _p(lab), _p(da), g.numel() // n, n, _stream())
+        return da, None, None, None, None, None
+
+
+def splice(a, b, *, max_spans=2, p_span=0.5, len_lo=800, len_hi=6400, p_original=1 / 3, p_silence=1 / 3, seed=0, draw=0, row0=0):
+    """(y, lab) of one wm_splice call on contiguous fp32 CUDA tensors a (watermarked) and b (clean) of one shape, all leading axes rows;
+    the lengths in samples.  Differentiable in a (ops.SpliceFn)."""
+    return SpliceFn.apply(a, b, (max_spans, p_span, len_lo, len_hi, p_original, p_silence), seed, draw, row0)
+
+
+class MaskedBCEFn(torch.autograd.Function):
+    """(loc, bce) of wm_bce_masked_fwd: BCEFn against per-sample labels.  logits (2B, T, 1 + bits), message (B,) int64, lab the (B,
+    ceil(T / 32)) int32 label mask of the watermarked half; the clean half has target 0 throughout.  The bit term averages over the
+    samples whose label is 1 -- their number N1 is counted on the device and stays there for the backward (`count`, a device int64
+    saved with logits, message and lab): no host sync."""
+
+    @staticmethod
+    def forward(ctx, logits, message, lab):
+        logits = _chk(logits, "logits", 3)
+        message = _chk(message, "message", 1, torch.int64)
+        R, T, NO = logits.shape
+        B = message.shape[0]
+        if R != 2 * B:
+            raise ValueError(f"logits must hold [watermarked; clean] = 2*B clips, got {R} for B={B}")
+        lab = _lab(lab, B, T)
+        dev = logits.device
+        part = _f32(3 * R * ((T * NO + 4095) // 4096), device=dev)
+        out = torch.zeros(2, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        lib.wm_bce_masked_fwd(_p(logits), _p(message), _p(lab), _p(part), _p(count), _p(out[0]), _p(out[1]), B, R, T, NO, _stream())
+        ctx.save_for_backward(logits, message, lab, count)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_loc, g_bce):
+        logits, message, lab, count = ctx.saved_tensors
+        R, T, NO = logits.shape
+        gl = g_loc.contiguous().float().reshape(1) if g_loc is not None else torch.zeros(1, device=logits.device)
+        gb = g_bce.contiguous().float().reshape(1) if g_bce is not None else torch.zeros(1, device=logits.device)
+        d = torch.empty_like(logits)
+        lib.wm_bce_masked_bwd(_p(logits), _p(message), _p(lab), _p(count), _p(gl), _p(gb), _p(d), message.shape[0], R, T, NO, _stream())
+        return d, None, None
+
+
+def loc_threshold_logit(threshold):
+    """log(p / (1 - p)) in float64 on the host: the logit the probability threshold p stands for; exactly 0.0 at p = 0.5"""
+    import math
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= threshold <= 1.0:
+        raise ValueError(f"threshold: expected a probability in [0, 1], got {threshold!r}")
+    p = float(threshold)
+    if p == 0.5:
+        return 0.0
+    if p == 0.0:
+        return -math.inf
+    if p == 1.0:
+        return math.inf
+    return math.log(p / (1.0 - p))
+
+
+def loc_counts(logits, lab, threshold=0.5, want_pred=False):
+    """The per-sample prediction sigmoid(logits[r, t, 0]) > threshold, taken as logits[r, t, 0] > log(p / (1 - p)), against the label mask
+    `lab` ((lab_rows, ceil(T / 32)) int32 with lab_rows <= R: rows behind it have label 0; None: every label is 1).  One wm_loc_score
+    launch.  Returns counts (R, 4) int32 = {tp, fp, fn, tn} on the device, exact; with want_pred also pred (R, ceil(T / 32)) int32, the
+    prediction in the mask layout.  NaN logits predict 0."""
+    logits = _chk(logits, "logits", 3)
+    R, T, NO = logits.shape
+    if R < 1 or T < 1 or NO < 1:
+        raise ValueError(f"logits: needs at least one row, one sample and one channel, got shape {tuple(logits.shape)}")
+    thr = loc_threshold_logit(threshold)
+    lab_rows = 0
+    if lab is not None:
+        lab = _chk(lab, "lab", 2, torch.int32)
+        lab_rows = lab.shape[0]
+        if lab_rows < 1 or lab_rows > R or lab.shape[1] != label_words(T):
+            raise ValueError(f"lab: expected (at most {R}, {label_words(T)}) int32, got shape {tuple(lab.shape)}")
+    counts = torch.empty(R, 4, dtype=torch.int32, device=logits.device)
+    pred = torch.empty(R, label_words(T), dtype=torch.int32, device=logits.device) if want_pred else None
+    lib.wm_loc_score(_p(logits), _p(lab), thr, _p(counts), _p(pred), R, T, NO, lab_rows, _stream())
+    return (counts, pred) if want_pred else counts

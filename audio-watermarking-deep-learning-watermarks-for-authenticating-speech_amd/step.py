@@ -15,16 +15,25 @@ _mel = L.MultiScaleMelLoss()
 _loud = L.TFLoudnessLoss()
 
 
-def forward_losses(generator, detector, s, message, codec=None):
+def forward_losses(generator, detector, s, message, codec=None, tamper=None):
     """delta -> post-processing -> detector on cat([s_w, s]) -> the six loss terms and both totals.
-    `codec` (a codec.PcmCodec): the main15c graph -- s_w = codec(s + delta) is what the Detector, mel and loudness see."""
+    `codec` (a codec.PcmCodec): the main15c graph -- s_w = codec(s + delta) is what the Detector, mel and loudness see.
+    `tamper` (an attacks.Splice): the Detector sees cat([s_t, s]) with s_t, labels = tamper(s_w, s) -- the splice comes last, behind any
+    codec -- and loc / bce are taken against the per-sample labels (losses.detection_losses_masked) behind the plain
+    detector(x, input_grad_rows=B): the fused Detector tail hard-codes "row < B => 1" and is not used.  Mel, loudness, l1 and hf see the
+    unspliced signals exactly as without it; `out` gains "labels" and "s_t".  None: the call as it was."""
     B = s.shape[0]
     delta_raw = generator(s, message)                                  # :244
     delta = L.postprocess(delta_raw)                                   # :245-247
     s_w = s + delta                                                    # :248
     if codec is not None:
         s_w = codec(s_w)                                               # main15c: perceptual_postprocess(s + delta)
-    logits, loc, bce = L.detect_with_losses(detector, torch.cat([s_w, s], dim=0), message, input_grad_rows=s.shape[0])   # :249-264
+    if tamper is None:
+        logits, loc, bce = L.detect_with_losses(detector, torch.cat([s_w, s], dim=0), message, input_grad_rows=s.shape[0])   # :249-264
+    else:
+        s_t, labels = tamper(s_w, s)
+        logits = detector(torch.cat([s_t, s], dim=0), input_grad_rows=s.shape[0])
+        loc, bce = L.detection_losses_masked(logits, message, labels)
     l1 = L.l1_to_zero(delta)                                           # :266
     mel = _mel(s, s_w)                                                 # :267
     loud = _loud(s, s_w)                                               # :268
@@ -32,14 +41,19 @@ def forward_losses(generator, detector, s, message, codec=None):
     raw = l1 + mel + loud + loc + bce                                  # :273
     w = LOSS_WEIGHTS
     total = w["l1"] * l1 + w["mel"] * mel + w["loud"] * loud + w["loc"] * loc + w["bce"] * bce + w["hf"] * hf   # :275-276
-    return total, OrderedDict(delta_raw=delta_raw, delta=delta, s_w=s_w, logits=logits, l1=l1, mel=mel, loud=loud, loc=loc,
-                              bce=bce, hf=hf, raw_total=raw, total=total)
+    out = OrderedDict(delta_raw=delta_raw, delta=delta, s_w=s_w, logits=logits, l1=l1, mel=mel, loud=loud, loc=loc,
+                      bce=bce, hf=hf, raw_total=raw, total=total)
+    if tamper is not None:
+        out["labels"], out["s_t"] = labels, s_t
+    return total, out
 
 
-def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec=None):
+def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec=None, tamper=None):
     """the step around a model family's forward_losses: zero_grad, forward, backward, gradient sync, message-id check, update.
-    `codec` is handed to forward_losses only when given (a family without one keeps its signature)."""
+    `codec` and `tamper` are handed to forward_losses only when given (a family without them keeps its signature)."""
     extra = {} if codec is None else {"codec": codec}
+    if tamper is not None:
+        extra["tamper"] = tamper
     optimizer.zero_grad(set_to_none=not hasattr(optimizer, "flat"))
     if hasattr(grad_sync, "begin_step"):
         grad_sync.begin_step()
@@ -61,11 +75,12 @@ def _train_step(forward_losses, generator, detector, optimizer, s, message, grad
     return out
 
 
-def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec=None):
+def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec=None, tamper=None):
     """One iteration of train_one_epoch's loop body (:242-278): zero_grad, forward, backward, optimizer step.
     `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce.
-    `codec` (a codec.PcmCodec): main15c's step, see forward_losses."""
-    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec)
+    `codec` (a codec.PcmCodec): main15c's step, see forward_losses.  `tamper` (an attacks.Splice): the splice attack with per-sample
+    labels, see forward_losses."""
+    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec, tamper)
 
 
 def _eval_reductions(logits, message, delta):
@@ -79,13 +94,15 @@ def _eval_reductions(logits, message, delta):
 
 
 @torch.no_grad()
-def eval_forward(generator, detector, s, message, codec=None):
+def eval_forward(generator, detector, s, message, codec=None, tamper=None):
     """evaluate_model's per-batch quantities (:383-403).  In eval mode BatchNorm uses running statistics, so the Detector's
     rows are independent: the clean half D(s) does not wait for the Generator -- it is queued for the side stream and released
     when the Generator reaches its latency-bound LSTM (B clips keep only B of the 256 CUs busy there), and the two halves are
     concatenated afterwards (bit-identical to the single 2B-row call).
     `codec` (a codec.PcmCodec): the Detector sees codec(s + delta), as in main15c's validate_one_epoch, on both branches; the processed
-    signal is returned as "s_w"."""
+    signal is returned as "s_w".
+    `tamper` (an attacks.Splice): the Detector's watermarked half is s_t, labels = tamper(s_w, s), the splice behind any codec; the
+    reductions are the same, and "labels" and "s_t" are returned as well."""
     overlap = (not generator.training) and (not detector.training) and s.is_cuda
     box = {}
     if overlap:
@@ -94,14 +111,20 @@ def eval_forward(generator, detector, s, message, codec=None):
         ops._on_side((s,), clean_half)                # queued: released on the side stream when the LSTM launch is reached
     delta = L.postprocess(generator(s, message))
     s_w = s + delta if codec is None else codec(s + delta)
+    if tamper is not None:
+        s_t, labels = tamper(s_w, s)
+    else:
+        s_t = s_w
     if overlap:
-        lg_wm = detector(s_w)
+        lg_wm = detector(s_t)
         ops.join_side_stream()                        # (also releases the queue if the Generator had no LSTM call)
         box["lg"].record_stream(torch.cuda.current_stream())
         logits = torch.cat([lg_wm, box["lg"]], dim=0)
     else:
-        logits = detector(torch.cat([s_w, s], dim=0))
+        logits = detector(torch.cat([s_t, s], dim=0))
     out = _eval_reductions(logits, message, delta)
     if codec is not None:
         out["s_w"] = s_w
+    if tamper is not None:
+        out["labels"], out["s_t"] = labels, s_t
     return out

@@ -579,6 +579,59 @@ int wm_time_warp(const float* x, const float* params, const float* tab, float* y
 int wm_stoi_plan(long long rows, long long n, long long* scratch_bytes, wm_stream_t stream);
 int wm_stoi(const float* x, const float* y, float* d, int* kept, void* scratch, long long rows, long long n, wm_stream_t stream);
 
+/* ---- splice attack and localisation: per-sample labels, the detection losses against them, confusion counts ------------------------
+ * the editing attack: part of a watermarked recording is cut out and replaced by unmarked audio, by silence, or by audio moved from
+ * elsewhere in the same recording (the reference ships no code for it; its target is all ones on the watermarked half, py/main16.py:255-258).
+ * LABEL MASKS, shared by the five entry points: lab (rows, W) 32-bit words (declared int*, read as uint32), W = ceil(n / 32); bit j of word w of row r is sample 32 w + j of row
+ *   r; 1 = "still watermarked"; bits at t >= n are zero.  Every mask is formed by wave ballots, one writer per word.
+ * wm_splice: a (the watermarked signal) and b (the clean one) (rows, n) fp32, y (rows, n) fp32 out, lab (rows, W) out; rows >= 1,
+ *   1 <= n <= 2^24, 1 <= max_spans <= 8, 1 <= len_lo <= len_hi <= n (samples), p_span, p_original, p_silence in [0, 1] with
+ *   p_original + p_silence <= 1 (the rest is the probability of "moved"); 0 <= row0, row0 + rows <= 2^32, 0 <= draw < 2^32; seed: any 64 bits.
+ *   Span j < max_spans of row r takes two Philox4x32-10 draws, key (seed low word, seed high word) as wm_distort, counters
+ *     (0xFFFFFFFB - 2j, 0xFFFFFFFF, row0 + r, draw) -> o0..o3   and   (0xFFFFFFFA - 2j, 0xFFFFFFFF, row0 + r, draw) -> o0'
+ *   which no other draw has.  With u(o) = ((o >> 9) + 0.5) * 2^-23 and v(o) = o >> 9:
+ *     active iff u(o0) < p_span                               L     = len_lo + ((v(o1) * (len_hi - len_lo + 1)) >> 23)
+ *     start = (v(o2) * (n - L + 1)) >> 23                     kind  = original if u(o3) < p_original, silence if u(o3) < p_original + p_silence, else moved
+ *     shift = 1 + ((v(o0') * (n - 1)) >> 23)                  (n = 1: moved acts as original)
+ *   the thresholds p_span, p_original and p_original + p_silence in fp64 from the fp32 arguments, the products in 64-bit integers: the
+ *   geometry has no float rounding and a host restatement agrees to the bit.
+ *   Sample t: let j* be the largest active j with start_j <= t < start_j + L_j.  None: y = a[r][t], label bit 1.  Else label bit 0 and
+ *   y = b[r][t] (original) | +0 (silence) | b[r][(t + shift) mod n] (moved).  Values are copied bit for bit; a rectangular cut, no crossfade.
+ *   A sample's bits depend on its row's data, (seed, draw, row0 + r), the scalars and t only: rows [0, R) in one call equal R one-row calls
+ *   with row0 = r; two launches give identical bits.
+ * wm_splice_bwd: da = dy where the label bit is 1, else +0, bit for bit.  b is data: it has no gradient.
+ * Both: one launch, stateless, enqueue-only, no scratch.  Pointers may start at any multiple of 4 bytes; y (da) leaves as 16-byte accesses
+ * wherever a whole aligned group lies inside the row and a, b (dy) are read so where they share that alignment.  IN PLACE IS REFUSED.
+ * hipErrorInvalidValue before any launch: rows, n, row0, draw, max_spans, a length or a probability out of range (NaN included), a null or
+ * misaligned pointer, an output overlapping an input or the other output.
+ *
+ * wm_bce_masked_fwd / _bwd: wm_bce_fwd / wm_bce_bwd against the labels.  logits [R][T][NO], message [B] int64, lab (B, ceil(T / 32)) for rows
+ *   < B; rows >= B have target 0 throughout; shapes and limits of wm_bce_fwd (T * NO < 2^23, R <= 65535), 0 <= B <= R, NO <= 64.
+ *     loc = (1 / (R T)) sum_{r, t} bce(logits[r][t][0], y_rt)                                  y_rt = the label bit for r < B, else 0
+ *     bce = (1 / (N1 (NO - 1))) sum_{r < B, t with label 1, o >= 1} bce(logits[r][t][o], bit_(o-1)(message_r))
+ *   N1 = the number of set label bits (at t < T): the message can only be decoded where the watermark still is.  It is an integer
+ *   popcount, written to count_out (a DEVICE int64) and read from the device by the finish and by the backward call (count): no host
+ *   sync.  N1 = 0: bce = 0 and every bit gradient is +0.  NO = 1 leaves bce_out untouched.
+ *   partial: >= 3 * R * ceil(T*NO / 4096) 32-bit words of scratch (wm_bce_fwd's two float slabs and one of integer counts).
+ *   The fp32 partials per workgroup and their fp64 finish are wm_bce_fwd's, in its order (bit-reproducible run to run); with every label 1
+ *   dlogits equals wm_bce_bwd's bit for bit.  The backward has wm_bce_bwd's expressions with y_rt and the scale 1 / (N1 (NO - 1)).
+ *   hipErrorInvalidValue before any launch: a shape out of range, a null pointer, dlogits overlapping logits.
+ *
+ * wm_loc_score: prediction = logits[r][t][0] > thr_logit (NaN predicts 0) against the label bit of lab (lab_rows, ceil(T / 32)); rows >=
+ *   lab_rows have label 0; lab == NULL: every label is 1.  counts (R, 4) int32 out = {tp, fp, fn, tn}, exact; pred (optional, (R,
+ *   ceil(T / 32)) out): the prediction in the mask layout, tail bits zero.  One launch, one workgroup per row.
+ *   hipErrorInvalidValue before any launch: R, T or NO < 1, lab_rows outside [0, R], a NaN threshold, a null logits or counts. */
+int wm_splice(const float* a, const float* b, float* y, int* lab, long long rows, long long n, long long row0, long long seed,
+              long long draw, int max_spans, float p_span, long long len_lo, long long len_hi, float p_original, float p_silence,
+              wm_stream_t stream);
+int wm_splice_bwd(const float* dy, const int* lab, float* da, long long rows, long long n, wm_stream_t stream);
+int wm_bce_masked_fwd(const float* logits, const long long* message, const int* lab, float* partial, long long* count_out,
+                      float* loc_out, float* bce_out, int B, int R, int T, int NO, wm_stream_t stream);
+int wm_bce_masked_bwd(const float* logits, const long long* message, const int* lab, const long long* count, const float* g_loc,
+                      const float* g_bce, float* dlogits, int B, int R, int T, int NO, wm_stream_t stream);
+int wm_loc_score(const float* logits, const int* lab, float thr_logit, int* counts, int* pred, int R, int T, int NO,
+                 int lab_rows, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
