@@ -33,10 +33,7 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
 
 The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
 and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws.  The counters (word 0, word 1, row, draw)
-of the seven families never meet: samples (t >> 2, 0), Distortion's and TransformCodec's parameters (~0, ~0), Reverb's and Convolved's
-parameters (~0 - 1, ~0), the taps of a synthetic response (k >> 2, ~0 - 1), TimeWarp's speed / shift / flutter (~0 - 2, ~0) and its
-flutter phase (~0 - 3, ~0), and Splice's span j < 8 (~0 - 4 - 2j, ~0) with its shift (~0 - 5 - 2j, ~0), i.e. the first words
-0xFFFFFFFB down to 0xFFFFFFEC."""
+of the families never meet: FAMILIES below is their one list, and a new attack takes a new row of it."""
 from __future__ import annotations
 
 import math
@@ -52,11 +49,19 @@ from .losses import postprocess
 
 NOISE_GRAD_MODES = ("through", "detached")
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-_PARAM_Q = 0xFFFFFFFFFFFFFFFF        # the counter words (q low, q high) of a row's parameters: no sample has them (n <= 2^34)
-_PARAM2_Q = 0xFFFFFFFFFFFFFFFE       # the same for Reverb's and Convolved's parameters
-_WARP_Q = 0xFFFFFFFFFFFFFFFD         # TimeWarp's speed, shift, flutter rate and flutter depth
-_WARP_PHASE_Q = 0xFFFFFFFFFFFFFFFC   # TimeWarp's flutter phase
-_RIR_HIGH = 0xFFFFFFFE               # the second counter word of a synthetic response's taps (the first is k >> 2 < 2^12)
+# The counter families: name -> (word 0, word 1) of the Philox counter (word 0, word 1, row, draw).  None is a word that counts: t >> 2 of
+# a row's samples (n <= 2^34, so below 2^32) and k >> 2 of a response's taps (below 2^12).  No two families share a counter, and
+# csrc/distort.hip and csrc/splice.hip spell the same words.
+FAMILIES = {
+    "sample": (None, 0),                        # Distortion's noise
+    "rir_tap": (None, 0xFFFFFFFE),              # the taps of Reverb's synthetic responses
+    "param": (0xFFFFFFFF, 0xFFFFFFFF),          # o0..o2: Distortion's gain, SNR and noise coin; o3: TransformCodec's SNR
+    "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry
+    "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
+    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase
+    **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
+    **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
+}
 
 
 def philox4x32_10(counter, key):
@@ -85,17 +90,30 @@ def _key(seed):
     return seed & 0xFFFFFFFF, seed >> 32
 
 
+def _words(family, seed, draw, rows, count=None):
+    """The four Philox output words of `family` for the rows `rows` (an int or an int array of row0 + r) of (seed, draw); count: the values
+    of the word that counts, for the families that have one"""
+    w0, w1 = FAMILIES[family]
+    return philox4x32_10((count if w0 is None else w0, w1, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
+
+
+def _affine(pair, u):
+    """fmaf(high - low, u, low) as the kernels form it: float32 bounds, the product exact in float64, one rounding to float32"""
+    lo, hi = (np.float32(v) for v in pair)
+    return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
+
+
 def normal_noise(seed, draw, row, n):
-    """z(seed, draw, row, t) for t < n as a float64 array: counter (q low, q high, row, draw) with q = t >> 2, key (seed low, seed high);
+    """z(seed, draw, row, t) for t < n as a float64 array: counter (q, 0, row, draw) with q = t >> 2, key (seed low, seed high);
     words (o0, o1) give sqrt(-2 ln u(o0)) * (cos, sin)(2 pi u(o1)) for samples 4q and 4q+1, (o2, o3) the same for 4q+2 and 4q+3."""
-    return _normals(seed, draw, row, n, None)
+    return _normals(seed, draw, row, n, "sample")
 
 
-def _normals(seed, draw, row, n, high):
-    """normal_noise with the second counter word replaced by `high` (None: q's own high word)"""
+def _normals(seed, draw, row, n, family):
+    """normal_noise from the counting family `family`: "sample" or "rir_tap" """
     n = int(n)
     q = np.arange((n + 3) // 4, dtype=np.uint64)
-    o = philox4x32_10((q, q >> np.uint64(32) if high is None else high, int(row), int(draw)), _key(seed))
+    o = _words(family, seed, draw, int(row), q)
     z = np.empty((len(q), 4), dtype=np.float64)
     for p in (0, 1):
         rad, th = np.sqrt(-2.0 * np.log(_unit(o[2 * p]))), 2.0 * math.pi * _unit(o[2 * p + 1])
@@ -105,12 +123,8 @@ def _normals(seed, draw, row, n, high):
 
 def row_parameters(seed, draw, rows, bounds):
     """(gain_db, snr_db, noisy) of rows `rows` (an int array of row0 + r), as the kernel draws them: float32 arrays and a bool array"""
-    gain_lo, gain_hi, snr_lo, snr_hi, p_noise = (np.float32(v) for v in bounds)
-    o = philox4x32_10((_PARAM_Q & 0xFFFFFFFF, _PARAM_Q >> 32, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
-
-    def affine(lo, hi, u):                                                        # fmaf(hi - lo, u, lo): the product is exact in float64
-        return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
-    return affine(gain_lo, gain_hi, _unit(o[0])), affine(snr_lo, snr_hi, _unit(o[1])), _unit(o[2]) < np.float64(p_noise)
+    bounds, o = tuple(bounds), _words("param", seed, draw, rows)
+    return _affine(bounds[0:2], _unit(o[0])), _affine(bounds[2:4], _unit(o[1])), _unit(o[2]) < np.float64(np.float32(bounds[4]))
 
 
 def _pair(v, name):
@@ -123,7 +137,32 @@ def _pair(v, name):
     return float(lo), float(hi)
 
 
-class Distortion(torch.nn.Module):
+class _RowDraws(torch.nn.Module):
+    """What the per-row random modules share: `seed`, the running `draw` with reset(draw), the numbering of rows from `row0`, and the
+    step to the next draw.  A forward checks its arguments first and steps last, so a call that raises consumes no draw."""
+
+    def __init__(self, seed):
+        super().__init__()
+        self.seed = ops._chk_int(seed, "seed", what="an int")
+        self.reset()
+
+    def reset(self, draw=0):
+        self.draw = ops._chk_int(draw, "draw", 0, 2 ** 32 - 1, "an int in [0, 2^32)")
+        return self
+
+    def _rows(self, x, row0):
+        """x as time rows and their number; row0 + rows must stay a row counter"""
+        x = _time_rows(x, "x")
+        rows = x.numel() // x.shape[-1]
+        ops._chk_int(row0, "row0", 0, 2 ** 32 - rows, "an int with 0 <= row0 and row0 + rows <= 2^32")
+        return x, rows
+
+    def _next_draw(self):
+        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        return draw
+
+
+class Distortion(_RowDraws):
     """y = g x + s z for every row (clip or channel) of x, (B, 1, T), (C, N) or (N,):  g = 10^(gain_db / 20) with gain_db drawn uniformly
     from the pair `gain_db` per row, z white Gaussian noise at an SNR of snr_db (drawn from the pair `snr_db`) against g x, added to a row with
     probability p_noise.  A number in place of a pair fixes the value; snr_db=None: no noise.  No clamping: chain a PcmCodec for saturation.
@@ -134,36 +173,24 @@ class Distortion(torch.nn.Module):
     gradient is g * dy.  CUDA tensors run the kernel; CPU tensors a numpy restatement of the same definition (forward only)."""
 
     def __init__(self, gain_db=(-6, 6), snr_db=(20, 40), p_noise=1.0, seed=0, noise_grad="through"):
-        super().__init__()
         if noise_grad not in NOISE_GRAD_MODES:
             raise ValueError(f"noise_grad must be one of {NOISE_GRAD_MODES}, got {noise_grad!r}")
         if isinstance(p_noise, bool) or not isinstance(p_noise, (int, float)) or not 0.0 <= p_noise <= 1.0:
             raise ValueError(f"p_noise: expected a probability in [0, 1], got {p_noise!r}")
-        if isinstance(seed, bool) or not isinstance(seed, int):
-            raise ValueError(f"seed: expected an int, got {seed!r}")
+        super().__init__(seed)
         self.gain_db = _pair(gain_db, "gain_db")
         self.snr_db = None if snr_db is None else _pair(snr_db, "snr_db")
         self.p_noise = float(p_noise) if snr_db is not None else 0.0
-        self.seed, self.noise_grad = seed, noise_grad
+        self.noise_grad = noise_grad
         self.last_stat = None
-        self.reset()
-
-    def reset(self, draw=0):
-        if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
-            raise ValueError(f"draw: expected an int in [0, 2^32), got {draw!r}")
-        self.draw = draw
-        return self
 
     @property
     def bounds(self):
         return (*self.gain_db, *(self.snr_db or (0.0, 0.0)), self.p_noise)
 
     def forward(self, x, row0=0):
-        x = _time_rows(x, "x")
-        rows = x.numel() // x.shape[-1]
-        if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 <= 2 ** 32 - rows:
-            raise ValueError(f"row0: expected an int with 0 <= row0 and row0 + rows <= 2^32, got {row0!r}")
-        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        x, _ = self._rows(x, row0)
+        draw = self._next_draw()
         if x.is_cuda:
             y, stat = ops.DistortFn.apply(x.to(torch.float32), self.bounds, self.seed, draw, row0, self.noise_grad == "through")
         else:
@@ -261,9 +288,7 @@ def row_snr_db(seed, draw, rows, snr_db):
     """TransformCodec's per-row quality for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the counter
     Distortion draws a row's parameters from -- the word Distortion leaves unused, so the two never share a number -- mapped onto the pair
     snr_db as fmaf(high - low, u, low)"""
-    lo, hi = (np.float32(v) for v in snr_db)
-    o = philox4x32_10((_PARAM_Q & 0xFFFFFFFF, _PARAM_Q >> 32, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
-    return (np.float64(hi - lo) * _unit(o[3]) + np.float64(lo)).astype(np.float32)
+    return _affine(snr_db, _unit(_words("param", seed, draw, rows)[3]))
 
 
 def code_entropy_kbps(codes, band, kcut, hop, sample_rate):
@@ -284,7 +309,7 @@ def code_entropy_kbps(codes, band, kcut, hop, sample_rate):
     return bits_per_frame * sample_rate / hop / 1000.0
 
 
-class TransformCodec(torch.nn.Module):
+class TransformCodec(_RowDraws):
     """A STAND-IN for lossy compression on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the signal path MP3 / AAC-like
     codecs share -- lapped MDCT at hop `hop`, per band of `band` coefficients a uniform quantiser whose step sits snr_db below the band's
     own level (noise shaped like the spectrum, weak coefficients fall into the dead zone; never finer than the 16-bit grid), an optional
@@ -298,37 +323,26 @@ class TransformCodec(torch.nn.Module):
     float32 numpy restatement of the definition (forward only)."""
 
     def __init__(self, snr_db=(10, 30), bandwidth_hz=None, hop=256, band=8, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
-        super().__init__()
         if grad not in ops.MDCT_GRAD_MODES:
             raise ValueError(f"grad must be one of {ops.MDCT_GRAD_MODES}, got {grad!r}")
-        if isinstance(seed, bool) or not isinstance(seed, int):
-            raise ValueError(f"seed: expected an int, got {seed!r}")
+        super().__init__(seed)
         self.snr_db = _pair(snr_db, "snr_db")
         if not 0.0 <= self.snr_db[0] <= self.snr_db[1] <= 60.0:
             raise ValueError(f"snr_db: expected values in [0, 60], got {snr_db!r}")
         self.kcut = ops.mdct_kcut(hop, band, bandwidth_hz, sample_rate)           # bad hops, bands and bandwidths fail here
         self.hop, self.band, self.bandwidth_hz, self.sample_rate = hop, band, bandwidth_hz, sample_rate
         self.floor_step = ops.mdct_default_floor_step(hop)
-        self.seed, self.grad = seed, grad
+        self.grad = grad
         self.last_snr_db = None
-        self.reset()
 
-    def reset(self, draw=0):
-        if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
-            raise ValueError(f"draw: expected an int in [0, 2^32), got {draw!r}")
-        self.draw = draw
-        return self
-
-    def _rows(self, x, row0):
-        x = _time_rows(x, "x")
-        rows = x.numel() // x.shape[-1]
-        if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 <= 2 ** 32 - rows:
-            raise ValueError(f"row0: expected an int with 0 <= row0 and row0 + rows <= 2^32, got {row0!r}")
+    def _snr(self, x, row0):
+        """x as time rows and the per-row quality of the CURRENT draw, which it does not advance"""
+        x, rows = self._rows(x, row0)
         return x, torch.from_numpy(row_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
 
     def forward(self, x, row0=0):
-        x, snr = self._rows(x, row0)
-        self.draw = (self.draw + 1) % 2 ** 32
+        x, snr = self._snr(x, row0)
+        self._next_draw()
         if x.is_cuda:
             y = ops.MdctCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.hop, self.band, self.kcut, self.floor_step, self.grad)
         else:
@@ -363,7 +377,7 @@ class TransformCodec(torch.nn.Module):
         """An ESTIMATE of the bitrate this setting costs on x, in kbit/s per row-second: code_entropy_kbps of the codes the current draw
         gives (the draw is not advanced).  First-order entropy per band index plus 8 bits per band per frame for the step; no entropy
         coder is run.  It relates snr_db to a bitrate and says nothing about what an MP3 / AAC encoder would spend."""
-        x, snr = self._rows(x, row0)
+        x, snr = self._snr(x, row0)
         if x.is_cuda:
             codes = ops.mdct_codec(x.detach().to(torch.float32), snr.to(x.device), hop=self.hop, band=self.band, kcut=self.kcut,
                                    floor_step=self.floor_step, codes_out=True)[1]
@@ -376,25 +390,17 @@ class TransformCodec(torch.nn.Module):
                 f"sample_rate={self.sample_rate}, seed={self.seed}, grad={self.grad!r}")
 
 
-def _param2_words(seed, draw, rows):
-    return philox4x32_10((_PARAM2_Q & 0xFFFFFFFF, _PARAM2_Q >> 32, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
-
-
 def row_reverb_params(seed, draw, rows, rt60, drr_db):
     """Reverb's (rt60, drr_db) of rows `rows` (an int array of row0 + r), two float32 arrays: words o0 and o1 of the counter
     (0xFFFFFFFE, 0xFFFFFFFF, row, draw) -- next to Distortion's parameter counter, met by nothing else -- mapped onto the pairs as
     fmaf(high - low, u, low) in float32"""
-    o = _param2_words(seed, draw, rows)
-
-    def affine(pair, u):
-        lo, hi = (np.float32(v) for v in pair)
-        return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
-    return affine(rt60, _unit(o[0])), affine(drr_db, _unit(o[1]))
+    o = _words("param2", seed, draw, rows)
+    return _affine(rt60, _unit(o[0])), _affine(drr_db, _unit(o[1]))
 
 
 def row_bank_index(seed, draw, rows, entries):
     """Convolved's choice among `entries` responses for rows `rows`: floor(u(o2) * entries) of the same counter, an int64 array"""
-    return np.floor(_unit(_param2_words(seed, draw, rows)[2]) * int(entries)).astype(np.int64)
+    return np.floor(_unit(_words("param2", seed, draw, rows)[2]) * int(entries)).astype(np.int64)
 
 
 def rir_taps(seed, draw, row, rt60, drr_db, K, sample_rate):
@@ -409,7 +415,7 @@ def rir_taps(seed, draw, row, rt60, drr_db, K, sample_rate):
     if K == 1 or not rt60 > 0.0 or not math.isfinite(drr_db):
         return h
     c = 3.0 * math.log(10.0) / (rt60 * float(np.float32(sample_rate)))
-    e = _normals(seed, draw, row, K, _RIR_HIGH) * np.exp(-np.arange(K, dtype=np.float64) * c)
+    e = _normals(seed, draw, row, K, "rir_tap") * np.exp(-np.arange(K, dtype=np.float64) * c)
     e[0] = 0.0
     E = float(np.sum(e * e))
     if not E > 0.0:
@@ -444,22 +450,7 @@ def _conv_rows_host(rows2d, h):
     return F.conv1d(F.pad(rows2d.unsqueeze(0), (K - 1, 0)), w, groups=rows)[0]
 
 
-def _check_seed_draw(seed=0, draw=0):
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError(f"seed: expected an int, got {seed!r}")
-    if isinstance(draw, bool) or not isinstance(draw, int) or not 0 <= draw < 2 ** 32:
-        raise ValueError(f"draw: expected an int in [0, 2^32), got {draw!r}")
-
-
-def _rows_of(x, row0):
-    x = _time_rows(x, "x")
-    rows = x.numel() // x.shape[-1]
-    if isinstance(row0, bool) or not isinstance(row0, int) or not 0 <= row0 <= 2 ** 32 - rows:
-        raise ValueError(f"row0: expected an int with 0 <= row0 and row0 + rows <= 2^32, got {row0!r}")
-    return x, rows
-
-
-class Convolved(torch.nn.Module):
+class Convolved(_RowDraws):
     """y = h * x, causal and cut to the input's length, for every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): lag 0 stays at
     lag 0, so per-sample labels stay aligned.  h: a (K,) impulse response for all rows, or an (R, K) bank of (measured) responses, of which
     row r takes entry floor(u * R), u drawn from (seed, draw, row0 + r) (row_bank_index); K <= 16384.  normalize: every response is
@@ -469,13 +460,12 @@ class Convolved(torch.nn.Module):
     CUDA tensors run wm_fir_rows, one launch each way (ops.FirRowsFn); CPU tensors F.conv1d in float32, differentiable by autograd."""
 
     def __init__(self, h, normalize=False, seed=0):
-        super().__init__()
         if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2) or h.numel() == 0 or not 1 <= h.shape[-1] <= ops.FIR_MAX_TAPS:
             raise ValueError(f"h: expected a (K,) or (R, K) tensor with 1 <= K <= {ops.FIR_MAX_TAPS}, got "
                              f"{tuple(h.shape) if isinstance(h, torch.Tensor) else type(h).__name__}")
         if not isinstance(normalize, bool):
             raise ValueError(f"normalize: expected a bool, got {normalize!r}")
-        _check_seed_draw(seed)
+        super().__init__(seed)
         h = h.detach().to(torch.float64)
         if not bool(torch.isfinite(h).all()):
             raise ValueError("h: expected finite taps")
@@ -485,18 +475,12 @@ class Convolved(torch.nn.Module):
                 raise ValueError("h: a response of zero energy cannot be normalised")
             h = h / energy.sqrt()
         self.register_buffer("h", h.to(torch.float32).contiguous())
-        self.normalize, self.seed = normalize, seed
+        self.normalize = normalize
         self.last_index = None
-        self.reset()
-
-    def reset(self, draw=0):
-        _check_seed_draw(draw=draw)
-        self.draw = draw
-        return self
 
     def forward(self, x, row0=0):
-        x, rows = _rows_of(x, row0)
-        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        x, rows = self._rows(x, row0)
+        draw = self._next_draw()
         h = self.h if self.h.device == x.device else self.h.to(x.device)
         self.last_index = None
         if h.dim() == 2:
@@ -511,7 +495,7 @@ class Convolved(torch.nn.Module):
         return f"h={tuple(self.h.shape)}, normalize={self.normalize}, seed={self.seed}"
 
 
-class Reverb(torch.nn.Module):
+class Reverb(_RowDraws):
     """Synthetic reverberation on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the row convolved (causal, cut to the
     input's length, lag 0 at lag 0) with a response of `taps` samples drawn for it -- a direct tap followed by Gaussian noise whose
     amplitude falls 60 dB in rt60 seconds, at a direct-to-reverberant energy ratio of drr_db and unit total energy (wm_rir_synth in
@@ -525,27 +509,17 @@ class Reverb(torch.nn.Module):
     differentiable by autograd."""
 
     def __init__(self, rt60=(0.1, 0.4), drr_db=(0, 12), taps=2048, sample_rate=SAMPLE_RATE, seed=0):
-        super().__init__()
-        _check_seed_draw(seed)
+        super().__init__(seed)
         self.rt60, self.drr_db = _pair(rt60, "rt60"), _pair(drr_db, "drr_db")
         if not self.rt60[0] > 0.0:
             raise ValueError(f"rt60: expected positive values, got {rt60!r}")
-        if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= ops.FIR_MAX_TAPS:
-            raise ValueError(f"taps: expected an int in [1, {ops.FIR_MAX_TAPS}], got {taps!r}")
-        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
-            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
-        self.taps, self.sample_rate, self.seed = taps, sample_rate, seed
+        self.taps = ops._chk_int(taps, "taps", 1, ops.FIR_MAX_TAPS)
+        self.sample_rate = ops._chk_positive(sample_rate, "sample_rate")
         self.last_params = self.last_ir = None
-        self.reset()
-
-    def reset(self, draw=0):
-        _check_seed_draw(draw=draw)
-        self.draw = draw
-        return self
 
     def forward(self, x, row0=0):
-        x, rows = _rows_of(x, row0)
-        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        x, rows = self._rows(x, row0)
+        draw = self._next_draw()
         rt60, drr = row_reverb_params(self.seed, draw, row0 + np.arange(rows), self.rt60, self.drr_db)
         self.last_params = torch.from_numpy(np.stack([rt60, drr], axis=1))
         x32 = x.to(torch.float32)
@@ -571,18 +545,13 @@ def row_warp_params(seed, draw, rows, speed, shift_s, flutter_hz, flutter_depth,
     float64 and rounded to float32 once each: a = speed, off = shift * sample_rate, w = rate / sample_rate, d = depth a / (2 pi w) with the
     rounded w (0 where w or depth is 0), phi = u, c = min(1, 1 / (a (1 + depth)))."""
     rows = np.asarray(rows, dtype=np.uint64)
-    key = _key(seed)
-    o = philox4x32_10((_WARP_Q & 0xFFFFFFFF, _WARP_Q >> 32, rows, int(draw)), key)
-    phase = _unit(philox4x32_10((_WARP_PHASE_Q & 0xFFFFFFFF, _WARP_PHASE_Q >> 32, rows, int(draw)), key)[0])
-
-    def affine(pair, u):
-        lo, hi = (np.float32(v) for v in pair)
-        return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
+    o = _words("warp", seed, draw, rows)
+    phase = _unit(_words("warp_phase", seed, draw, rows)[0])
     flutter = flutter_hz is not None and flutter_depth is not None
-    a = affine(speed, _unit(o[0])).astype(np.float64)
-    shift = affine(shift_s, _unit(o[1])).astype(np.float64)
-    hz = affine(flutter_hz, _unit(o[2])).astype(np.float64) if flutter else np.zeros(len(rows))
-    depth = affine(flutter_depth, _unit(o[3])).astype(np.float64) if flutter else np.zeros(len(rows))
+    a = _affine(speed, _unit(o[0])).astype(np.float64)
+    shift = _affine(shift_s, _unit(o[1])).astype(np.float64)
+    hz = _affine(flutter_hz, _unit(o[2])).astype(np.float64) if flutter else np.zeros(len(rows))
+    depth = _affine(flutter_depth, _unit(o[3])).astype(np.float64) if flutter else np.zeros(len(rows))
     w = (hz / float(sample_rate)).astype(np.float32)
     on = (w != 0) & (depth != 0)
     d = np.where(on, depth * a / (2.0 * math.pi * np.where(on, w.astype(np.float64), 1.0)), 0.0)
@@ -623,7 +592,7 @@ def _warp_rows_host(x2, params, table, zeros, res):
     return torch.stack(out)
 
 
-class TimeWarp(torch.nn.Module):
+class TimeWarp(_RowDraws):
     """The desynchronising channel on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): y[t] reads x at the position
     p(t) = speed * t + shift + flutter, through a Hann-windowed sinc interpolator of `zeros` zero crossings a side whose cutoff follows the
     speed, so a faster playback does not alias (wm_time_warp in include/wm_hip.h has the definition).  It is a speed change -- tempo and
@@ -644,10 +613,8 @@ class TimeWarp(torch.nn.Module):
     RES = 512
 
     def __init__(self, speed=(0.9, 1.1), shift_s=0.0, flutter_hz=None, flutter_depth=None, zeros=16, sample_rate=SAMPLE_RATE, seed=0):
-        super().__init__()
-        _check_seed_draw(seed)
-        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
-            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+        super().__init__(seed)
+        self.sample_rate = ops._chk_positive(sample_rate, "sample_rate")
         self.speed, self.shift_s = _pair(speed, "speed"), _pair(shift_s, "shift_s")
         if not 0.5 <= self.speed[0] <= self.speed[1] <= 2.0:
             raise ValueError(f"speed: expected values in [0.5, 2], got {speed!r}")
@@ -661,18 +628,12 @@ class TimeWarp(torch.nn.Module):
             if not 0.0 <= self.flutter_depth[0] <= self.flutter_depth[1] <= 0.25:
                 raise ValueError(f"flutter_depth: expected values in [0, 0.25], got {flutter_depth!r}")
         ops.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
-        self.zeros, self.sample_rate, self.seed = zeros, sample_rate, seed
+        self.zeros = zeros
         self.last_params = None
-        self.reset()
-
-    def reset(self, draw=0):
-        _check_seed_draw(draw=draw)
-        self.draw = draw
-        return self
 
     def forward(self, x, row0=0):
-        x, rows = _rows_of(x, row0)
-        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        x, rows = self._rows(x, row0)
+        draw = self._next_draw()
         self.last_params = torch.from_numpy(row_warp_params(self.seed, draw, row0 + np.arange(rows), self.speed, self.shift_s,
                                                             self.flutter_hz, self.flutter_depth, self.sample_rate))
         x2 = x.to(torch.float32).reshape(rows, -1)
@@ -689,7 +650,6 @@ class TimeWarp(torch.nn.Module):
 
 
 SPLICE_KINDS = ("original", "silence", "moved")           # the `kind` of a span: 0, 1, 2
-_SPLICE_Q0 = 0xFFFFFFFB                                   # span j: first counter words _SPLICE_Q0 - 2j and _SPLICE_Q0 - 2j - 1, second word ~0
 
 
 def _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence):
@@ -717,11 +677,9 @@ def row_splice_spans(seed, draw, rows, n, max_spans=2, p_span=0.5, len_lo=800, l
     "original".  An inactive span keeps the geometry it drew."""
     n, max_spans, len_lo, len_hi, p_span, t_original, t_silence = _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence)
     rows = np.asarray(rows, dtype=np.uint64).reshape(-1)
-    key = _key(seed)
     out = [[] for _ in rows]
     for j in range(max_spans):
-        o = philox4x32_10(((_SPLICE_Q0 - 2 * j), 0xFFFFFFFF, rows, int(draw)), key)
-        o2 = philox4x32_10(((_SPLICE_Q0 - 2 * j - 1), 0xFFFFFFFF, rows, int(draw)), key)[0]
+        o, o2 = _words(f"splice_span{j}", seed, draw, rows), _words(f"splice_shift{j}", seed, draw, rows)[0]
         for i in range(len(rows)):
             v = [int(o[k][i]) >> 9 for k in range(4)]
             L = len_lo + ((v[1] * (len_hi - len_lo + 1)) >> 23)
@@ -777,7 +735,7 @@ def unpack_labels(lab, n):
     return (((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)) != 0).reshape(lab.shape[0], -1)[:, :int(n)]
 
 
-class Splice(torch.nn.Module):
+class Splice(_RowDraws):
     """The editing attack on every row (clip or channel) of a watermarked signal, (B, 1, T), (C, N) or (N,): up to max_spans spans per row,
     each present with probability p_span, of a length drawn uniformly from length_s (seconds; a number fixes it) at a uniform position, are
     cut out and replaced -- with probabilities kinds = (original, silence, moved) -- by the same span of the CLEAN signal, by silence, or by
@@ -795,14 +753,11 @@ class Splice(torch.nn.Module):
     splice_rows_host (forward only)."""
 
     def __init__(self, max_spans=2, p_span=0.5, length_s=(0.05, 0.4), kinds=(1 / 3, 1 / 3, 1 / 3), seed=0, sample_rate=SAMPLE_RATE):
-        super().__init__()
-        _check_seed_draw(seed)
-        if isinstance(max_spans, bool) or not isinstance(max_spans, int) or not 1 <= max_spans <= ops.SPLICE_MAX_SPANS:
-            raise ValueError(f"max_spans: expected an int in [1, {ops.SPLICE_MAX_SPANS}], got {max_spans!r}")
+        super().__init__(seed)
+        ops._chk_int(max_spans, "max_spans", 1, ops.SPLICE_MAX_SPANS)
         if isinstance(p_span, bool) or not isinstance(p_span, (int, float)) or not 0.0 <= p_span <= 1.0:
             raise ValueError(f"p_span: expected a probability in [0, 1], got {p_span!r}")
-        if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
-            raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+        ops._chk_positive(sample_rate, "sample_rate")
         self.length_s = _pair(length_s, "length_s")
         if not self.length_s[0] > 0.0:
             raise ValueError(f"length_s: expected positive lengths, got {length_s!r}")
@@ -810,7 +765,7 @@ class Splice(torch.nn.Module):
                 not all(isinstance(k, (int, float)) and not isinstance(k, bool) and 0.0 <= k <= 1.0 for k in kinds) or
                 abs(sum(kinds) - 1.0) > 1e-6):
             raise ValueError(f"kinds: expected three probabilities (original, silence, moved) that sum to 1, got {kinds!r}")
-        self.max_spans, self.p_span, self.kinds, self.seed, self.sample_rate = max_spans, float(p_span), tuple(map(float, kinds)), seed, sample_rate
+        self.max_spans, self.p_span, self.kinds, self.sample_rate = max_spans, float(p_span), tuple(map(float, kinds)), sample_rate
         self.len_lo = max(1, int(round(self.length_s[0] * sample_rate)))
         self.len_hi = max(self.len_lo, int(round(self.length_s[1] * sample_rate)))
         if self.len_hi > ops.SPLICE_MAX_N:
@@ -821,12 +776,6 @@ class Splice(torch.nn.Module):
             ps = np.nextafter(ps, np.float32(0.0))
         self.p_original, self.p_silence = float(po), float(ps)
         self.last_labels = None
-        self.reset()
-
-    def reset(self, draw=0):
-        _check_seed_draw(draw=draw)
-        self.draw = draw
-        return self
 
     def cut(self, n):
         """wm_splice's scalars for rows of n samples, row_splice_spans's keywords: the span lengths never exceed the row"""
@@ -835,7 +784,7 @@ class Splice(torch.nn.Module):
                     p_silence=self.p_silence)
 
     def forward(self, watermarked, clean, row0=0):
-        a, rows = _rows_of(watermarked, row0)
+        a, rows = self._rows(watermarked, row0)
         b = _time_rows(clean, "clean")
         if a.shape != b.shape or a.device != b.device:
             raise ValueError(f"watermarked and clean: expected equal shapes on one device, got {tuple(a.shape)} on {a.device} and "
@@ -843,7 +792,7 @@ class Splice(torch.nn.Module):
         n = a.shape[-1]
         if n > ops.SPLICE_MAX_N:
             raise ValueError(f"a row may have 2^24 samples, got {n}")
-        draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
+        draw = self._next_draw()
         cut = self.cut(n)
         if a.is_cuda:
             y, lab = ops.SpliceFn.apply(a.to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous(),

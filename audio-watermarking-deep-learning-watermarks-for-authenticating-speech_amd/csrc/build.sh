@@ -7,9 +7,10 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 # 16K-instruction limit the compiler silently unrolls by 2 and the register-resident weight fragments land in scratch memory
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -mllvm -pragma-unroll-threshold=100000 ${WM_EXTRA_FLAGS:-}"
 mkdir -p obj
+newest_hpp=$(ls -t *.hpp | head -n 1)            # every object depends on every header
 pids=()
 for f in conv64 bn small_convs lstm postproc stft_loss losses gconv resample biquad distort mdct_codec fir_rows time_warp stoi splice; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ wm_common.hpp -nt obj/$f.o ]; then
+  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ $newest_hpp -nt obj/$f.o ]; then
     $HIPCC $FLAGS -c $f.hip -o obj/$f.o &
     pids+=($!)
   fi

@@ -21,7 +21,7 @@
 // way when they share the output's alignment.  Where the group straddles two quads of the row (row start off a 16-byte boundary) the
 // lane draws both.  Rows without noise skip the generator: they run at the speed of the copy.  No atomics: one writer per element.
 #include <cmath>
-#include "wm_common.hpp"
+#include "wm_draw.hpp"
 using namespace wm;
 
 namespace {
@@ -31,23 +31,7 @@ constexpr int kSeg = 16384;                     // samples of one partial sum
 constexpr int kSegQuads = kSeg / 4;
 constexpr int kTile = kThreads * 4;             // samples a workgroup applies per step
 
-struct Rng { unsigned k0, k1, draw; long long row0; };
 struct Draw { float gain_lo, gain_hi, snr_lo, snr_hi, p_noise; };
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&o)[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// (o >> 9) + 0.5 has 24 bits: exact, and never 0 or 1
-__device__ __forceinline__ float unit(unsigned o) { return ((float)(o >> 9) + 0.5f) * 0x1p-23f; }
 
 // z of samples 4q .. 4q+3 of row `row`: accurate logf / sincospif (2 u_b is exact, so the angle carries no rounding of its own)
 __device__ __forceinline__ void normal_quad(const Rng& g, long long q, unsigned row, float (&z)[4]) {
@@ -62,28 +46,6 @@ __device__ __forceinline__ void normal_quad(const Rng& g, long long q, unsigned 
         z[2 * p + 1] = rad * sn;
     }
 }
-
-// v[e] = p[base + t0 + e] where 0 <= t0 + e < n, else 0; one 16-byte load when `aligned` (the address of p[base + t0] is a multiple of 16)
-// and the four lie inside the row
-__device__ __forceinline__ void load4(const float* __restrict__ p, long long base, long long t0, long long n, bool aligned, float (&v)[4]) {
-    if (aligned && t0 >= 0 && t0 + 4 <= n) {
-        const f32x4 s = *reinterpret_cast<const f32x4*>(p + base + t0);
-        v[0] = s[0]; v[1] = s[1]; v[2] = s[2]; v[3] = s[3];
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (t0 + e >= 0 && t0 + e < n) ? p[base + t0 + e] : 0.f;
-    }
-}
-__device__ __forceinline__ void store4(float* __restrict__ p, long long base, long long t0, long long n, const float (&v)[4]) {
-    if (t0 >= 0 && t0 + 4 <= n) {                                    // the caller's groups are on 16-byte boundaries of p
-        const f32x4 s = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p + base + t0) = s;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (t0 + e >= 0 && t0 + e < n) p[base + t0 + e] = v[e];
-    }
-}
-__device__ __forceinline__ bool aligned16(const float* p, long long i) { return (((uintptr_t)p >> 2) + (unsigned long long)i) % 4 == 0; }
 
 __device__ __forceinline__ float exp10_db(float db) { return db == 0.f ? 1.f : exp10f(__fdiv_rn(db, 20.f)); }   // 0 dB is exactly 1
 
@@ -252,17 +214,10 @@ __global__ __launch_bounds__(kThreads) void rir_synth_kernel(const float* __rest
     }
 }
 
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 bool shape_ok(long long rows, long long n, long long row0, long long draw) {
     return rows >= 1 && n >= 1 && n <= (1ll << 34) && rows <= (1ll << 46) / n && row0 >= 0 && row0 <= (1ll << 32) - rows && draw >= 0 &&
            draw < (1ll << 32);
 }
-
-int grid_for(long long work) { const long long cap = 8ll * kNumCU; return (int)(work < cap ? work : cap); }
 
 }  // namespace
 
@@ -285,7 +240,7 @@ int wm_distort(const float* x, float* y, float* stat, float* scratch, long long 
     if ((uintptr_t)x % 4 || (uintptr_t)y % 4 || (uintptr_t)stat % 4 || (uintptr_t)scratch % 4) return (int)hipErrorInvalidValue;
     const unsigned long long bytes = (unsigned long long)rows * (unsigned long long)n * 4;
     if (overlap(x, bytes, y, bytes)) return (int)hipErrorInvalidValue;            // in place is refused
-    const Rng g{(unsigned)((unsigned long long)seed & 0xffffffffu), (unsigned)((unsigned long long)seed >> 32), (unsigned)draw, row0};
+    const Rng g = make_rng(seed, draw, row0);
     const Draw d{gain_lo, gain_hi, snr_lo, snr_hi, p_noise};
     const long long nseg = (n + kSeg - 1) / kSeg, segs = rows * nseg;
     hipLaunchKernelGGL(distort_sum_kernel<0>, dim3(grid_for(segs)), dim3(kThreads), 0, stream, x, stat, scratch, nullptr, n, nseg, segs, g, d);
@@ -308,7 +263,7 @@ int wm_distort_bwd(const float* dy, const float* x, const float* stat, float* dx
         return (int)hipErrorInvalidValue;
     const unsigned long long bytes = (unsigned long long)rows * (unsigned long long)n * 4;
     if (overlap(dx, bytes, dy, bytes) || overlap(dx, bytes, x, bytes)) return (int)hipErrorInvalidValue;
-    const Rng g{(unsigned)((unsigned long long)seed & 0xffffffffu), (unsigned)((unsigned long long)seed >> 32), (unsigned)draw, row0};
+    const Rng g = make_rng(seed, draw, row0);
     const Draw d{};
     const long long nseg = (n + kSeg - 1) / kSeg, segs = rows * nseg;
     float* coef = through ? scratch + segs : nullptr;                             // behind the segment totals
@@ -334,7 +289,7 @@ int wm_rir_synth(const float* params, float* h, long long rows, int K, float sam
     if (!std::isfinite(sample_rate) || !(sample_rate > 0.f)) return (int)hipErrorInvalidValue;
     if ((uintptr_t)params % 4 || (uintptr_t)h % 4) return (int)hipErrorInvalidValue;
     if (overlap(params, (unsigned long long)rows * 8, h, (unsigned long long)rows * (unsigned long long)K * 4)) return (int)hipErrorInvalidValue;
-    const Rng g{(unsigned)((unsigned long long)seed & 0xffffffffu), (unsigned)((unsigned long long)seed >> 32), (unsigned)draw, row0};
+    const Rng g = make_rng(seed, draw, row0);
     hipLaunchKernelGGL(rir_synth_kernel, dim3(grid_for(rows)), dim3(kThreads), 0, stream, params, h, rows, K, sample_rate, g);
     WM_CHECK_LAUNCH();
     return 0;

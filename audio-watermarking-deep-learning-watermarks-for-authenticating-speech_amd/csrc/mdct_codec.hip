@@ -186,11 +186,6 @@ long long tiles_per_row(long long nb, int NT) { return (nb + 32 * NT - 2) / (32 
 // fit the LDS of a CU side by side)
 int column_tiles(long long nb, int M) { return M <= 256 && 64 * tiles_per_row(nb, 2) <= 32 * tiles_per_row(nb, 1) ? 2 : 1; }
 
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 template <int M, int NT>
 int launch(Args& a, long long nb, hipStream_t stream) {
     static DevOnce done;

@@ -19,7 +19,7 @@
 // N1, the number of set label bits, is counted in integers (per workgroup at channel 0, added by the finish) and stays on the device
 // for the finish and the backward.  A workgroup's label words (at most 128) are staged in LDS once.
 #include <cmath>
-#include "wm_common.hpp"
+#include "wm_draw.hpp"
 using namespace wm;
 
 namespace {
@@ -29,24 +29,8 @@ constexpr int kChunk = 4096;                    // samples of a row one workgrou
 constexpr int kTile = kThreads * 4;
 constexpr int kMaxSpans = 8;
 
-struct Rng { unsigned k0, k1, draw; long long row0; };
 struct Cut { int max_spans, len_lo, len_hi; double p_span, t_original, t_silence; };
 struct Span { int start, end, kind, shift; };   // [start, end) is empty for a span that is not active; kind 0 original | 1 silence | 2 moved
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&o)[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// u = ((o >> 9) + 0.5) 2^-23 as a double: exact, so the comparison with a threshold is the host's
-__device__ __forceinline__ double unit_d(unsigned o) { return ((double)(o >> 9) + 0.5) * 0x1p-23; }
 
 // span j of row `row` (= row0 + r): counters (0xFFFFFFFB - 2j, ~0, row, draw) and (0xFFFFFFFA - 2j, ~0, row, draw)
 __device__ __forceinline__ Span draw_span(const Rng& g, const Cut& c, unsigned row, int j, int n) {
@@ -70,27 +54,6 @@ __device__ __forceinline__ int span_of(const Span* __restrict__ sp, int nsp, int
     int hit = -1;
     for (int j = 0; j < nsp; ++j) hit = (t >= sp[j].start && t < sp[j].end) ? j : hit;
     return hit;
-}
-
-__device__ __forceinline__ bool aligned16(const void* p, long long i) { return (((uintptr_t)p >> 2) + (unsigned long long)i) % 4 == 0; }
-
-__device__ __forceinline__ void load4(const float* __restrict__ p, long long base, int t0, int n, bool aligned, float (&v)[4]) {
-    if (aligned && t0 >= 0 && t0 + 4 <= n) {
-        const f32x4 s = *reinterpret_cast<const f32x4*>(p + base + t0);
-        v[0] = s[0]; v[1] = s[1]; v[2] = s[2]; v[3] = s[3];
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (t0 + e >= 0 && t0 + e < n) ? p[base + t0 + e] : 0.f;
-    }
-}
-__device__ __forceinline__ void store4(float* __restrict__ p, long long base, int t0, int n, const float (&v)[4]) {
-    if (t0 >= 0 && t0 + 4 <= n) {                                      // the caller's groups are on 16-byte boundaries of p
-        const f32x4 s = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p + base + t0) = s;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (t0 + e >= 0 && t0 + e < n) p[base + t0 + e] = v[e];
-    }
 }
 
 // the two words of a wave's 64 predicates (sample t0 + lane, t0 a multiple of 64) into row `lrow` of a mask of W words
@@ -350,16 +313,9 @@ __global__ __launch_bounds__(kThreads) void loc_score_kernel(const float* __rest
     }
 }
 
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 bool rows_ok(long long rows, long long n) { return rows >= 1 && n >= 1 && n <= (1ll << 24) && rows <= (1ll << 46) / n; }
 
 bool prob(float p) { return p >= 0.f && p <= 1.f; }                    // NaN: false
-
-int grid_for(long long work) { const long long cap = 8ll * kNumCU; return (int)(work < cap ? work : cap); }
 
 bool bce_shape_ok(int B, int R, int T, int NO) {
     return R >= 1 && R <= 65535 && B >= 0 && B <= R && T >= 1 && NO >= 1 && NO <= 64 && (long long)T * NO < (1 << 23);
@@ -382,7 +338,7 @@ int wm_splice(const float* a, const float* b, float* y, int* lab_, long long row
     if (overlap(y, bytes, a, bytes) || overlap(y, bytes, b, bytes) || overlap(lab, lbytes, a, bytes) || overlap(lab, lbytes, b, bytes) ||
         overlap(lab, lbytes, y, bytes))
         return (int)hipErrorInvalidValue;                                         // in place is refused
-    const Rng g{(unsigned)((unsigned long long)seed & 0xffffffffu), (unsigned)((unsigned long long)seed >> 32), (unsigned)draw, row0};
+    const Rng g = make_rng(seed, draw, row0);
     const Cut c{max_spans, (int)len_lo, (int)len_hi, (double)p_span, (double)p_original, (double)p_original + (double)p_silence};
     const long long chunks_per_row = (n + kChunk - 1) / kChunk, chunks = rows * chunks_per_row;
     hipLaunchKernelGGL(splice_kernel, dim3(grid_for(chunks)), dim3(kThreads), 0, stream, a, b, y, lab, (int)n, (int)W, chunks_per_row, chunks, g, c);

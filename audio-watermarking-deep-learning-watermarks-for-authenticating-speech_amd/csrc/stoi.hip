@@ -310,11 +310,6 @@ bool plan(long long rows, long long n, Args& a, long long& words) {
 
 unsigned grid_for(long long tiles) { return (unsigned)(tiles < 1 ? 1 : (tiles < kGridCap ? tiles : kGridCap)); }
 
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" {

@@ -140,11 +140,6 @@ __global__ __launch_bounds__(kThreads) void time_warp_kernel(Args a) {
     }
 }
 
-bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" {

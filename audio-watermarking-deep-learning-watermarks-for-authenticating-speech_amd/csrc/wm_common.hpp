@@ -27,6 +27,12 @@ inline void dev_mark(DevOnce& d) {
     d.mask.fetch_or(1ull << (dev & 63), std::memory_order_release);
 }
 
+// host only: do [a, a + na) and [b, b + nb) share a byte?  The launchers refuse in-place calls with it.
+inline bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -7,6 +7,7 @@ block of the reference graph (py/main16.py:112-186, :53-81, :192-217).
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 
 import torch
@@ -37,6 +38,26 @@ def _chk(t: torch.Tensor, name: str, ndim: int | None = None, dtype=torch.float3
     if ndim is not None and t.dim() != ndim:
         raise ValueError(f"{name}: expected {ndim} dims, got shape {tuple(t.shape)}")
     return t.contiguous()
+
+
+def _chk_int(v, name, lo=None, hi=None, what=None):
+    """v where it is an int (bools refused), in [lo, hi] where a range is given; `what` replaces "an int in [lo, hi]" in the message"""
+    if isinstance(v, bool) or not isinstance(v, int) or not (lo is None or lo <= v <= hi):
+        raise ValueError(f"{name}: expected {what or f'an int in [{lo}, {hi}]'}, got {v!r}")
+    return v
+
+
+def _chk_positive(v, name):
+    """v where it is a positive finite number (bools refused)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+    return v
+
+
+def _seed64(seed):
+    """the seed's low 64 bits as the signed value the launchers take (they split it into the key's two halves)"""
+    seed = int(seed) & (2 ** 64 - 1)
+    return seed - 2 ** 64 if seed >= 2 ** 63 else seed
 
 
 def _frames(x: torch.Tensor, name: str, ch: int) -> torch.Tensor:
@@ -1158,7 +1179,6 @@ def _rate(v, name):
 
 def resample_length(n, orig_freq, new_freq):
     """ceil(new * n / orig): the number of samples torchaudio keeps for an input of n"""
-    import math
     g = math.gcd(int(orig_freq), int(new_freq))
     P, Q = int(orig_freq) // g, int(new_freq) // g
     return -((-Q * int(n)) // P)
@@ -1168,7 +1188,6 @@ def resample_table(orig_freq, new_freq):
     """Host tables of one rate pair (cached): P, Q, width, K = 2*width + P, the dense float32 table `dense` (Q, K), and the compact
     one the kernel reads: `taps` (Q, W) with `first` (Q,) int32 such that dense[i, first[i]:first[i]+W] == taps[i] and every other
     entry of dense is 0.0.  W is the longest run of non-zero taps over the phases, made odd where K allows (LDS banks)."""
-    import math
     orig_freq, new_freq = _rate(orig_freq, "orig_freq"), _rate(new_freq, "new_freq")
     key = (orig_freq, new_freq)
     if key in _RESAMPLE_HOST:
@@ -1352,8 +1371,7 @@ def _rows_length(N, orig_freq, new_freq, length):
     full = resample_length(N, orig_freq, new_freq)
     if length is None:
         return full
-    if isinstance(length, bool) or not isinstance(length, int) or not 0 <= length <= full:
-        raise ValueError(f"length: expected an int in [0, {full}] (what {N} samples give), got {length!r}")
+    _chk_int(length, "length", 0, full, f"an int in [0, {full}] (what {N} samples give)")
     return length
 
 
@@ -1403,15 +1421,13 @@ _BIQUAD_PLAN = {}
 def biquad_lowpass_coeffs(sample_rate, cutoff_freq, Q=0.707):
     """(b0, b1, b2, a1, a2) of the low-pass section exactly as inference.lowpass_biquad forms it: float64, divided by a0, each value
     rounded once to float32 (returned as Python floats that hold those float32 values).  Host-only, cached."""
-    import math
     key = (sample_rate, cutoff_freq, Q)
     try:
         return _BIQUAD_COEFFS[key]
     except (KeyError, TypeError):
         pass
     for v, name in ((sample_rate, "sample_rate"), (cutoff_freq, "cutoff_freq"), (Q, "Q")):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
-            raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+        _chk_positive(v, name)
     if 2.0 * float(cutoff_freq) >= float(sample_rate):
         raise ValueError(f"cutoff_freq must lie below half the sample rate, got {cutoff_freq} Hz at {sample_rate} Hz")
     import numpy as np
@@ -1427,7 +1443,6 @@ def biquad_lowpass_coeffs(sample_rate, cutoff_freq, Q=0.707):
 
 
 def _biquad_coeffs(coeffs):
-    import math
     import numpy as np
     try:
         c = tuple(float(v) for v in coeffs)
@@ -1441,7 +1456,6 @@ def _biquad_coeffs(coeffs):
 def biquad_warm(coeffs):
     """the smallest W with r^W <= 2^-40, r the pole radius of 1 / (1 + a1 z^-1 + a2 z^-2): the warm-up after which a recursion started
     from a zero state has forgotten that (0 for a section without poles).  An unstable section (r >= 1) raises ValueError."""
-    import math
     _, _, _, a1, a2 = _biquad_coeffs(coeffs)
     disc = a1 * a1 - 4.0 * a2
     r = math.sqrt(a2) if disc < 0 else (abs(a1) + math.sqrt(disc)) / 2.0
@@ -1561,8 +1575,7 @@ class DistortFn(torch.autograd.Function):
             raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
         n = x.shape[-1]
         rows = x.numel() // n
-        seed = int(seed) & (2 ** 64 - 1)
-        ctx.key = (rows, n, int(row0), seed - 2 ** 64 if seed >= 2 ** 63 else seed, int(draw))
+        ctx.key = (rows, n, int(row0), _seed64(seed), int(draw))
         ctx.through = bool(through)
         y, stat = torch.empty_like(x), _f32(rows, 4, device=x.device)
         lib.wm_distort(_p(x), _p(y), _p(stat), _p(DistortFn._scratch(rows, n, x.device)), *ctx.key, *map(float, bounds), _stream())
@@ -1591,7 +1604,6 @@ MDCT_GRAD_MODES = ("straight_through", "dead_zone")
 def mdct_default_floor_step(hop):
     """2^-15 * sqrt(hop / 2): the coefficient step whose time-domain noise equals the 16-bit grid's (synthesis scales coefficient variance
     by 2 / hop)"""
-    import math
     return 2.0 ** -15 * math.sqrt(hop / 2.0)
 
 
@@ -1611,7 +1623,6 @@ def mdct_plan(n, hop):
 def mdct_kcut(hop, band, bandwidth_hz=None, sample_rate=16000):
     """The first coefficient the bandwidth cut zeroes: floor(bandwidth_hz * 2 hop / sample_rate) rounded down to a multiple of `band`
     (coefficient k sits at (k + 1/2) sample_rate / (2 hop) Hz); None: hop, no cut.  A cut below one band, or above Nyquist, is refused."""
-    import math
     if hop not in MDCT_HOPS:
         raise ValueError(f"hop must be one of {MDCT_HOPS}, got {hop!r}")
     if band not in MDCT_BANDS:
@@ -1619,8 +1630,7 @@ def mdct_kcut(hop, band, bandwidth_hz=None, sample_rate=16000):
     if bandwidth_hz is None:
         return hop
     for v, name in ((bandwidth_hz, "bandwidth_hz"), (sample_rate, "sample_rate")):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
-            raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+        _chk_positive(v, name)
     if 2.0 * bandwidth_hz > sample_rate:
         raise ValueError(f"bandwidth_hz must not lie above half the sample rate, got {bandwidth_hz} Hz at {sample_rate} Hz")
     kcut = int(math.floor(bandwidth_hz * 2 * hop / sample_rate)) // band * band
@@ -1637,7 +1647,6 @@ def mdct_codec(x, snr_db, *, hop=256, band=8, kcut=None, bandwidth_hz=None, samp
     (a (rows,) fp32 CUDA tensor, values in [0, 60]; ignored with quantise=False, where None is allowed) with floor_step (None:
     mdct_default_floor_step(hop)), synthesis with overlap-add.  codes_out: also returns the int16 codes, (rows, mdct_frames(n, hop), hop),
     as (y, codes).  mask_in: an int16 tensor of that shape.  A stand-in for lossy compression; parity with MP3 / AAC is unmeasured."""
-    import math
     x = _chk(x, "x")
     if x.dim() < 1 or x.numel() == 0:
         raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
@@ -1650,8 +1659,7 @@ def mdct_codec(x, snr_db, *, hop=256, band=8, kcut=None, bandwidth_hz=None, samp
         raise ValueError(f"kcut: expected a multiple of band = {band} in [{band}, {hop}], got {kcut!r}")
     if floor_step is None:
         floor_step = mdct_default_floor_step(hop)
-    if isinstance(floor_step, bool) or not isinstance(floor_step, (int, float)) or not math.isfinite(floor_step) or floor_step <= 0:
-        raise ValueError(f"floor_step must be a positive finite number, got {floor_step!r}")
+    _chk_positive(floor_step, "floor_step")
     if codes_out and not quantise:
         raise ValueError("codes_out needs quantise=True: the linear map has no codes")
     n = x.shape[-1]
@@ -1754,21 +1762,16 @@ def rir_synth(params, taps, sample_rate=16000, seed=0, draw=0, row0=0):
     """One launch of wm_rir_synth: (rows, taps) fp32 synthetic room responses from params, a (rows, 2) fp32 CUDA tensor of {rt60 in seconds,
     direct-to-reverberant ratio in dB} per row -- exponentially decaying Gaussian noise behind a direct tap, unit energy, NOT a room
     simulation.  Row r is a function of (seed, draw, row0 + r, params[r], taps, sample_rate) alone."""
-    import math
     params = _chk(params, "params", 2)
     if params.shape[0] < 1 or params.shape[1] != 2:
         raise ValueError(f"params: expected (rows, 2) with at least one row, got shape {tuple(params.shape)}")
-    if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= FIR_MAX_TAPS:
-        raise ValueError(f"taps: expected an int in [1, {FIR_MAX_TAPS}], got {taps!r}")
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate) or sample_rate <= 0:
-        raise ValueError(f"sample_rate must be a positive finite number, got {sample_rate!r}")
+    _chk_int(taps, "taps", 1, FIR_MAX_TAPS)
+    _chk_positive(sample_rate, "sample_rate")
     rows = params.shape[0]
-    for v, name, top in ((draw, "draw", 2 ** 32 - 1), (row0, "row0", 2 ** 32 - rows)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top:
-            raise ValueError(f"{name}: expected an int in [0, {top}], got {v!r}")
-    seed = int(seed) & (2 ** 64 - 1)
+    _chk_int(draw, "draw", 0, 2 ** 32 - 1)
+    _chk_int(row0, "row0", 0, 2 ** 32 - rows)
     h = _f32(rows, taps, device=params.device)
-    lib.wm_rir_synth(_p(params), _p(h), rows, taps, float(sample_rate), row0, seed - 2 ** 64 if seed >= 2 ** 63 else seed, draw, _stream())
+    lib.wm_rir_synth(_p(params), _p(h), rows, taps, float(sample_rate), row0, _seed64(seed), draw, _stream())
     return h
 
 
@@ -1779,9 +1782,8 @@ TIME_WARP_MAX_TABLE = 128 * 1024 // 4           # floats
 
 
 def _time_warp_dims(zeros, res):
-    for v, name, lo, hi in ((zeros, "zeros", 4, 32), (res, "res", 64, 1024)):
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise ValueError(f"{name}: expected an int in [{lo}, {hi}], got {v!r}")
+    _chk_int(zeros, "zeros", 4, 32)
+    _chk_int(res, "res", 64, 1024)
     if res & (res - 1):
         raise ValueError(f"res: expected a power of two, got {res}")
     if zeros * res + 2 > TIME_WARP_MAX_TABLE:
@@ -1865,8 +1867,7 @@ def stoi_plan(rows, n):
     """bytes of scratch one wm_stoi launch on (rows, n) needs"""
     import ctypes
     for v, name in ((rows, "rows"), (n, "n")):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-            raise ValueError(f"{name}: expected a positive int, got {v!r}")
+        _chk_int(v, name, 1, math.inf, "a positive int")
     if n > 2 ** 34 or rows * n > 2 ** 46:
         raise ValueError(f"rows = {rows}, n = {n}: a row may have 2^34 samples and a launch 2^46")
     need = ctypes.c_longlong(0)
@@ -1957,10 +1958,9 @@ class SpliceFn(torch.autograd.Function):
         n = a.shape[-1]
         rows = a.numel() // n
         max_spans, p_span, len_lo, len_hi, p_original, p_silence = cut
-        seed = int(seed) & (2 ** 64 - 1)
         y = torch.empty_like(a)
         lab = torch.empty(rows, label_words(n), dtype=torch.int32, device=a.device)
-        lib.wm_splice(_p(a), _p(b), _p(y), _p(lab), rows, n, int(row0), seed - 2 ** 64 if seed >= 2 ** 63 else seed, int(draw), int(max_spans),
+        lib.wm_splice(_p(a), _p(b), _p(y), _p(lab), rows, n, int(row0), _seed64(seed), int(draw), int(max_spans),
                       float(p_span), int(len_lo), int(len_hi), float(p_original), float(p_silence), _stream())
         ctx.save_for_backward(lab)
         ctx.mark_non_differentiable(lab)
@@ -2018,7 +2018,6 @@ class MaskedBCEFn(torch.autograd.Function):
 
 def loc_threshold_logit(threshold):
     """log(p / (1 - p)) in float64 on the host: the logit the probability threshold p stands for; exactly 0.0 at p = 0.5"""
-    import math
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= threshold <= 1.0:
         raise ValueError(f"threshold: expected a probability in [0, 1], got {threshold!r}")
     p = float(threshold)

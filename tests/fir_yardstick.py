@@ -6,12 +6,14 @@ tests/test_gpu_fir_rows.py.
   fir_adjoint(x, h)  y[t] = sum_k h[k] x[t + k], written as flip(fir(flip(x), h))
   bound(x, h)        gamma(K + 2) * sum_k |h_k x_{t-k}|: for ANY summation order of K rounded fp32 products
                      |y - y64| <= gamma(K + 2) sum |h x|, gamma(m) = m u / (1 - m u), u = 2^-24 (Higham, Accuracy and Stability, ch. 3-4)
-  philox4x32_10, unit, normals      the generator, from Salmon et al. (SC'11) and the comment of wm_distort
+  philox4x32_10, unit, normals      the generator of tests/draw_yardstick.py, handed on under the names the tests use
   reverb_params, bank_index, rir    the draws and the response of the comment of wm_rir_synth"""
 import functools
 import math
 
 import numpy as np
+
+from draw_yardstick import PARAM, PARAM2, RIR_HIGH, SAMPLE_HIGH, affine32, key_of, normals, philox4x32_10, unit  # noqa: F401
 
 U = 2.0 ** -24
 # the device normal against float64 Box-Muller: 4 * the largest error tests/test_gpu_attacks.py has measured on an MI355X (NOISE_MEASURED
@@ -89,53 +91,10 @@ def float_ref(rows, n, K, shared, reverse):
     return ref
 
 
-# ------------------------------------------------------------------------------------------ the generator
-_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-
-
-def philox4x32_10(counter, key):
-    """four uint32 counter words (values or arrays that broadcast), two key words -> uint32 array (4, ...)"""
-    c = list(np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for v in counter]))
-    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
-    lo = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & lo, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & lo]
-        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
-    return np.stack(c).astype(np.uint32)
-
-
-def unit(o):
-    return ((o >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
-
-
-def key_of(seed):
-    seed = int(seed) & (2 ** 64 - 1)
-    return seed & 0xFFFFFFFF, seed >> 32
-
-
-SAMPLE_HIGH, PARAM, PARAM2, RIR_HIGH = 0, (0xFFFFFFFF, 0xFFFFFFFF), (0xFFFFFFFE, 0xFFFFFFFF), 0xFFFFFFFE
-
-
-def normals(seed, draw, row, n, high):
-    """the Box-Muller normals of "samples" t < n from the counters (t >> 2, high, row, draw)"""
-    q = np.arange((n + 3) // 4, dtype=np.uint64)
-    o = philox4x32_10((q, high, int(row), int(draw)), key_of(seed))
-    z = np.empty((len(q), 4))
-    for p in (0, 1):
-        rad, th = np.sqrt(-2.0 * np.log(unit(o[2 * p]))), 2.0 * math.pi * unit(o[2 * p + 1])
-        z[:, 2 * p], z[:, 2 * p + 1] = rad * np.cos(th), rad * np.sin(th)
-    return z.reshape(-1)[:n]
-
-
-def _affine32(pair, u):
-    lo, hi = np.float32(pair[0]), np.float32(pair[1])
-    return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)      # fmaf(hi - lo, u, lo): the product is exact in float64
-
-
+# ------------------------------------------------------------------------------------------ the draws (the generator is tests/draw_yardstick.py's)
 def reverb_params(seed, draw, rows, rt60, drr_db):
     o = philox4x32_10((PARAM2[0], PARAM2[1], np.asarray(rows, dtype=np.uint64), int(draw)), key_of(seed))
-    return _affine32(rt60, unit(o[0])), _affine32(drr_db, unit(o[1]))
+    return affine32(rt60, unit(o[0])), affine32(drr_db, unit(o[1]))
 
 
 def bank_index(seed, draw, rows, entries):

@@ -1,33 +1,22 @@
 """Yardsticks for the splice attack and the localisation kernels, written from the definitions in include/wm_hip.h in integer / float64 numpy.
-Nothing from the package: its own Philox4x32-10 (as published), its own geometry, its own bit packing, its own BCE."""
+Nothing from the package: the Philox4x32-10 of tests/draw_yardstick.py, its own integer geometry, its own bit packing, its own BCE."""
 import numpy as np
 
+from draw_yardstick import key_of, philox4x32_10, splice_shift, splice_span
+
 ORIGINAL, SILENCE, MOVED = 0, 1, 2
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on scalar words -> four python ints"""
-    c = [np.uint64(int(v) & 0xFFFFFFFF) for v in (c0, c1, c2, c3)]
-    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & M32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & M32]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return [int(v) for v in c]
 
 
 def spans(seed, draw, row, n, max_spans, p_span, len_lo, len_hi, p_original, p_silence):
     """[(start, L, kind, shift, active)] for span j = 0 .. max_spans - 1 of row `row` (= row0 + r)"""
-    seed = int(seed) & (2 ** 64 - 1)
-    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    key = key_of(seed)
     t_span = float(np.float32(p_span))                                 # float32 arguments, compared in float64
     t_orig = float(np.float32(p_original))
     t_sil = t_orig + float(np.float32(p_silence))
     out = []
     for j in range(max_spans):
-        o = philox(0xFFFFFFFB - 2 * j, 0xFFFFFFFF, row, draw, k0, k1)
-        o2 = philox(0xFFFFFFFA - 2 * j, 0xFFFFFFFF, row, draw, k0, k1)
+        o = [int(w) for w in philox4x32_10((*splice_span(j), row, draw), key)]
+        o2 = [int(w) for w in philox4x32_10((*splice_shift(j), row, draw), key)]
         v = [w >> 9 for w in o]
         u = [(w + 0.5) * 2.0 ** -23 for w in v]
         L = len_lo + ((v[1] * (len_hi - len_lo + 1)) >> 23)

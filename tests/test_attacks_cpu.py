@@ -10,6 +10,8 @@ from scipy.signal import lfilter
 import awm_amd
 from awm_amd import attacks
 
+import draw_yardstick
+
 
 def words(text):
     return [int(w, 16) for w in text.split()]
@@ -21,10 +23,12 @@ def words(text):
     ("243f6a88 85a308d3 13198a2e 03707344", "a4093822 299f31d0", "d16cfe09 94fdcceb 5001e420 24126ea1"),
 ])
 def test_philox_known_answers(counter, key, want):
-    """the known-answer vectors published with Random123 (kat_vectors, philox4x32 10 rounds)"""
-    out = attacks.philox4x32_10(words(counter), words(key))
-    assert out.dtype == np.uint32 and out.shape == (4,)
-    assert [int(v) for v in out] == words(want)
+    """the known-answer vectors published with Random123 (kat_vectors, philox4x32 10 rounds): the package's restatement and the tests'
+    one yardstick, each pinned to the publication"""
+    for philox in (attacks.philox4x32_10, draw_yardstick.philox4x32_10):
+        out = philox(words(counter), words(key))
+        assert out.dtype == np.uint32 and out.shape == (4,)
+        assert [int(v) for v in out] == words(want)
 
 
 def test_philox_broadcasts_over_counters():

@@ -1,7 +1,7 @@
 """Channel distortions on the GPU: wm_distort / wm_distort_bwd (csrc/distort.hip) through ops.DistortFn, the modules of attacks.py on top
 of them, a train step through a chain of them, and evaluate_robustness.
 
-The yardstick is written here in float64 and uses nothing from the package: Philox4x32-10 as published, u = ((o >> 9) + 0.5) 2^-23 (exact in
+The yardstick is float64 and uses nothing from the package: the Philox4x32-10 of tests/draw_yardstick.py, u = ((o >> 9) + 0.5) 2^-23 (exact in
 both precisions), Box-Muller on exactly those u, the row parameters from their own counter, and y = g x + s z.  Tolerances (derived, not tuned):
 
   noise   NOISE_TOL = 4 * NOISE_MEASURED, where NOISE_MEASURED is the largest |y - 1 - z64| this file's noise test has shown on an MI355X
@@ -23,6 +23,7 @@ import pytest
 import torch
 from scipy.signal import lfilter
 
+import draw_yardstick as Y
 from oracle import recipes as R
 from oracle import wm_oracle as O
 
@@ -55,30 +56,9 @@ def gamma(k):
 
 
 # ------------------------------------------------------------------------------------------ yardstick (nothing from the package)
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10; uint64 arrays holding 32-bit words -> four such arrays"""
-    m = np.uint64(0xFFFFFFFF)
-    c = [np.asarray(v, dtype=np.uint64) & m for v in np.broadcast_arrays(c0, c1, c2, c3)]
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c
-
-
-def unit(o):
-    return ((o >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
-
-
 @functools.lru_cache(maxsize=None)
 def noise64(seed, draw, row, n):
-    q = np.arange((n + 3) // 4, dtype=np.uint64)
-    o = philox(q, q >> np.uint64(32), row, draw, seed & 0xFFFFFFFF, seed >> 32)
-    z = np.empty((len(q), 4))
-    for p in (0, 1):
-        rad, th = np.sqrt(-2.0 * np.log(unit(o[2 * p]))), 2.0 * math.pi * unit(o[2 * p + 1])
-        z[:, 2 * p], z[:, 2 * p + 1] = rad * np.cos(th), rad * np.sin(th)
-    z = z.reshape(-1)[:n]
+    z = Y.normals(seed, draw, row, n, None)
     z.setflags(write=False)
     return z
 
@@ -86,11 +66,9 @@ def noise64(seed, draw, row, n):
 def params64(seed, draw, rows, bounds):
     """(gain_db, snr_db, noisy) of the rows `rows`: fmaf(hi - lo, u, lo) in float32 (the product of two float32 is exact in float64, so the one
     rounding of the sum is the fmaf's up to a double rounding no tolerance here can see)"""
-    glo, ghi, slo, shi, p = (np.float32(v) for v in bounds)
-    o = philox(0xFFFFFFFF, 0xFFFFFFFF, np.asarray(rows, dtype=np.uint64), draw, seed & 0xFFFFFFFF, seed >> 32)
-    gain_db = (np.float64(ghi - glo) * unit(o[0]) + np.float64(glo)).astype(np.float32).astype(np.float64)
-    snr_db = (np.float64(shi - slo) * unit(o[1]) + np.float64(slo)).astype(np.float32).astype(np.float64)
-    return gain_db, snr_db, unit(o[2]) < np.float64(p)
+    o = Y.philox4x32_10((*Y.PARAM, np.asarray(rows, dtype=np.uint64), draw), Y.key_of(seed))
+    gain_db, snr_db = Y.affine32(bounds[0:2], Y.unit(o[0])), Y.affine32(bounds[2:4], Y.unit(o[1]))
+    return gain_db.astype(np.float64), snr_db.astype(np.float64), Y.unit(o[2]) < np.float64(np.float32(bounds[4]))
 
 
 def signal(rows, n, seed=0):

@@ -82,15 +82,15 @@ def test_counter_domains_never_coincide():
     taps = lambda k4: (k4, Y.RIR_HIGH)
     assert samples(q_max)[1] == Y.SAMPLE_HIGH == 0 and Y.RIR_HIGH != 0
     assert Y.PARAM != Y.PARAM2 and Y.PARAM[1] != Y.RIR_HIGH and Y.PARAM2[1] != Y.RIR_HIGH and Y.PARAM[1] != 0 and Y.PARAM2[1] != 0
-    assert (attacks._PARAM_Q & 0xFFFFFFFF, attacks._PARAM_Q >> 32) == Y.PARAM
-    assert (attacks._PARAM2_Q & 0xFFFFFFFF, attacks._PARAM2_Q >> 32) == Y.PARAM2 and attacks._RIR_HIGH == Y.RIR_HIGH
+    assert attacks.FAMILIES["param"] == Y.PARAM
+    assert attacks.FAMILIES["param2"] == Y.PARAM2 and attacks.FAMILIES["rir_tap"] == (None, Y.RIR_HIGH)
     assert taps(k_max)[0] < Y.PARAM2[0], "a tap counter's first word stays far below the parameter counters'"
     # and the numbers differ: the same (seed, draw, row) through the four domains
     key = Y.key_of(12345)
     words = [tuple(Y.philox4x32_10((c0, c1, 9, 2), key).tolist()) for c0, c1 in (samples(0), taps(0), Y.PARAM, Y.PARAM2)]
     assert len(set(words)) == 4
     # the package's normals with the tap counter are the yardstick's
-    assert np.array_equal(attacks._normals(12345, 2, 9, 37, attacks._RIR_HIGH), Y.normals(12345, 2, 9, 37, Y.RIR_HIGH))
+    assert np.array_equal(attacks._normals(12345, 2, 9, 37, "rir_tap"), Y.normals(12345, 2, 9, 37, Y.RIR_HIGH))
     assert np.array_equal(attacks.normal_noise(12345, 2, 9, 37), Y.normals(12345, 2, 9, 37, 0))
 
 

@@ -11,6 +11,7 @@ import torch
 import awm_amd
 from awm_amd import _lib, attacks, ops
 
+import draw_yardstick as D
 import time_warp_yardstick as Y
 
 MODULES = [dict(), dict(speed=0.8), dict(speed=1.25, shift_s=0.004), dict(speed=2.0, shift_s=-0.002),
@@ -45,22 +46,29 @@ def test_draws_are_reproducible_and_the_yardsticks():
 
 
 def test_the_new_counters_meet_none_of_the_others():
-    """(word 0, word 1) of the six families for one (seed, draw, row): samples (q, 0), a response's taps (k >> 2, ~0 - 1), and the four
-    parameter counters (~0 - i, ~0), i = 0..3"""
-    assert (attacks._PARAM_Q & 0xFFFFFFFF, attacks._PARAM_Q >> 32) == Y.PARAM == (0xFFFFFFFF, 0xFFFFFFFF)
-    assert (attacks._PARAM2_Q & 0xFFFFFFFF, attacks._PARAM2_Q >> 32) == Y.PARAM2 == (0xFFFFFFFE, 0xFFFFFFFF)
-    assert (attacks._WARP_Q & 0xFFFFFFFF, attacks._WARP_Q >> 32) == Y.WARP == (0xFFFFFFFD, 0xFFFFFFFF)
-    assert (attacks._WARP_PHASE_Q & 0xFFFFFFFF, attacks._WARP_PHASE_Q >> 32) == Y.WARP_PHASE == (0xFFFFFFFC, 0xFFFFFFFF)
-    assert attacks._RIR_HIGH == Y.RIR_HIGH
-    families = [Y.PARAM, Y.PARAM2, Y.WARP, Y.WARP_PHASE]
-    assert len(set(families)) == 4
+    """(word 0, word 1) of every family for one (seed, draw, row), from the package's table and from the yardstick's: samples (q, 0), a
+    response's taps (k >> 2, ~0 - 1), the four parameter counters (~0 - i, ~0), i = 0..3, and Splice's sixteen (~0 - 4 - i, ~0), i = 0..15"""
+    assert attacks.FAMILIES["param"] == Y.PARAM == (0xFFFFFFFF, 0xFFFFFFFF)
+    assert attacks.FAMILIES["param2"] == Y.PARAM2 == (0xFFFFFFFE, 0xFFFFFFFF)
+    assert attacks.FAMILIES["warp"] == Y.WARP == (0xFFFFFFFD, 0xFFFFFFFF)
+    assert attacks.FAMILIES["warp_phase"] == Y.WARP_PHASE == (0xFFFFFFFC, 0xFFFFFFFF)
+    assert attacks.FAMILIES["sample"] == (None, D.SAMPLE_HIGH) and attacks.FAMILIES["rir_tap"] == (None, Y.RIR_HIGH)
+    fixed = {name: f for name, f in attacks.FAMILIES.items() if f[0] is not None}
+    assert fixed == D.FAMILIES and len(fixed) == len(attacks.FAMILIES) - 2 == 4 + 2 * ops.SPLICE_MAX_SPANS
+    assert [fixed[f"splice_span{j}"][0] for j in range(8)] == [0xFFFFFFFB - 2 * j for j in range(8)]
+    assert [fixed[f"splice_shift{j}"][0] for j in range(8)] == [0xFFFFFFFA - 2 * j for j in range(8)]
+    families = list(fixed.values())
+    assert families[:4] == [Y.PARAM, Y.PARAM2, Y.WARP, Y.WARP_PHASE]
+    assert len({f[0] for f in families}) == len(families) == 20, "all first words are distinct"
     q_max, k_max = (1 << 34) - 1 >> 2, ops.FIR_MAX_TAPS - 1 >> 2
     for f in families:
         assert f[1] != 0 and f[1] != Y.RIR_HIGH, "a sample counter's high word is 0, a tap counter's 0xFFFFFFFE"
-    assert q_max >> 32 == 0 and k_max < Y.WARP_PHASE[0]
+    assert q_max >> 32 == 0 and k_max < min(f[0] for f in families) == 0xFFFFFFEC
     key = Y.key_of(12345)
     words = [tuple(Y.philox4x32_10((c0, c1, 9, 2), key).tolist()) for c0, c1 in [(0, 0), (0, Y.RIR_HIGH)] + families]
-    assert len(set(words)) == 6, "and the numbers differ"
+    assert len(set(words)) == 22, "and the numbers differ"
+    for name, f in fixed.items():
+        assert np.array_equal(attacks._words(name, 12345, 2, 9), Y.philox4x32_10((*f, 9, 2), key)), name
     # the reverb's draws are what they were
     rt60, _ = attacks.row_reverb_params(12345, 2, np.array([9]), (0.1, 0.4), (0, 12))
     u = Y.unit(Y.philox4x32_10((*Y.PARAM2, 9, 2), key)[0])

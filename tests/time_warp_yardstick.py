@@ -8,7 +8,7 @@ tests/test_gpu_time_warp.py.
                                support predicate: the dense (n, J) form every map below is read from
   forward / adjoint            y[t] = sum_k W x[k] and dx[k] = sum_t W dy[t] per row, with their per-sample bounds
   matrix(prm, n, tab, Z, R)    the dense (n, n) float64 matrix M[t, k] = W(p(t) - k), for small n
-  philox4x32_10, unit, warp_params   the generator (Salmon et al., SC'11) and TimeWarp's draws
+  philox4x32_10, unit, warp_params   the generator of tests/draw_yardstick.py, handed on, and TimeWarp's draws
 
 The bound.  With u = 2^-24, T the number of taps in a sample's support and gamma(m) = m u / (1 - m u) (Higham, Accuracy and Stability,
 ch. 3-4):
@@ -22,6 +22,8 @@ import functools
 import math
 
 import numpy as np
+
+from draw_yardstick import PARAM, PARAM2, RIR_HIGH, WARP, WARP_PHASE, affine32, key_of, philox4x32_10, unit  # noqa: F401
 
 U = 2.0 ** -24
 TILE = 256                                        # the samples a workgroup of csrc/time_warp.hip takes at a time
@@ -166,41 +168,7 @@ def case_ref(n, fi, adj):
     return ref
 
 
-# ------------------------------------------------------------------------------------------ the generator and the draws
-_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-
-
-def philox4x32_10(counter, key):
-    """four uint32 counter words (values or arrays that broadcast), two key words -> uint32 array (4, ...)"""
-    c = list(np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for v in counter]))
-    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
-    lo = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & lo, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & lo]
-        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
-    return np.stack(c).astype(np.uint32)
-
-
-def unit(o):
-    return ((o >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
-
-
-def key_of(seed):
-    seed = int(seed) & (2 ** 64 - 1)
-    return seed & 0xFFFFFFFF, seed >> 32
-
-
-# the first two counter words of the families: samples have (q, 0), a synthetic response's taps (k >> 2, 0xFFFFFFFE)
-PARAM, PARAM2, WARP, WARP_PHASE = ((0xFFFFFFFF - i, 0xFFFFFFFF) for i in range(4))
-RIR_HIGH = 0xFFFFFFFE
-
-
-def _affine32(pair, u):
-    lo, hi = np.float32(pair[0]), np.float32(pair[1])
-    return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)          # fmaf(hi - lo, u, lo): the product is exact in float64
-
-
+# ------------------------------------------------------------------------------------------ the draws (the generator is tests/draw_yardstick.py's)
 def warp_params(seed, draw, rows, speed, shift_s, flutter_hz, flutter_depth, sample_rate=SAMPLE_RATE):
     """(len(rows), 6) float32: words o0..o3 of (0xFFFFFFFD, 0xFFFFFFFF, row, draw) onto speed, shift, flutter rate and depth, word o0 of
     (0xFFFFFFFC, 0xFFFFFFFF, row, draw) the phase; derived in float64 from the float32 draws and rounded once each"""
@@ -209,10 +177,10 @@ def warp_params(seed, draw, rows, speed, shift_s, flutter_hz, flutter_depth, sam
     ph = unit(philox4x32_10((WARP_PHASE[0], WARP_PHASE[1], rows, int(draw)), key_of(seed))[0])
     out = np.zeros((len(rows), 6), dtype=np.float32)
     for r in range(len(rows)):
-        a = float(_affine32(speed, unit(o[0][r])))
-        shift = float(_affine32(shift_s, unit(o[1][r])))
-        hz = float(_affine32(flutter_hz, unit(o[2][r]))) if flutter_hz is not None else 0.0
-        depth = float(_affine32(flutter_depth, unit(o[3][r]))) if flutter_depth is not None else 0.0
+        a = float(affine32(speed, unit(o[0][r])))
+        shift = float(affine32(shift_s, unit(o[1][r])))
+        hz = float(affine32(flutter_hz, unit(o[2][r]))) if flutter_hz is not None else 0.0
+        depth = float(affine32(flutter_depth, unit(o[3][r]))) if flutter_depth is not None else 0.0
         w = np.float32(hz / sample_rate)
         on = w != 0 and depth != 0
         out[r] = [a, shift * sample_rate, depth * a / (2.0 * math.pi * float(w)) if on else 0.0, w, ph[r] if on else 0.0,
