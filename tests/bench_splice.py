@@ -21,26 +21,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import awm_amd                                                        # noqa: E402
 from awm_amd.ops import _stream                                       # noqa: E402
+from bench_timing import batch_ms, launches_for                       # noqa: E402
 
 T, NO = 16000, 17
-
-
-def batch_ms(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
-def launches_for(fn, batch_seconds, cap):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    t = batch_ms(fn, 2)
-    return max(1, min(cap, int(batch_seconds * 1e3 / max(t, 1e-3)) + 1))
 
 
 def stats(v):

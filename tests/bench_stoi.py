@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import awm_amd                                                        # noqa: E402
 from awm_amd import ops, quality                                      # noqa: E402
 from awm_amd.ops import _stream                                       # noqa: E402
-from bench_time_warp import measure                                   # noqa: E402
+from bench_timing import measure                                      # noqa: E402
 import stoi_yardstick as Y                                            # noqa: E402
 
 

@@ -14,8 +14,8 @@ import math
 import numpy as np
 
 from draw_yardstick import PARAM, PARAM2, RIR_HIGH, SAMPLE_HIGH, affine32, key_of, normals, philox4x32_10, unit  # noqa: F401
+from yardstick_common import gamma
 
-U = 2.0 ** -24
 # the device normal against float64 Box-Muller: 4 * the largest error tests/test_gpu_attacks.py has measured on an MI355X (NOISE_MEASURED
 # = 6.679e-7 there, NOISE_TOL = 4 * that); restated, not imported
 NOISE_TOL = 4 * 6.679e-7
@@ -26,10 +26,6 @@ RIR_REL = 2e-5                                    # fp32 scalars, exp and the su
 # longest response there is, whose taps and history need more than 64 KB of LDS
 CASES = [(3, n, K) for n, K in ((1, 1), (5, 1), (31, 2), (32, 32), (33, 33), (40, 100), (1000, 257), (1025, 64), (4099, 1000),
                                 (16000, 2048))] + [(2, 16000, 4096), (1, 4200, 16384)]
-
-
-def gamma(m):
-    return m * U / (1.0 - m * U)
 
 
 # ------------------------------------------------------------------------------------------ the convolution

@@ -10,21 +10,13 @@ from scipy.signal import lfilter
 
 import awm_amd
 from awm_amd import ops
-
-
-def rbj(rate, cutoff, Q=0.707):
-    w0 = 2.0 * math.pi * cutoff / rate
-    alpha = math.sin(w0) / (2.0 * Q)
-    cw = math.cos(w0)
-    b = np.array([(1.0 - cw) / 2.0, 1.0 - cw, (1.0 - cw) / 2.0], dtype=np.float64)
-    a = np.array([1.0 + alpha, -2.0 * cw, 1.0 - alpha], dtype=np.float64)
-    return (b / a[0]).astype(np.float32), (a / a[0]).astype(np.float32)
+from biquad_yardstick import section
 
 
 @pytest.mark.parametrize("rate,cutoff", [(16000, 7000), (44100, 7000), (48000, 7000), (48000, 500), (16000, 50)])
 def test_coeffs_reproduce_lowpass_biquad(rate, cutoff):
     c = ops.biquad_lowpass_coeffs(rate, cutoff)
-    b32, a32 = rbj(rate, cutoff)
+    b32, a32 = (v.astype(np.float32) for v in section(rate, cutoff))
     assert len(c) == 5 and all(isinstance(v, float) for v in c)
     assert c == (float(b32[0]), float(b32[1]), float(b32[2]), float(a32[1]), float(a32[2]))
     assert all(float(np.float32(v)) == v for v in c), "every value is a float32"

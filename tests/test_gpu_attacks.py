@@ -21,38 +21,22 @@ import os
 import numpy as np
 import pytest
 import torch
-from scipy.signal import lfilter
 
+import biquad_yardstick
 import draw_yardstick as Y
-from oracle import recipes as R
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import reference_models
 from oracle import wm_oracle as O
+from yardstick_common import U, gamma
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 NOISE_MEASURED = 6.679e-7            # on an MI355X, in the (64, 4096) case of test_noise_vs_float64_box_muller
 NOISE_TOL = min(4 * NOISE_MEASURED, 2e-5)
 LENGTHS = [1, 2, 3, 4, 5, 7, 8, 1023, 1024, 1025, 4099, 16000,
            16384, 16385, 40000]      # the last three: one full segment of the row sums, one sample more (the second kernel), three segments
 BOUNDS = (-6.0, 6.0, 20.0, 40.0, 1.0)
 SEED, DRAW, ROW0 = (7 << 32) + 11, 2, 5
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def gamma(k):
-    return k * U / (1 - k * U)
 
 
 # ------------------------------------------------------------------------------------------ yardstick (nothing from the package)
@@ -271,49 +255,6 @@ def test_distortion_module(awm, dev):
         assert torch.equal(xg.grad, m.last_stat[:, 0].view(4, 1, 1).expand_as(xg)) == (mode == "detached")
 
 
-# the bound of tests/test_gpu_biquad.py for the biquad section in float mode, copied
-GAMMA6 = 6 * U / (1 - 6 * U)
-
-
-def section(rate, cutoff, Q=0.707):
-    w0 = 2.0 * math.pi * cutoff / rate
-    alpha = math.sin(w0) / (2.0 * Q)
-    cw = math.cos(w0)
-    b = np.array([(1.0 - cw) / 2.0, 1.0 - cw, (1.0 - cw) / 2.0], dtype=np.float64)
-    a = np.array([1.0 + alpha, -2.0 * cw, 1.0 - alpha], dtype=np.float64)
-    return (b / a[0]).astype(np.float32).astype(np.float64), (a / a[0]).astype(np.float32).astype(np.float64)
-
-
-def responses(rate, cutoff, W):
-    b, a = section(rate, cutoff)
-    imp = np.zeros(W + 60000)
-    imp[0] = 1.0
-    g = np.abs(lfilter([1.0], a, imp))
-    h = np.abs(lfilter(b, a, imp))
-    live = np.nonzero(g > 1e-40 * g[0])[0]
-    return g[:int(live[-1]) + 1], float(h[W:].sum())
-
-
-def shifted(v, k):
-    out = np.zeros_like(v)
-    if k < v.shape[-1]:
-        out[..., k:] = v[..., :v.shape[-1] - k]
-    return out
-
-
-def biquad_yardstick(x, rate, cutoff, W):
-    """x (rows, n) -> (y64, bound): |y - y64| <= (|g| * e)[t] + tail + spacing(float32(|y64|)), see tests/test_gpu_biquad.py"""
-    b, a = section(rate, cutoff)
-    x = np.asarray(x, dtype=np.float64)
-    y = lfilter(b, a, x, axis=-1)
-    e = GAMMA6 * (np.abs(b[0] * x) + np.abs(b[1] * shifted(x, 1)) + np.abs(b[2] * shifted(x, 2)) +
-                  np.abs(a[1] * shifted(y, 1)) + np.abs(a[2] * shifted(y, 2)))
-    g, tail = responses(rate, cutoff, W)
-    n = x.shape[-1]
-    carried = np.stack([np.convolve(row, g[:n])[:n] for row in e])
-    return y, carried + np.abs(x).max() * tail + np.spacing(np.abs(y).astype(np.float32)).astype(np.float64)
-
-
 def test_lowpass_forward_and_adjoint(awm, dev):
     from awm_amd import ops
     rate, cutoff = 16000, 4000
@@ -322,7 +263,7 @@ def test_lowpass_forward_and_adjoint(awm, dev):
     for n in (1, 65, 1000, 4097):
         x = 3.0 * signal(3, n, seed=4)                                            # loud: a clamp would show
         w = signal(3, n, seed=5)
-        y64, bound = biquad_yardstick(x.numpy(), rate, cutoff, W)
+        y64, bound = biquad_yardstick.yardstick(x.numpy(), rate, cutoff, W)
         xd = x.view(3, 1, n).to(dev).requires_grad_()
         y = low(xd)
         assert y.shape == (3, 1, n)
@@ -334,7 +275,7 @@ def test_lowpass_forward_and_adjoint(awm, dev):
         # <L x, w> = <x, L^T w>: L^T w is the filter of the flipped w, flipped; its bound is the forward bound of that run
         y.backward(w.view(3, 1, n).to(dev))
         lt = xd.grad.double().cpu().numpy().reshape(3, n)
-        r64, rbound = biquad_yardstick(w.numpy()[:, ::-1], rate, cutoff, W)
+        r64, rbound = biquad_yardstick.yardstick(w.numpy()[:, ::-1], rate, cutoff, W)
         assert np.all(np.abs(lt - r64[:, ::-1]) <= rbound[:, ::-1])
         lhs = float((y.detach().double().cpu().numpy().reshape(3, n) * w.double().numpy()).sum())
         rhs = float((x.double().numpy() * lt).sum())
@@ -344,19 +285,10 @@ def test_lowpass_forward_and_adjoint(awm, dev):
 
 
 # ------------------------------------------------------------------------------------------ 5. the step and the evaluation loop
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
 def test_train_step_through_a_chain(awm, dev):
     """T = 2048, not 1024: the loudness loss pads its 2048-point frames by reflection, which needs T > 1024 (wm_loud_loss returns
     hipErrorInvalidValue below that, as torch.stft does), so 2048 is the shortest clip of the other step tests that the step accepts"""
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     G2, D2 = copy.deepcopy(G), copy.deepcopy(D)
     B, T = 2, 2048
     s = O.synthetic_clips(B, seed=41, T=T).to(dev)

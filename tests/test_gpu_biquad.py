@@ -3,101 +3,36 @@ time-parallel chunks (or one lane per row where the warm-up would be too long), 
 its epilogue; `ops.biquad`, `ops.PcmCodecFn`, `perceptual_postprocess`, `PcmCodec`, `encode_pcm16`, `save_audio(device=)` and the
 `codec=` keyword of the step functions on top of it.
 
-The yardstick is `yardstick()` below and uses nothing from the package: y64 = scipy.signal.lfilter in float64 with the float32-rounded
-coefficients of the published RBJ low-pass section, on the float64 image of the input.  Tolerance (derived, nothing tuned, no rtol):
-
-    |y - y64| <= (|g| * e)[t] + tail + spacing(float32(|y64|))
-
-g: float64 impulse response of 1 / A(z);  e[t] = gamma6 (|b0 x[t]| + |b1 x[t-1]| + |b2 x[t-2]| + |a1 y64[t-1]| + |a2 y64[t-2]|), gamma6 =
-6u / (1 - 6u), u = 2^-24: the local rounding error of one step of the direct-form-I recursion (five roundings, six allowed), carried to
-the output by the recursion itself;  tail = max|x| sum_{k >= W} |h[k]|, h the impulse response of the whole section and W =
-ops.biquad_warm(coeffs): what a chunk that starts W samples early from a zero state can have missed;  the spacing term is the
-representation of y64 in float32.  (|g| is cut where it has decayed below 1e-40 of its start, which only makes the bound smaller.)
+The yardstick is `yardstick()` of tests/biquad_yardstick.py, float64 scipy.signal.lfilter with nothing from the package; the derived
+tolerance of the float mode stands in that module's docstring.
 
 The int16 codes are compared with trunc(clamp(y64) * 32767): a truncating cast after a recursive filter cannot be bit-identical between two
 evaluation orders, so every difference must be +-1 and at most 1 % of the samples may differ (a condition, not a measurement).  Given
 the kernel's own float output the two quantisers are exact, and are held to bit identity."""
 import copy
-import functools
 import math
 import wave
 
 import numpy as np
 import pytest
 import torch
-from scipy.signal import lfilter
 
-from oracle import recipes as R
+from biquad_yardstick import yardstick
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import reference_models, rel_err
 from oracle import wm_oracle as O
+from yardstick_common import assert_within
 
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = 1e-4
-U = 2.0 ** -24
-GAMMA6 = 6 * U / (1 - 6 * U)
 PAIRS = [(16000, 7000), (44100, 7000), (48000, 7000), (48000, 500), (16000, 50)]
 LENGTHS = [1, 2, 3, 63, 64, 65, 1000, 4097, 40000]
 KINDS = ["noise", "tonal", "impulse", "loud"]
 ROWS = 3
 
 
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-# ------------------------------------------------------------------------------------------ yardstick (nothing from the package)
-@functools.lru_cache(maxsize=None)
-def section(rate, cutoff, Q=0.707):
-    """(b (3,), a (3,)) float64 images of the float32-rounded RBJ low-pass coefficients, a[0] = 1"""
-    w0 = 2.0 * math.pi * cutoff / rate
-    alpha = math.sin(w0) / (2.0 * Q)
-    cw = math.cos(w0)
-    b = np.array([(1.0 - cw) / 2.0, 1.0 - cw, (1.0 - cw) / 2.0], dtype=np.float64)
-    a = np.array([1.0 + alpha, -2.0 * cw, 1.0 - alpha], dtype=np.float64)
-    return (b / a[0]).astype(np.float32).astype(np.float64), (a / a[0]).astype(np.float32).astype(np.float64)
-
-
-@functools.lru_cache(maxsize=None)
-def responses(rate, cutoff, W):
-    """(|g| cut where it has decayed below 1e-40 of its start, sum_{k >= W} |h[k]|)"""
-    b, a = section(rate, cutoff)
-    imp = np.zeros(W + 60000)
-    imp[0] = 1.0
-    g = np.abs(lfilter([1.0], a, imp))
-    h = np.abs(lfilter(b, a, imp))
-    live = np.nonzero(g > 1e-40 * g[0])[0]
-    return g[:int(live[-1]) + 1], float(h[W:].sum())
-
-
-def shifted(v, k):
-    out = np.zeros_like(v)
-    if k < v.shape[-1]:
-        out[..., k:] = v[..., :v.shape[-1] - k]
-    return out
-
-
-def yardstick(x, rate, cutoff, W):
-    """x (rows, n) float -> (y64 (rows, n), bound (rows, n)), both float64"""
-    b, a = section(rate, cutoff)
-    x = np.asarray(x, dtype=np.float64)
-    y = lfilter(b, a, x, axis=-1)
-    e = GAMMA6 * (np.abs(b[0] * x) + np.abs(b[1] * shifted(x, 1)) + np.abs(b[2] * shifted(x, 2)) +
-                  np.abs(a[1] * shifted(y, 1)) + np.abs(a[2] * shifted(y, 2)))
-    g, tail = responses(rate, cutoff, W)
-    n = x.shape[-1]
-    carried = np.stack([np.convolve(row, g[:n])[:n] for row in e])
-    return y, carried + np.abs(x).max() * tail + np.spacing(np.abs(y).astype(np.float32)).astype(np.float64)
-
-
+# ------------------------------------------------------------------------------------------ inputs and their shared references
 def signal(kind, n, rate, seed=0):
     """(ROWS, n) float32 CPU"""
     g = torch.Generator().manual_seed(1000 * seed + n)
@@ -129,15 +64,6 @@ def reference(rate, cutoff, kind, n, W):
         y64, bound = yardstick(x.numpy(), rate, cutoff, W)
         _REF[key] = (x, y64, bound)
     return _REF[key]
-
-
-def assert_within(y, ref, bound, what):
-    y = np.asarray(y, dtype=np.float64)
-    assert y.shape == ref.shape, f"{what}: {y.shape} vs {ref.shape}"
-    err = np.abs(y - ref)
-    worst = np.unravel_index(int(np.argmax(err - bound)), err.shape)
-    print(f"{what}: max err {err.max():.3e}, max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-    assert np.all(err <= bound), f"{what}: sample {worst}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
 
 
 def bits_of(mask, n):
@@ -384,25 +310,11 @@ def test_straight_through_backward(awm, dev, rate, cutoff):
     assert not ref.requires_grad and torch.equal(ref, out.detach())
 
 
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
-def rel_err(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).abs().max() / (ref.abs().max() + 1e-30))
-
-
 def test_train_step_reference_gradient_mode(awm, dev, monkeypatch):
     """main15c's step: s_w = codec(s + delta) feeds the Detector, mel and loudness; with torch.round's zero gradient only l1 and hf train
     the Generator, the Detector trains on the processed signal, and nothing leaves the device on the way"""
     from awm_amd import step
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     G2, D2 = copy.deepcopy(G), copy.deepcopy(D)
     for m in (G, D, G2, D2):
         m.train()
@@ -447,7 +359,7 @@ def _same(a, b):
 
 def test_codec_none_is_todays_graph(awm, dev):
     from awm_amd import step
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     s = O.synthetic_clips(2, seed=33, T=2048).to(dev)
     msg = torch.tensor([7, 4242], device=dev)
     G.train(); D.train()
@@ -458,7 +370,7 @@ def test_codec_none_is_todays_graph(awm, dev):
 
 
 def test_eval_forward_codec_on_both_branches(awm, dev):
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     G.eval(); D.eval()
     s = O.synthetic_clips(2, seed=35, T=2048).to(dev)
     msg = torch.tensor([9, 777], device=dev)

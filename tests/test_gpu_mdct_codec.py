@@ -16,25 +16,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import recipes as R
 from oracle import wm_oracle as O
 
 import mdct_yardstick as Y
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import reference_models
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 def spacing32(v):
@@ -192,19 +180,10 @@ def test_module_on_the_gpu_matches_its_cpu_path_in_shape_and_draw(awm, dev):
 
 
 # ------------------------------------------------------------------------------------------ 4. the step and the evaluation loop
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
 @pytest.mark.parametrize("grad", ["straight_through", "dead_zone"])
 def test_train_step_through_the_codec(awm, dev, grad):
     """T = 2048: the shortest clip the step's loudness loss accepts"""
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     s = O.synthetic_clips(2, seed=41, T=2048).to(dev)
     msg = torch.tensor([3, 60001], device=dev)
     codec = torch.nn.Sequential(awm.Distortion(seed=3), awm.TransformCodec(seed=3, grad=grad), awm.PcmCodec(grad="straight_through"))

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import rel_err, rnd
 from oracle import recipes as R
 from oracle import wm_oracle as O
 
@@ -19,33 +21,11 @@ GRAD_FLOOR_TRAIN = 5e-3   # test_all_grads_vs_oracle's floor: train-mode BatchNo
 GRAD_FLOOR_TRAIN_BIAS = 2e-2   # train-mode BatchNorm bias gradients: the CPU fp32 run alone is up to 6e-3 from fp64 (bits = 8)
 
 
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def rel_err(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).abs().max() / (ref.abs().max() + 1e-30))
-
-
 def check(a, ref, tol, what=""):
     assert a.shape == ref.shape, f"{what}: shape {tuple(a.shape)} vs {tuple(ref.shape)}"
     e = rel_err(a, ref)
     assert e <= tol, f"{what}: rel err {e:.3e} > {tol}"
     return e
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 # ------------------------------------------------------------------------------------------ 1. the head against fp64

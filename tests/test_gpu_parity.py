@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import rel_err, rnd
 from oracle import recipes as R
 from oracle import wm_oracle as O
 
@@ -23,25 +25,6 @@ FWD_TOL = 1e-4
 GRAD_TOL = 2e-3
 GRAD_FLOOR = 3e-4     # whole-network gradients vs an fp64 run: floor of the "<= 2 x CPU-fp32 distance" bar
 GRAD_FLOOR_BIAS = 2e-3   # same for bias gradients (cancellation-dominated sums)
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def rel_err(a, ref):
-    a = a.detach().double().cpu()
-    ref = ref.detach().double().cpu()
-    return float((a - ref).abs().max() / (ref.abs().max() + 1e-30))
 
 
 def check(a, ref, tol, what=""):
@@ -61,10 +44,6 @@ def check_elementwise(a, ref, what="", rtol=1e-4, atol_of_max=1e-6):
     worst = float(excess.max())
     assert worst <= 0.0, (f"{what}: {int((excess > 0).sum())} of {a.numel()} elements outside rtol {rtol} + {atol_of_max}*max; "
                           f"worst excess {worst:.3e} at ref = {float(ref.flatten()[int(excess.argmax())]):.3e}")
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def states():

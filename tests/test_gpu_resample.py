@@ -1,14 +1,9 @@
 """Sample-rate conversion of the file ingest on the GPU: the HIP resampler (csrc/resample.hip) alone, as the (S,1,16000) segment
 producer, and under the file-level wrappers' `orig_freq` keyword.
 
-The yardstick is `yardstick()` below (the same text as in tests/test_resample_cpu.py; no conftest.py may carry it): torchaudio's documented
-default design evaluated in float64 numpy over ALL K = 2*width + P taps of every phase as a dense matrix product -- no compact table, no
-conv1d, nothing from the package.
-
-Tolerance (derived, nothing tuned, no rtol): the yardstick applies the same float32-rounded taps in float64, so the kernel differs from it
-only by the roundings of its float32 sums: for output sample m*Q + i at most
-    gamma_n * sum_j |h[i][j]| * |xmono[m*P + j]|,   gamma_n = n u / (1 - n u),   u = 2**-24,   n = (non-zero taps of phase i) + C
-plus one float32 ulp of the result for its final rounding.  Model outputs downstream of it: FWD_TOL, as everywhere in this suite."""
+The yardstick is `yardstick()` of tests/resample_yardstick.py, float64 numpy with nothing from the package; the derived tolerance
+(one stage, n = non-zero taps of the phase + C) stands in that module's docstring.  Model outputs downstream of it: FWD_TOL, as
+everywhere in this suite."""
 import math
 import os
 
@@ -16,96 +11,17 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import recipes as R
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import check, reference_models, same
+from resample_yardstick import design, signal, yardstick
+from yardstick_common import assert_within
 
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = 1e-4
 
-LPW, ROLLOFF, U = 6, 0.99, 2.0 ** -24
 RATES_TO_16K = [48000, 44100, 32000, 22050, 11025, 8000]
 PAIRS = [(r, 16000) for r in RATES_TO_16K] + [(16000, 48000)]
-
-
-def design(orig, new):
-    """(P, Q, width, K, dense float32 table (Q, K)) from the published formula, float64 rounded once to float32"""
-    g = math.gcd(orig, new)
-    P, Q = orig // g, new // g
-    base = min(P, Q) * ROLLOFF
-    width = int(math.ceil(LPW * P / base))
-    K = 2 * width + P
-    j = np.arange(K, dtype=np.float64)[None, :]
-    i = np.arange(Q, dtype=np.float64)[:, None]
-    t = np.clip(((j - width) / P - i / Q) * base, -LPW, LPW)
-    pt = np.pi * t
-    sinc = np.where(pt == 0, 1.0, np.sin(pt) / np.where(pt == 0, 1.0, pt))
-    h = (base / P) * sinc * np.cos(pt / (2 * LPW)) ** 2
-    return P, Q, width, K, h.astype(np.float32)
-
-
-def yardstick(xmono, orig, new, C=1):
-    """float64 resampling of the float64 mono signal `xmono` (N,) -> (y (L,), bound (L,))"""
-    P, Q, width, K, h32 = design(orig, new)
-    h = h32.astype(np.float64)
-    N = xmono.shape[0]
-    L = -((-Q * N) // P)
-    periods = N // P + 1
-    xpad = np.concatenate([np.zeros(width), np.asarray(xmono, dtype=np.float64), np.zeros(width + P)])
-    frames = np.lib.stride_tricks.sliding_window_view(xpad, K)[::P][:periods]            # (periods, K): xpad[m*P + j]
-    n = (h32 != 0).sum(axis=1) + C
-    gamma = n * U / (1 - n * U)                                                              # (Q,)
-    y, bound = np.empty((periods, Q)), np.empty((periods, Q))
-    step = max(1, 4_000_000 // K)
-    for a in range(0, periods, step):
-        f = np.ascontiguousarray(frames[a:a + step])
-        y[a:a + step] = f @ h.T
-        bound[a:a + step] = (np.abs(f) @ np.abs(h).T) * gamma[None, :]
-    y, bound = y.reshape(-1)[:L], bound.reshape(-1)[:L]
-    return y, bound + np.spacing(np.abs(y).astype(np.float32)).astype(np.float64)
-
-
-def signal(kind, C, N, rate, seed):
-    g = torch.Generator().manual_seed(seed)
-    if kind == "noise":
-        return 0.5 * torch.randn(C, N, generator=g)
-    t = torch.arange(N, dtype=torch.float64) / rate                                          # recording-like: partials + a noise floor
-    x = sum(a * torch.sin(2 * math.pi * f * t + p) for a, f, p in ((0.4, 220.0, 0.1), (0.2, 1730.0, 1.0), (0.1, 5200.0, 2.0)))
-    return (x[None, :].repeat(C, 1) * torch.linspace(1.0, 0.6, C, dtype=torch.float64)[:, None]).float() + 0.01 * torch.randn(C, N, generator=g)
-
-
-def assert_within(y, ref, bound, what):
-    y = np.asarray(y, dtype=np.float64).reshape(-1)
-    assert y.shape == ref.shape, f"{what}: {y.shape} vs {ref.shape}"
-    if y.size:
-        err = np.abs(y - ref)
-        worst = int(np.argmax(err - bound))
-        print(f"{what}: max err {err.max():.3e}, max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-        assert np.all(err <= bound), f"{what}: sample {worst}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def rel_err(a, ref):
-    a, ref = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(ref).detach().double().cpu()
-    return float((a - ref).abs().max() / (ref.abs().max() + 1e-30))
-
-
-def check(a, ref, tol, what=""):
-    assert tuple(a.shape) == tuple(ref.shape), f"{what}: shape {tuple(a.shape)} vs {tuple(ref.shape)}"
-    e = rel_err(a, ref)
-    print(f"{what}: rel err {e:.3e}")
-    assert e <= tol, f"{what}: rel err {e:.3e} > {tol}"
 
 
 def pq(orig, new):
@@ -223,16 +139,6 @@ def shipped_detector(awm, dev):
     return D.to(dev).eval()
 
 
-def init_models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd)
-    D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
 def compare_detections(got, want):
     assert set(got) == set(want)
     assert abs(got["mean_probability"] - want["mean_probability"]) <= FWD_TOL
@@ -264,7 +170,7 @@ def test_detect_waveform_orig_freq(awm, dev):
 
 
 def test_embed_waveform_orig_freq(awm, dev):
-    G, D = init_models(awm, dev)
+    G, D = reference_models(awm, dev)
     x48 = signal("recording", 2, 48000 * 2 + 15000, 48000, seed=83)
     msgs = torch.tensor([11, 22222, 65535])
     x16 = awm.resample(x48.cpu(), 48000, 16000)
@@ -303,20 +209,8 @@ def test_load_audio_on_the_device(awm, dev, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------ 5. orig_freq=None changes nothing
-def same(a, b):
-    if isinstance(a, dict):
-        return set(a) == set(b) and all(same(a[k], b[k]) for k in a)
-    if isinstance(a, (tuple, list)):
-        return len(a) == len(b) and all(same(u, v) for u, v in zip(a, b))
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, np.ndarray):
-        return np.array_equal(a, b)
-    return a == b or (isinstance(a, float) and math.isnan(a) and math.isnan(b))
-
-
 def test_orig_freq_none_is_the_old_call(awm, dev):
-    G, D = init_models(awm, dev)
+    G, D = reference_models(awm, dev)
     w = signal("recording", 1, 2 * 16000 + 5000, 16000, seed=90)
     msgs = torch.tensor([11, 22222, 65535])
     for kw in ({"orig_freq": None}, {"orig_freq": 16000}):

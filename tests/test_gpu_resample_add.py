@@ -2,16 +2,10 @@
 and adds it to every channel of the untouched recording in one launch; `ops.resample_add`, `resample_add`, and the `native_rate=True`
 keyword of embed_waveform / generate_watermarked_audio on top of it.
 
-The yardstick is `yardstick()` below (the text of tests/test_gpu_resample.py; no conftest.py may carry it): torchaudio's documented default
-design evaluated in float64 numpy over ALL K = 2*width + P taps of every phase as a dense matrix product -- nothing from the package.
-`design` is cached here: the table of 16000 -> 16001 has 16001 x 16014 entries.
-
-Tolerance (derived, nothing tuned, no rtol): with (u64, bound) = yardstick(delta[:n_d], 16000, R, C=1) cut to N samples,
-    |up - u64| <= bound                                     (the roundings of the float32 sums of the filter, see test_gpu_resample.py)
-    |out[c] - (x[c] + u64)| <= bound + spacing(float32(|x[c] + u64|))      (the same error carried through ONE more float32 add).
+The yardstick is `yardstick()` of tests/resample_yardstick.py, float64 numpy with nothing from the package; the two derived bounds
+(`up` against u64, `out[c]` through one more float32 add) stand in that module's docstring under "resample_add".
 Beyond that the kernel is held to bit identity: up is ops.resample of the same samples, out is one torch add.  Model outputs downstream
 of it: FWD_TOL, as everywhere in this suite."""
-import functools
 import math
 import wave
 
@@ -19,96 +13,16 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import recipes as R_
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import check, reference_models, same
+from resample_yardstick import LPW, ROLLOFF, signal, yardstick
+from yardstick_common import assert_within
 
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = 1e-4
 
-LPW, ROLLOFF, U = 6, 0.99, 2.0 ** -24
 RATES = [48000, 44100, 32000, 22050, 11025, 8000]
-
-
-@functools.lru_cache(maxsize=1)
-def design(orig, new):
-    """(P, Q, width, K, dense float32 table (Q, K)) from the published formula, float64 rounded once to float32"""
-    g = math.gcd(orig, new)
-    P, Q = orig // g, new // g
-    base = min(P, Q) * ROLLOFF
-    width = int(math.ceil(LPW * P / base))
-    K = 2 * width + P
-    j = np.arange(K, dtype=np.float64)[None, :]
-    i = np.arange(Q, dtype=np.float64)[:, None]
-    t = np.clip(((j - width) / P - i / Q) * base, -LPW, LPW)
-    pt = np.pi * t
-    sinc = np.where(pt == 0, 1.0, np.sin(pt) / np.where(pt == 0, 1.0, pt))
-    h = (base / P) * sinc * np.cos(pt / (2 * LPW)) ** 2
-    return P, Q, width, K, h.astype(np.float32)
-
-
-def yardstick(xmono, orig, new, C=1):
-    """float64 resampling of the float64 mono signal `xmono` (N,) -> (y (L,), bound (L,))"""
-    P, Q, width, K, h32 = design(orig, new)
-    h = h32.astype(np.float64)
-    N = xmono.shape[0]
-    L = -((-Q * N) // P)
-    periods = N // P + 1
-    xpad = np.concatenate([np.zeros(width), np.asarray(xmono, dtype=np.float64), np.zeros(width + P)])
-    frames = np.lib.stride_tricks.sliding_window_view(xpad, K)[::P][:periods]            # (periods, K): xpad[m*P + j]
-    n = (h32 != 0).sum(axis=1) + C
-    gamma = n * U / (1 - n * U)                                                              # (Q,)
-    y, bound = np.empty((periods, Q)), np.empty((periods, Q))
-    step = max(1, 4_000_000 // K)
-    for a in range(0, periods, step):
-        f = np.ascontiguousarray(frames[a:a + step])
-        y[a:a + step] = f @ h.T
-        bound[a:a + step] = (np.abs(f) @ np.abs(h).T) * gamma[None, :]
-    y, bound = y.reshape(-1)[:L], bound.reshape(-1)[:L]
-    return y, bound + np.spacing(np.abs(y).astype(np.float32)).astype(np.float64)
-
-
-def signal(kind, C, N, rate, seed):
-    g = torch.Generator().manual_seed(seed)
-    if kind == "noise":
-        return 0.5 * torch.randn(C, N, generator=g)
-    t = torch.arange(N, dtype=torch.float64) / rate                                          # recording-like: partials + a noise floor
-    x = sum(a * torch.sin(2 * math.pi * f * t + p) for a, f, p in ((0.4, 220.0, 0.1), (0.2, 1730.0, 1.0), (0.1, 5200.0, 2.0)))
-    return (x[None, :].repeat(C, 1) * torch.linspace(1.0, 0.6, C, dtype=torch.float64)[:, None]).float() + 0.01 * torch.randn(C, N, generator=g)
-
-
-def assert_within(y, ref, bound, what):
-    y = np.asarray(y, dtype=np.float64).reshape(-1)
-    assert y.shape == ref.shape, f"{what}: {y.shape} vs {ref.shape}"
-    if y.size:
-        err = np.abs(y - ref)
-        worst = int(np.argmax(err - bound))
-        print(f"{what}: max err {err.max():.3e}, max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-        assert np.all(err <= bound), f"{what}: sample {worst}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def rel_err(a, ref):
-    a, ref = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(ref).detach().double().cpu()
-    return float((a - ref).abs().max() / (ref.abs().max() + 1e-30))
-
-
-def check(a, ref, tol, what=""):
-    assert tuple(a.shape) == tuple(ref.shape), f"{what}: shape {tuple(a.shape)} vs {tuple(ref.shape)}"
-    e = rel_err(a, ref)
-    print(f"{what}: rel err {e:.3e}")
-    assert e <= tol, f"{what}: rel err {e:.3e} > {tol}"
 
 
 def pq(delta_rate, rate):
@@ -345,31 +259,9 @@ def test_arguments(awm, dev):
 
 
 # ------------------------------------------------------------------------------------------ B8 - B10. the file-level entry points
-def init_models(awm, dev):
-    gsd, dsd = R_.reference_layout_init()
-    R_.perturb_bn_(gsd, R_.BN_SEED_G)
-    R_.perturb_bn_(dsd, R_.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd)
-    D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
-def same(a, b):
-    if isinstance(a, dict):
-        return set(a) == set(b) and all(same(a[k], b[k]) for k in a)
-    if isinstance(a, (tuple, list)):
-        return len(a) == len(b) and all(same(u, v) for u, v in zip(a, b))
-    if isinstance(a, torch.Tensor):
-        return torch.equal(a, b)
-    if isinstance(a, np.ndarray):
-        return np.array_equal(a, b)
-    return a == b or (isinstance(a, float) and math.isnan(a) and math.isnan(b))
-
-
 @pytest.fixture(scope="module")
 def models(awm, dev):
-    return init_models(awm, dev)
+    return reference_models(awm, dev)
 
 
 def test_embed_waveform_native_rate(awm, dev, models):

@@ -7,23 +7,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_parity import FWD_TOL, check, rel_err
-from test_gpu_tail_in_head import FP32_ULP, bits_equal, fp64_losses, frames, head_params, messages, p, rnd, st
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import p, rel_err, rnd, st
+from test_gpu_parity import FWD_TOL, check
+from test_gpu_tail_in_head import FP32_ULP, bits_equal, fp64_losses, frames, head_params, messages
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------- stem

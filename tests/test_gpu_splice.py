@@ -16,7 +16,8 @@ import pytest
 import torch
 
 import splice_yardstick as Y
-from oracle import recipes as R
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import _spy, p, reference_models, st
 from oracle import wm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -26,27 +27,6 @@ SEED, DRAW, ROW0 = (7 << 32) + 1, 1, 5
 CUT = dict(max_spans=2, p_span=0.5, len_lo=800, len_hi=6400, p_original=1 / 3, p_silence=1 / 3)
 FP32_ULP = 2.0 ** -23
 SENTINEL = 0x55555555
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def p(t):
-    return None if t is None else t.data_ptr()
-
-
-def st():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def bits(a):
@@ -415,27 +395,6 @@ SPIED = ("wm_splice", "wm_splice_bwd", "wm_bce_masked_fwd", "wm_bce_masked_bwd",
          "wm_headN_bwd_bce", "wm_headN_fwd", "wm_headN_bwd", "wm_loc_score")
 
 
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev).train(), D.to(dev).train()
-
-
-def _spy(mp, lib, names):
-    counts = {}
-    for name in names:
-        real = getattr(lib, name)
-
-        def spy(*a, _real=real, _name=name):
-            counts[_name] = counts.get(_name, 0) + 1
-            return _real(*a)
-        mp.setattr(lib, name, spy)
-    return counts
-
-
 def _golden_detector(awm, dev):
     ck = np.load(os.path.join(os.path.dirname(__file__), "golden", "detector_best_unprefixed.npz"))
     D = awm.Detector(16)
@@ -444,7 +403,7 @@ def _golden_detector(awm, dev):
 
 
 def test_train_step_with_and_without_tamper(awm, dev, monkeypatch):
-    G0, D0 = _models(awm, dev)
+    G0, D0 = (m.train() for m in reference_models(awm, dev))
     s = O.synthetic_clips(NET_B, seed=41, T=NET_T).to(dev)
     msg = torch.tensor([3, 60001], device=dev)
     runs = {}

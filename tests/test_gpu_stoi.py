@@ -18,31 +18,15 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import recipes as R
 from oracle import wm_oracle as O
 
 import stoi_yardstick as Y
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import bits, reference_models
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL32 = float(np.float32(Y.SENTINEL))
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def off_by_one_float(a, dev):
@@ -177,18 +161,9 @@ def test_public_stoi_keeps_the_leading_shape(awm, dev):
     assert not cpu.is_cuda and float((cpu - want.cpu()).abs().max()) <= bar(), "the host path is the float64 restatement"
 
 
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
 def test_evaluate_robustness_quality_columns(awm, dev):
     from awm_amd import ops
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     B, T = 4, 16000
     batches = [O.synthetic_clips(B, seed=71, T=T)]
     messages = [torch.tensor([3, 60001, 77, 12345])]
@@ -225,7 +200,7 @@ def test_evaluate_robustness_quality_columns(awm, dev):
 
 def test_file_level_stoi(awm, dev):
     from awm_amd import ops
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     n = 51200                                            # 3.2 s at 16 kHz: three whole segments and a remainder
     wave = O.synthetic_clips(4, seed=81, T=16000).reshape(1, -1)[:, :n].contiguous()
     torch.manual_seed(5)

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import _spy, p, rnd, st
 from oracle import wm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -18,31 +20,6 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(4, 2, 64), (4, 2, 200), (4, 2, 320), (3, 1, 36)]
 WIDTHS = [1, 17, 9, 33]          # both exact-width builds, and the run-time width below and above 32
 FP32_ULP = 2.0 ** -23
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def p(t):
-    return None if t is None else t.data_ptr()
-
-
-def st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def bits_equal(a, b):
@@ -233,18 +210,6 @@ def _models(awm, dev, bits, seed=5):
     torch.manual_seed(seed)
     G, D = awm.Generator(bits), awm.Detector(bits)
     return G.to(dev).train(), D.to(dev).train()
-
-
-def _spy(monkeypatch, lib, names):
-    counts = {}
-    for name in names:
-        real = getattr(lib, name)
-
-        def spy(*a, _real=real, _name=name):
-            counts[_name] = counts.get(_name, 0) + 1
-            return _real(*a)
-        monkeypatch.setattr(lib, name, spy)
-    return counts
 
 
 SPIED = ("wm_bn_add_relu_mask", "wm_bn_add_relu", "wm_bce_fwd", "wm_bce_bwd", "wm_headN_tail_fwd", "wm_head1_tail_fwd",

@@ -18,33 +18,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import recipes as R
 from oracle import wm_oracle as O
 
 import time_warp_yardstick as Y
+from gpu_support import awm, dev  # noqa: F401
+from gpu_support import bits, reference_models, to_dev
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def awm():
-    import awm_amd
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    awm_amd.lib.load()
-    return awm_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def to_dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def off_by_one_float(a, dev):
@@ -254,18 +234,9 @@ def test_other_table_sizes(awm, dev, zeros, res):
 
 
 # ------------------------------------------------------------------------------------------ 8., 9. the training step and the robustness loop
-def _models(awm, dev):
-    gsd, dsd = R.reference_layout_init()
-    R.perturb_bn_(gsd, R.BN_SEED_G)
-    R.perturb_bn_(dsd, R.BN_SEED_D)
-    G, D = awm.Generator(16), awm.Detector(16)
-    G.load_state_dict(gsd); D.load_state_dict(dsd)
-    return G.to(dev), D.to(dev)
-
-
 def test_train_step_through_the_warp(awm, dev):
     """T = 2048: the shortest clip the step's loudness loss accepts"""
-    G, D = _models(awm, dev)
+    G, D = reference_models(awm, dev)
     s = O.synthetic_clips(2, seed=41, T=2048).to(dev)
     msg = torch.tensor([3, 60001], device=dev)
     codec = torch.nn.Sequential(awm.TimeWarp(speed=(0.9, 1.1), flutter_hz=4.0, flutter_depth=0.01, seed=3), awm.PcmCodec(grad="straight_through"))

@@ -1,13 +1,7 @@
 """Sample-rate conversion of the file ingest, on the host: `resample` / `Resample` / `load_audio` without torchaudio.
 
-The yardstick is `yardstick()` below: torchaudio's documented default design (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99)
-evaluated in float64 numpy over ALL K = 2*width + P taps of every phase as a dense matrix product -- no compact table, no conv1d, nothing
-from the package -- so a mistake the package's CPU twin and its kernel share (say in the compact table's first index) shows here.
-
-Tolerance (derived, nothing tuned, no rtol): the yardstick applies the same float32-rounded taps in float64, so the package differs from it
-only by the roundings of its float32 sums.  For output sample m*Q + i that is at most
-    gamma_n * sum_j |h[i][j]| * |xmono[m*P + j]|,   gamma_n = n u / (1 - n u),   u = 2**-24,   n = (non-zero taps of phase i) + C
-(n - C products and additions of the filter, C roundings of the channel mean), plus one float32 ulp of the result for its final rounding."""
+The yardstick is `yardstick()` of tests/resample_yardstick.py, float64 numpy with nothing from the package; the derived tolerance
+(one stage, n = non-zero taps of the phase + C) stands in that module's docstring."""
 import math
 import struct
 import wave
@@ -18,66 +12,11 @@ import torch
 
 import awm_amd
 from awm_amd import inference, ops
+from resample_yardstick import design, signal, yardstick
+from yardstick_common import assert_within
 
-LPW, ROLLOFF, U = 6, 0.99, 2.0 ** -24
 RATES_TO_16K = [48000, 44100, 32000, 22050, 11025, 8000]
 PAIRS = [(r, 16000) for r in RATES_TO_16K] + [(16000, 48000)]
-
-
-def design(orig, new):
-    """(P, Q, width, K, dense float32 table (Q, K)) from the published formula, float64 rounded once to float32"""
-    g = math.gcd(orig, new)
-    P, Q = orig // g, new // g
-    base = min(P, Q) * ROLLOFF
-    width = int(math.ceil(LPW * P / base))
-    K = 2 * width + P
-    j = np.arange(K, dtype=np.float64)[None, :]
-    i = np.arange(Q, dtype=np.float64)[:, None]
-    t = np.clip(((j - width) / P - i / Q) * base, -LPW, LPW)
-    pt = np.pi * t
-    sinc = np.where(pt == 0, 1.0, np.sin(pt) / np.where(pt == 0, 1.0, pt))
-    h = (base / P) * sinc * np.cos(pt / (2 * LPW)) ** 2
-    return P, Q, width, K, h.astype(np.float32)
-
-
-def yardstick(xmono, orig, new, C=1):
-    """float64 resampling of the float64 mono signal `xmono` (N,) -> (y (L,), bound (L,))"""
-    P, Q, width, K, h32 = design(orig, new)
-    h = h32.astype(np.float64)
-    N = xmono.shape[0]
-    L = -((-Q * N) // P)
-    periods = N // P + 1
-    xpad = np.concatenate([np.zeros(width), np.asarray(xmono, dtype=np.float64), np.zeros(width + P)])
-    frames = np.lib.stride_tricks.sliding_window_view(xpad, K)[::P][:periods]            # (periods, K): xpad[m*P + j]
-    n = (h32 != 0).sum(axis=1) + C
-    gamma = n * U / (1 - n * U)                                                              # (Q,)
-    y, bound = np.empty((periods, Q)), np.empty((periods, Q))
-    step = max(1, 4_000_000 // K)
-    for a in range(0, periods, step):
-        f = np.ascontiguousarray(frames[a:a + step])
-        y[a:a + step] = f @ h.T
-        bound[a:a + step] = (np.abs(f) @ np.abs(h).T) * gamma[None, :]
-    y, bound = y.reshape(-1)[:L], bound.reshape(-1)[:L]
-    return y, bound + np.spacing(np.abs(y).astype(np.float32)).astype(np.float64)
-
-
-def signal(kind, C, N, rate, seed):
-    g = torch.Generator().manual_seed(seed)
-    if kind == "noise":
-        return 0.5 * torch.randn(C, N, generator=g)
-    t = torch.arange(N, dtype=torch.float64) / rate                                          # recording-like: partials + a noise floor
-    x = sum(a * torch.sin(2 * math.pi * f * t + p) for a, f, p in ((0.4, 220.0, 0.1), (0.2, 1730.0, 1.0), (0.1, 5200.0, 2.0)))
-    return (x[None, :].repeat(C, 1) * torch.linspace(1.0, 0.6, C, dtype=torch.float64)[:, None]).float() + 0.01 * torch.randn(C, N, generator=g)
-
-
-def assert_within(y, ref, bound, what):
-    y = np.asarray(y, dtype=np.float64).reshape(-1)
-    assert y.shape == ref.shape, f"{what}: {y.shape} vs {ref.shape}"
-    if y.size:
-        err = np.abs(y - ref)
-        worst = int(np.argmax(err - bound))
-        print(f"{what}: max err {err.max():.3e}, max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-        assert np.all(err <= bound), f"{what}: sample {worst}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
 
 
 def lengths(P):

@@ -1,18 +1,8 @@
 """The resampling attack on the host: the adjoint table of the resampler, attacks.Resampled on CPU tensors, resample(mixdown=False), exports.
 
-The yardstick is the text below (design() as in tests/test_resample_cpu.py; no conftest.py may carry it): torchaudio's documented default
-design evaluated in float64 numpy over ALL K = 2*width + P taps of every phase.  One row of the resampler is the (L, N) matrix
-    A[m*Q + i][m*P + j - width] = h[i][j]
-and apply64 / adjoint64 are A @ x and A.T @ dy written as dense products over the periods -- no compact table, no conv1d, nothing from the
-package.  Nothing from the package serves as a yardstick except in the bit-identity checks.
-
-Tolerance (derived, nothing tuned, no rtol): the yardstick applies the same float32-rounded taps in float64, so the package differs from it
-only by the roundings of its float32 sums.  One stage, output sample of phase i (or input sample of adjoint phase p):
-    gamma_n * sum |h| |x|,   gamma_n = n u / (1 - n u),   u = 2**-24,   n = (non-zero taps of the phase) + 1
-plus one float32 ulp of the result.  Two stages (y = B (A x)): the first stage's bound b_A goes through |B|, the second adds its own:
-    |B| b_A + gamma_B * |B| |A x| + ulp(y);        for the gradient A.T (B.T g):   |A|.T b_B + gamma * |A|.T |B.T g| + ulp."""
+The yardstick is apply64 / adjoint64 / attack64 / attack_grad64 of tests/resample_yardstick.py, float64 numpy with nothing from the
+package; the derived one-stage and two-stage tolerances stand in that module's docstring."""
 import ctypes
-import math
 import os
 
 import numpy as np
@@ -21,112 +11,11 @@ import torch
 
 import awm_amd
 from awm_amd import _lib, ops
+from resample_yardstick import adjoint64, apply64, attack64, attack_grad64, design, rows_signal
+from yardstick_common import assert_within
 
-LPW, ROLLOFF, U = 6, 0.99, 2.0 ** -24
 TABLE_PAIRS = [(16000, 8000), (8000, 16000), (16000, 12000), (16000, 44100), (44100, 16000)]
 RATES = [8000, 12000, 44100]
-
-
-def design(orig, new):
-    """(P, Q, width, K, dense float32 table (Q, K)) from the published formula, float64 rounded once to float32"""
-    g = math.gcd(orig, new)
-    P, Q = orig // g, new // g
-    base = min(P, Q) * ROLLOFF
-    width = int(math.ceil(LPW * P / base))
-    K = 2 * width + P
-    j = np.arange(K, dtype=np.float64)[None, :]
-    i = np.arange(Q, dtype=np.float64)[:, None]
-    t = np.clip(((j - width) / P - i / Q) * base, -LPW, LPW)
-    pt = np.pi * t
-    sinc = np.where(pt == 0, 1.0, np.sin(pt) / np.where(pt == 0, 1.0, pt))
-    h = (base / P) * sinc * np.cos(pt / (2 * LPW)) ** 2
-    return P, Q, width, K, h.astype(np.float32)
-
-
-def apply64(h, P, width, x, L):
-    """A @ x in float64 for the (Q, K) table h (or |h|): y[m*Q + i] = sum_j h[i][j] * xpad[m*P + j], the first L samples"""
-    Q, K = h.shape
-    N = x.shape[0]
-    periods = -(-L // Q)
-    xpad = np.zeros(max(N + 2 * width + P, (periods - 1) * P + K))
-    xpad[width:width + N] = x
-    frames = np.lib.stride_tricks.sliding_window_view(xpad, K)[::P][:periods]               # (periods, K): xpad[m*P + j]
-    return (frames @ h.T).reshape(-1)[:L]
-
-
-def adjoint64(h, P, width, dy, N):
-    """A.T @ dy in float64, A the (L, N) matrix of the table h (or |h|), L = len(dy): period m hands dy[m*Q + i] * h[i][j] to xpad[m*P + j]"""
-    Q, K = h.shape
-    L = dy.shape[0]
-    periods = -(-L // Q)
-    d = np.zeros(periods * Q)
-    d[:L] = dy
-    F = d.reshape(periods, Q) @ h                                                            # (periods, K)
-    buf = np.zeros(max((periods - 1) * P + K, width + N))
-    for j in range(K):
-        buf[j:j + (periods - 1) * P + 1:P] += F[:, j]
-    return buf[width:width + N]
-
-
-def ulp32(v):
-    return np.spacing(np.abs(v).astype(np.float32)).astype(np.float64)
-
-
-def gamma(n):
-    return n * U / (1 - n * U)
-
-
-def forward_gamma(h32, L):
-    """gamma_n of output sample o < L: n = non-zero taps of its phase o % Q, + 1"""
-    return gamma((h32 != 0).sum(axis=1) + 1.0)[np.arange(L) % h32.shape[0]]
-
-
-def adjoint_gamma(h32, P, width, N):
-    """gamma_n of input sample n < N: the taps of adjoint phase p = n % P are the columns j = p + width (mod P) of the table"""
-    col = (h32 != 0).sum(axis=0)
-    nnz = np.array([col[(p + width) % P::P].sum() for p in range(P)], dtype=np.float64)
-    return gamma(nnz + 1.0)[np.arange(N) % P]
-
-
-def attack64(x, rate, sr=16000):
-    """float64 up(down(x))[:T] of one row and its composed bound"""
-    T = x.shape[0]
-    Pd, Qd, wd, _, hd32 = design(sr, rate)
-    Pu, Qu, wu, _, hu32 = design(rate, sr)
-    hd, hu = hd32.astype(np.float64), hu32.astype(np.float64)
-    L1 = -((-Qd * T) // Pd)
-    v = apply64(hd, Pd, wd, x, L1)
-    b1 = forward_gamma(hd32, L1) * apply64(np.abs(hd), Pd, wd, np.abs(x), L1) + ulp32(v)
-    y = apply64(hu, Pu, wu, v, T)
-    bound = apply64(np.abs(hu), Pu, wu, b1, T) + forward_gamma(hu32, T) * apply64(np.abs(hu), Pu, wu, np.abs(v), T) + ulp32(y)
-    return y, bound
-
-
-def attack_grad64(g, rate, sr=16000):
-    """float64 A_down.T @ (A_up[:T].T @ g) of one row and its composed bound"""
-    T = g.shape[0]
-    Pd, Qd, wd, _, hd32 = design(sr, rate)
-    Pu, Qu, wu, _, hu32 = design(rate, sr)
-    hd, hu = hd32.astype(np.float64), hu32.astype(np.float64)
-    L1 = -((-Qd * T) // Pd)
-    v = adjoint64(hu, Pu, wu, g, L1)
-    b_up = adjoint_gamma(hu32, Pu, wu, L1) * adjoint64(np.abs(hu), Pu, wu, np.abs(g), L1) + ulp32(v)
-    dx = adjoint64(hd, Pd, wd, v, T)
-    bound = adjoint64(np.abs(hd), Pd, wd, b_up, T) + adjoint_gamma(hd32, Pd, wd, T) * adjoint64(np.abs(hd), Pd, wd, np.abs(v), T) + ulp32(dx)
-    return dx, bound
-
-
-def assert_within(y, ref, bound, what):
-    y = np.asarray(y, dtype=np.float64).reshape(-1)
-    assert y.shape == ref.shape, f"{what}: {y.shape} vs {ref.shape}"
-    err = np.abs(y - ref)
-    worst = int(np.argmax(err - bound))
-    print(f"{what}: max err {err.max():.3e}, max err/bound {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-    assert np.all(err <= bound), f"{what}: sample {worst}: err {err[worst]:.3e} > bound {bound[worst]:.3e}"
-
-
-def rows_signal(rows, n, seed):
-    return 0.5 * torch.randn(rows, n, generator=torch.Generator().manual_seed(1000 * seed + n))
 
 
 def dense_matrix(orig, new, N, L):

@@ -24,8 +24,8 @@ import math
 import numpy as np
 
 from draw_yardstick import PARAM, PARAM2, RIR_HIGH, WARP, WARP_PHASE, affine32, key_of, philox4x32_10, unit  # noqa: F401
+from yardstick_common import gamma
 
-U = 2.0 ** -24
 TILE = 256                                        # the samples a workgroup of csrc/time_warp.hip takes at a time
 NS = (1, 2, 33, TILE - 1, TILE, TILE + 1, 1025, 4099, 16000)
 SPEEDS = (0.5, 0.8, 1.0, 1.25, 2.0)
@@ -34,10 +34,6 @@ SPEEDS = (0.5, 0.8, 1.0, 1.25, 2.0)
 FLUTTERS = (None, (4.0, 0.01, 0.3), (0.5, 0.25, 0.5))
 SAMPLE_RATE = 16000.0
 ZEROS, RES = 16, 512
-
-
-def gamma(m):
-    return m * U / (1.0 - m * U)
 
 
 # ------------------------------------------------------------------------------------------ the table
