@@ -1,578 +1,9 @@
-// 64 -> 64 channel 1-D convolutions on [B,64,T] fp32 frames as implicit GEMMs on the gfx950
-// fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32, frees the VALU for the fused
-// prologue / epilogue work).
-//
-// Replaces, for the hot path of py/main16.py:
-//   * ResBlock's two Conv1d(64,64,3,padding=1) (+ the BatchNorm1d / ReLU around them)   :115-121
-//   * Generator.decoder[0] = ConvTranspose1d(64,64,7,padding=3) (+ the embedding add)      :144,156-159
-//   * their data-gradients (same kernel, re-packed weights) and weight-gradients.
-//
-// One persistent 256-thread workgroup per CU streams (clip, time-tile) tiles:
-//   global --(dwordx4, software-pipelined one tile ahead, through registers so the prologue
-//   transform can be applied)--> LDS [64][NT+halo]  --ds_read_b32--> MFMA B operand
-//   packed weights [tap][cin][cout] live in LDS for the whole kernel --> MFMA A operand
-//   D tile (cout x time) leaves the accumulators as 128-B row segments (time is contiguous).
-#include "wm_common.hpp"
-using namespace wm;
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-#ifdef WM_STAMP
-// diagnostic build only (-DWM_STAMP): per-wave cycle totals of the kernel's phases
-__device__ unsigned long long* g_wm_stamp = nullptr;
-#define STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
-#else
-#define STAMP(var)
-#endif
+// The bf16x6 / f16 split families of the 64 -> 64 convolutions (conv64.hpp): the k3 forward and data-gradient kernels
+// (phase-serial conv64bf, pipelined conv64bf3), the two 7-tap kernels with their weight gradient, the k3 weight gradients.
+// The fp32, inference and fused families are conv64_fp32.hip, conv64_eval.hip and conv64_dwgrad.hip.
+#include "conv64.hpp"
 
 namespace {
-
-enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_ADDVEC = 2, PRO_BNBWD = 3 };
-enum { EPI_BIAS = 0, EPI_RELUMASK = 1, EPI_ADD = 2, EPI_NONE = 3, EPI_BNADDRELU = 4,    // 4: relu(e1 + (acc + bias) * ea + eb), conv64bf3 only
-       EPI_BIASELU = 5, EPI_BIASADDELU = 6, EPI_MULDELU = 7,
-       EPI_ADDSTATS = 8 };    // dwgrad64bf only: EPI_ADD, then the ReLU mask of the PREVIOUS block and its two BatchNorm sums   // main14b_2's 64-channel blocks (conv64bf_kernel only): elu(acc + bias),
-                                                                 // elu(acc + bias + e1), acc * ELU'(e1) with e1 = the ELU output y
-
-struct Conv64Args {
-    const float* x;     // [B,64,T] primary input
-    const float* x2;    // [B,64,T] second input (PRO_BNBWD)
-    const float* wp;    // packed weights [KW][64 in][64 out]
-    const float* pa;    // prologue per-channel a  (BNRELU: scale, BNBWD: A, ADDVEC: vec[B,64])
-    const float* pb;    // prologue per-channel b  (BNRELU: shift, BNBWD: B)
-    const float* pc;    // prologue per-channel c  (BNBWD: C)
-    const float* bias;  // [64] (EPI_BIAS)
-    const float* e1;    // [B,64,T] epilogue tensor (RELUMASK: pre-BN activation, ADD: addend)
-    const float* ea;    // [64] epilogue scale (RELUMASK)
-    const float* eb;    // [64] epilogue shift (RELUMASK)
-    float* y;           // [B,64,T]
-    float* stats;       // [gridDim.x][2][64] partial sums or nullptr
-    int B, T;
-};
-
-template <int PRO>
-__device__ __forceinline__ float pro_apply(float v, float v2, float ca, float cb, float cc, float cl = 0.f) {
-    if (PRO == PRO_BNRELU) return fmaxf(fmaf(v, ca, cb), 0.f);
-    if (PRO == PRO_ADDVEC) return v + ca;
-    if (PRO == PRO_BNBWD) return fmaf(ca, v, fmaf(cc, v2, cb)) + cl;      // cb + cl: offset as hi + lo words (pb[0..63], pb[64..127])
-    return v;
-}
-
-template <int KW, int NT, int PRO, int EPI, bool STATS>
-__global__ __launch_bounds__(256) void conv64_kernel(Conv64Args a) {
-    constexpr int PAD = KW / 2;
-    constexpr int XS = NT + 8;            // LDS row stride; main part starts at column 4 (16-B aligned)
-    constexpr int NTW = NT / 4;           // time columns per wave
-    constexpr int NN = NTW / 32;          // 32-wide N tiles per wave
-    constexpr int QR = NT / 4;            // float4 per row
-    constexpr int NV = 64 * QR / 256;     // float4 per thread per staged tensor
-    constexpr int HTOT = 64 * 2 * PAD;    // halo elements per tile
-    constexpr int HN = (HTOT + 255) / 256;
-    constexpr bool TWO = (PRO == PRO_BNBWD);
-    constexpr bool E1 = (EPI == EPI_RELUMASK || EPI == EPI_ADD);
-
-    extern __shared__ __align__(16) float smem[];
-    float* Ws = smem;                     // [KW*64][64]
-    float* Xs = smem + KW * 4096;         // [64][XS]
-    float* Cs = Xs + 64 * XS;             // [6][64] per-channel constants: pa pb pc bias ea eb
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int T = a.T;
-    const int tilesPerClip = (T + NT - 1) / NT;
-    const int ntiles = a.B * tilesPerClip;
-
-    float4 st[NV];
-    float4 st2[TWO ? NV : 1];
-    float hl[HN], hl2[TWO ? HN : 1];
-
-    // Loads are UNCONDITIONAL (addresses clamped into the clip) and the out-of-range masking happens when the tile is
-    // written to LDS: a per-element "load or zero" select makes hipcc branch around every load and drain vmcnt at
-    // each join -- measured 15 K cycles of serialised round trips per tile in the two-tensor variants.
-    auto load_tile = [&](int tile) {
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        const float* xb = a.x + (size_t)b * 64 * T;
-        const float* xb2 = TWO ? a.x2 + (size_t)b * 64 * T : nullptr;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * 256, c = idx / QR, q = idx % QR;
-            const int t = min(t0 + 4 * q, T - 4);
-            st[i] = *reinterpret_cast<const float4*>(xb + (size_t)c * T + t);
-            if (TWO) st2[i] = *reinterpret_cast<const float4*>(xb2 + (size_t)c * T + t);
-        }
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int idx = min(tid + i * 256, HTOT - 1);
-            const int c = idx / (2 * PAD), h = idx % (2 * PAD);
-            const int t = min(max((h < PAD) ? t0 - PAD + h : t0 + NT + (h - PAD), 0), T - 1);
-            hl[i] = xb[(size_t)c * T + t];
-            if (TWO) hl2[i] = xb2[(size_t)c * T + t];
-        }
-    };
-    auto write_tile = [&](int tile) {
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * 256, c = idx / QR, q = idx % QR, t = t0 + 4 * q;
-            float4 v = st[i];
-            if (PRO != PRO_NONE) {
-                const float ca = (PRO == PRO_ADDVEC) ? a.pa[b * 64 + c] : Cs[c];
-                const float cb = Cs[64 + c], cc = Cs[128 + c], cl = TWO ? Cs[192 + c] : 0.f;
-                const float4 w = TWO ? st2[i] : v;
-                v.x = pro_apply<PRO>(v.x, w.x, ca, cb, cc, cl);
-                v.y = pro_apply<PRO>(v.y, w.y, ca, cb, cc, cl);
-                v.z = pro_apply<PRO>(v.z, w.z, ca, cb, cc, cl);
-                v.w = pro_apply<PRO>(v.w, w.w, ca, cb, cc, cl);
-            }
-            if (t >= T) v = make_float4(0.f, 0.f, 0.f, 0.f);     // T % 4 == 0: a float4 is all in or all out
-            *reinterpret_cast<float4*>(Xs + c * XS + 4 + 4 * q) = v;
-        }
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int idx = tid + i * 256;
-            if (idx < HTOT) {
-                const int c = idx / (2 * PAD), h = idx % (2 * PAD);
-                const int t = (h < PAD) ? t0 - PAD + h : t0 + NT + (h - PAD);
-                float v = hl[i];
-                if (PRO != PRO_NONE) {
-                    const float ca = (PRO == PRO_ADDVEC) ? a.pa[b * 64 + c] : Cs[c];
-                    v = pro_apply<PRO>(v, TWO ? hl2[i] : v, ca, Cs[64 + c], Cs[128 + c], TWO ? Cs[192 + c] : 0.f);
-                }
-                if (t < 0 || t >= T) v = 0.f;
-                Xs[c * XS + ((h < PAD) ? 4 - PAD + h : 4 + NT + (h - PAD))] = v;
-            }
-        }
-    };
-
-    int tile = blockIdx.x;
-    if (tile < ntiles) load_tile(tile);
-    // resident operands: packed weights + per-channel constants
-    for (int i = tid; i < KW * 1024; i += 256)
-        reinterpret_cast<float4*>(Ws)[i] = reinterpret_cast<const float4*>(a.wp)[i];
-    if (tid < 64) {
-        Cs[tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pa[tid] : 0.f;
-        Cs[64 + tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pb[tid] : 0.f;
-        Cs[128 + tid] = (PRO == PRO_BNBWD) ? a.pc[tid] : 0.f;
-        Cs[192 + tid] = (EPI == EPI_BIAS && a.bias) ? a.bias[tid] : 0.f;
-        Cs[256 + tid] = (EPI == EPI_RELUMASK) ? a.ea[tid] : 0.f;
-        Cs[320 + tid] = (EPI == EPI_RELUMASK) ? a.eb[tid] : 0.f;
-    }
-    __syncthreads();
-    if (tile < ntiles) write_tile(tile);
-    __syncthreads();
-
-    float s1[STATS ? 32 : 1], s2[STATS ? 32 : 1];
-    if (STATS) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    }
-
-#ifdef WM_STAMP
-    unsigned long long tm[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    while (tile < ntiles) {
-        STAMP(ts0);
-        const int next = tile + gridDim.x;
-        if (next < ntiles) load_tile(next);           // in flight while the matrix cores work
-
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        float e1r[E1 ? 2 * NN * 16 : 1];
-        if (E1) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NN; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int co = mt * 32 + mfma_row(r, half), t = min(t0 + wave * NTW + nt * 32 + l31, T - 1);
-                        e1r[(mt * NN + nt) * 16 + r] = a.e1[((size_t)b * 64 + co) * T + t];      // masked at use (t < T)
-                    }
-        }
-
-        STAMP(ts1);
-        f32x16 acc[2][NN];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NN; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-
-        const float* xcol = Xs + half * XS + (4 - PAD) + wave * NTW + l31;
-        const float* wrow = Ws + half * 64 + l31;
-#pragma unroll 1
-        for (int tap = 0; tap < KW; ++tap) {
-#pragma unroll 8
-            for (int cp = 0; cp < 32; ++cp) {
-                const float* wk = wrow + (tap * 64 + 2 * cp) * 64;
-                const float* xk = xcol + (2 * cp) * XS + tap;
-                const float a0 = wk[0], a1 = wk[32];
-                float bv[NN];
-#pragma unroll
-                for (int nt = 0; nt < NN; ++nt) bv[nt] = xk[nt * 32];
-#pragma unroll
-                for (int nt = 0; nt < NN; ++nt) {
-                    acc[0][nt] = mfma32(a0, bv[nt], acc[0][nt]);
-                    acc[1][nt] = mfma32(a1, bv[nt], acc[1][nt]);
-                }
-            }
-        }
-
-        STAMP(ts2);
-        // epilogue straight from the accumulators
-        float* yb = a.y + (size_t)b * 64 * T;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NN; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = mt * 32 + mfma_row(r, half), t = t0 + wave * NTW + nt * 32 + l31;
-                    float v = acc[mt][nt][r];
-                    float q = 0.f;
-                    if (EPI == EPI_BIAS) v += Cs[192 + co];
-                    if (EPI == EPI_RELUMASK) {
-                        q = e1r[(mt * NN + nt) * 16 + r];
-                        v = (fmaf(q, Cs[256 + co], Cs[320 + co]) > 0.f) ? v : 0.f;
-                    }
-                    if (EPI == EPI_ADD) v += e1r[(mt * NN + nt) * 16 + r];
-                    if (t < T) {
-                        yb[(size_t)co * T + t] = v;
-                        if (STATS) {
-                            s1[mt * 16 + r] += v;
-                            s2[mt * 16 + r] += (EPI == EPI_RELUMASK) ? v * q : v * v;
-                        }
-                    }
-                }
-
-        STAMP(ts3);
-        __syncthreads();                              // every wave is done with Xs
-        STAMP(ts4);
-        if (next < ntiles) write_tile(next);
-        STAMP(ts5);
-        __syncthreads();
-        STAMP(ts6);
-#ifdef WM_STAMP
-        tm[0] += ts1 - ts0; tm[1] += ts2 - ts1; tm[2] += ts3 - ts2; tm[3] += ts4 - ts3; tm[4] += ts5 - ts4; tm[5] += ts6 - ts5;
-#endif
-        tile = next;
-    }
-#ifdef WM_STAMP
-    if (g_wm_stamp && lane == 0) {
-        unsigned long long* d = g_wm_stamp + ((size_t)blockIdx.x * 4 + wave) * 6;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = tm[i];
-    }
-#endif
-
-    if (STATS) {
-        float* red = Xs;                              // [4 waves][2][64]
-#pragma unroll
-        for (int j = 0; j < 32; ++j) { s1[j] = half_wave_sum(s1[j]); s2[j] = half_wave_sum(s2[j]); }
-        if (l31 == 0) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = mt * 32 + mfma_row(r, half);
-                    red[wave * 128 + co] = s1[mt * 16 + r];
-                    red[wave * 128 + 64 + co] = s2[mt * 16 + r];
-                }
-        }
-        __syncthreads();
-        if (tid < 128)
-            a.stats[(size_t)blockIdx.x * 128 + tid] = red[tid] + red[128 + tid] + red[256 + tid] + red[384 + tid];
-    }
-}
-
-template <int KW, int NT, int PRO, int EPI, bool STATS>
-int launch_conv64(const Conv64Args& a, hipStream_t stream) {
-    constexpr size_t lds = (size_t)(KW * 4096 + 64 * (NT + 8) + 6 * 64) * sizeof(float);
-    static wm::DevOnce attr_done;
-    auto kern = conv64_kernel<KW, NT, PRO, EPI, STATS>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
-    const int ntiles = a.B * ((a.T + NT - 1) / NT);
-    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    if (STATS && grid < kNumCU)
-        WM_TRY(hipMemsetAsync(a.stats, 0, sizeof(float) * 128 * kNumCU, stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// weight packing: parameter layout -> [tap][in][out] GEMM-A image (runs every step: Adam updates
-// the parameters in place, so the image is rebuilt from the live tensors; 12-28 K elements).
-//   mode 0  conv   forward : wp[tap][ci][co] = w[co][ci][tap]
-//   mode 1  conv   dgrad   : wp[tap][co][ci] = w[co][ci][KW-1-tap]
-//   mode 2  convT  forward : wp[tap][ci][co] = w[ci][co][KW-1-tap]      (w is [in][out][k])
-//   mode 3  convT  dgrad   : wp[tap][co][ci] = w[ci][co][tap]
-// ---------------------------------------------------------------------------------------------
-__global__ void pack_w64_kernel(const float* __restrict__ w, float* __restrict__ wp, int KW, int mode) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= KW * 4096) return;
-    const int tap = i / 4096, in = (i / 64) % 64, out = i % 64;
-    int src;
-    if (mode == 0) src = (out * 64 + in) * KW + tap;
-    else if (mode == 1) src = (in * 64 + out) * KW + (KW - 1 - tap);
-    else if (mode == 2) src = (in * 64 + out) * KW + (KW - 1 - tap);
-    else src = (out * 64 + in) * KW + tap;
-    wp[i] = w[src];
-}
-
-// ---------------------------------------------------------------------------------------------
-// weight gradient:  G[tap][out][in] = sum_{b,t} g[b,out,t] * xin[b,in,t+tap-PAD]   (+ bias grad)
-// as a GEMM with the (b,t) axis as the contraction (K of the MFMA = 2 time steps).
-// Each workgroup writes one partial slab; wgrad64_reduce sums the slabs in a fixed order
-// (bitwise reproducible, no float atomics) into the parameter-gradient layout.
-// ---------------------------------------------------------------------------------------------
-struct Wgrad64Args {
-    const float* g;  const float* g2;                   // gradient tensor(s) [B,64,T]
-    const float* ga; const float* gb; const float* gc;  // BNBWD constants for g
-    const float* x;                                     // layer input [B,64,T]
-    const float* xa; const float* xb;                   // x prologue constants (BNRELU scale/shift, ADDVEC vec[B,64])
-    float* partial;                                     // [grid][KW*4096 + 64]
-    int B, T;
-};
-
-template <int KW, int GPRO, int XPRO>
-__global__ __launch_bounds__(256) void wgrad64_kernel(Wgrad64Args a) {
-    constexpr int NT = 128, PAD = KW / 2;
-    constexpr int GS = NT + 4, XS = NT + 8;
-    constexpr int QR = NT / 4, NV = 64 * QR / 256;      // 8 float4 per thread per tensor
-    constexpr int HTOT = 64 * 2 * PAD, HN = (HTOT + 255) / 256;
-    constexpr bool TIME_SPLIT = (KW == 3);              // waves split the tile's time range, else the taps
-    constexpr int TL = TIME_SPLIT ? KW : 2;             // taps held per wave
-    constexpr bool GTWO = (GPRO == PRO_BNBWD);
-
-    extern __shared__ __align__(16) float smem[];
-    float* Gs = smem;                 // [64][GS]
-    float* Xs = Gs + 64 * GS;         // [64][XS]
-    float* Cs = Xs + 64 * XS;         // [5][64]: ga gb gc xa xb
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int T = a.T;
-    const int tilesPerClip = (T + NT - 1) / NT, ntiles = a.B * tilesPerClip;
-
-    float4 sg[NV], sg2[GTWO ? NV : 1], sx[NV];
-    float hx[HN];
-    float bsum[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) bsum[i] = 0.f;
-
-    auto load_tile = [&](int tile) {            // branch-free, see conv64_kernel
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        const size_t base = (size_t)b * 64 * T;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * 256, c = idx / QR, q = idx % QR;
-            const int t = min(t0 + 4 * q, T - 4);
-            sg[i] = *reinterpret_cast<const float4*>(a.g + base + (size_t)c * T + t);
-            if (GTWO) sg2[i] = *reinterpret_cast<const float4*>(a.g2 + base + (size_t)c * T + t);
-            sx[i] = *reinterpret_cast<const float4*>(a.x + base + (size_t)c * T + t);
-        }
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int idx = min(tid + i * 256, HTOT - 1);
-            const int c = idx / (2 * PAD), h = idx % (2 * PAD);
-            const int t = min(max((h < PAD) ? t0 - PAD + h : t0 + NT + (h - PAD), 0), T - 1);
-            hx[i] = a.x[base + (size_t)c * T + t];
-        }
-    };
-    auto write_tile = [&](int tile) {
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int idx = tid + i * 256, c = idx / QR, q = idx % QR, t = t0 + 4 * q;
-            float4 v = sg[i], u = sx[i];
-            if (GPRO == PRO_BNBWD) {
-                const float ca = Cs[c], cb = Cs[64 + c], cc = Cs[128 + c], cl = Cs[320 + c];
-                const float4 w = sg2[i];
-                v.x = pro_apply<PRO_BNBWD>(v.x, w.x, ca, cb, cc, cl);
-                v.y = pro_apply<PRO_BNBWD>(v.y, w.y, ca, cb, cc, cl);
-                v.z = pro_apply<PRO_BNBWD>(v.z, w.z, ca, cb, cc, cl);
-                v.w = pro_apply<PRO_BNBWD>(v.w, w.w, ca, cb, cc, cl);
-            }
-            if (XPRO != PRO_NONE) {
-                const float ca = (XPRO == PRO_ADDVEC) ? a.xa[b * 64 + c] : Cs[192 + c];
-                const float cb = Cs[256 + c];
-                u.x = pro_apply<XPRO>(u.x, 0.f, ca, cb, 0.f);
-                u.y = pro_apply<XPRO>(u.y, 0.f, ca, cb, 0.f);
-                u.z = pro_apply<XPRO>(u.z, 0.f, ca, cb, 0.f);
-                u.w = pro_apply<XPRO>(u.w, 0.f, ca, cb, 0.f);
-            }
-            if (t >= T) { v = make_float4(0.f, 0.f, 0.f, 0.f); u = v; }
-            bsum[i] += (v.x + v.y) + (v.z + v.w);
-            *reinterpret_cast<float4*>(Gs + c * GS + 4 * q) = v;
-            *reinterpret_cast<float4*>(Xs + c * XS + 4 + 4 * q) = u;
-        }
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int idx = tid + i * 256;
-            if (idx < HTOT) {
-                const int c = idx / (2 * PAD), h = idx % (2 * PAD);
-                const int t = (h < PAD) ? t0 - PAD + h : t0 + NT + (h - PAD);
-                float v = hx[i];
-                if (XPRO != PRO_NONE) {
-                    const float ca = (XPRO == PRO_ADDVEC) ? a.xa[b * 64 + c] : Cs[192 + c];
-                    v = pro_apply<XPRO>(v, 0.f, ca, Cs[256 + c], 0.f);
-                }
-                if (t < 0 || t >= T) v = 0.f;
-                Xs[c * XS + ((h < PAD) ? 4 - PAD + h : 4 + NT + (h - PAD))] = v;
-            }
-        }
-    };
-
-    int tile = blockIdx.x;
-    if (tile < ntiles) load_tile(tile);
-    if (tid < 64) {
-        Cs[tid] = GTWO ? a.ga[tid] : 0.f;
-        Cs[64 + tid] = GTWO ? a.gb[tid] : 0.f;
-        Cs[128 + tid] = GTWO ? a.gc[tid] : 0.f;
-        Cs[192 + tid] = (XPRO == PRO_BNRELU) ? a.xa[tid] : 0.f;
-        Cs[256 + tid] = (XPRO == PRO_BNRELU) ? a.xb[tid] : 0.f;
-        Cs[320 + tid] = GTWO ? a.gb[64 + tid] : 0.f;        // low word of the BatchNorm-backward offset
-    }
-    __syncthreads();
-    if (tile < ntiles) write_tile(tile);
-    __syncthreads();
-
-    f32x16 acc[TL][2][2];
-#pragma unroll
-    for (int tl = 0; tl < TL; ++tl)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[tl][mt][nt][r] = 0.f;
-
-    const int tbeg = TIME_SPLIT ? wave * (NT / 4) : 0;
-    constexpr int NSTEP = (TIME_SPLIT ? NT / 4 : NT) / 2;
-
-    while (tile < ntiles) {
-        const int next = tile + gridDim.x;
-        if (next < ntiles) load_tile(next);
-        const float* gp = Gs + l31 * GS + tbeg + half;
-        const float* xp = Xs + l31 * XS + (4 - PAD) + tbeg + half;
-#pragma unroll 4
-        for (int s = 0; s < NSTEP; ++s) {
-            const float a0 = gp[2 * s], a1 = gp[32 * GS + 2 * s];
-#pragma unroll
-            for (int tl = 0; tl < TL; ++tl) {
-                const int tap = TIME_SPLIT ? tl : wave + 4 * tl;
-                if (TIME_SPLIT || tap < KW) {
-                    const float b0 = xp[2 * s + tap], b1 = xp[32 * XS + 2 * s + tap];
-                    acc[tl][0][0] = mfma32(a0, b0, acc[tl][0][0]);
-                    acc[tl][0][1] = mfma32(a0, b1, acc[tl][0][1]);
-                    acc[tl][1][0] = mfma32(a1, b0, acc[tl][1][0]);
-                    acc[tl][1][1] = mfma32(a1, b1, acc[tl][1][1]);
-                }
-            }
-        }
-        __syncthreads();
-        if (next < ntiles) write_tile(next);
-        __syncthreads();
-        tile = next;
-    }
-
-    float* out = a.partial + (size_t)blockIdx.x * (KW * 4096 + 64);
-    if (TIME_SPLIT) {
-        // fixed-order reduction of the four waves' slabs through LDS (reuses the tile buffers)
-        float* red = smem;            // KW*4096 floats = 48 KB <= tile buffers (67 KB)
-        for (int w = 0; w < 4; ++w) {
-            if (wave == w) {
-#pragma unroll
-                for (int tl = 0; tl < TL; ++tl)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int o = (tl * 64 + mt * 32 + mfma_row(r, half)) * 64 + nt * 32 + l31;
-                                red[o] = (w == 0) ? acc[tl][mt][nt][r] : red[o] + acc[tl][mt][nt][r];
-                            }
-            }
-            __syncthreads();
-        }
-        for (int i = tid; i < KW * 4096; i += 256) out[i] = red[i];
-    } else {
-#pragma unroll
-        for (int tl = 0; tl < TL; ++tl) {
-            const int tap = wave + 4 * tl;
-            if (tap < KW) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            out[(tap * 64 + mt * 32 + mfma_row(r, half)) * 64 + nt * 32 + l31] = acc[tl][mt][nt][r];
-            }
-        }
-    }
-    // bias gradient: rows of this thread are c = idx / QR with idx = tid + i*256 -> (tid>>5) + 8 i;
-    // the 32 lanes of a half-wave share the row.
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float v = half_wave_sum(bsum[i]);
-        if (l31 == 0) out[KW * 4096 + (tid >> 5) + 8 * i] = v;
-    }
-}
-
-template <int KW, int GPRO, int XPRO>
-int launch_wgrad64(const Wgrad64Args& a, int* grid_out, hipStream_t stream) {
-    constexpr int NT = 128;
-    constexpr size_t lds = (size_t)(64 * (NT + 4) + 64 * (NT + 8) + 6 * 64) * sizeof(float);
-    static wm::DevOnce attr_done;
-    auto kern = wgrad64_kernel<KW, GPRO, XPRO>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
-    const int ntiles = a.B * ((a.T + NT - 1) / NT);
-    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    *grid_out = grid;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-// dst layout: mode 0 conv  dW[out][in][KW]   <- G[tap][out][in]
-//             mode 1 convT dW[in][out][KW]   <- G[KW-1-k][out][in]
-__global__ __launch_bounds__(256) void wgrad64_reduce_kernel(const float* __restrict__ partial, int nparts, int KW, int mode,
-                                                             float* __restrict__ dw, float* __restrict__ dbias, int accumulate) {
-    // block = 64 outputs x 4 quarters of the slab list; fixed order, fp64: bitwise reproducible and cancellation-safe
-    __shared__ double sq[4][64];
-    const int il = threadIdx.x & 63, grp = threadIdx.x >> 6, i = blockIdx.x * 64 + il;
-    const int stride = KW * 4096 + 64;
-    const int per = (nparts + 3) / 4, p0 = grp * per, p1 = min(p0 + per, nparts);
-    double s0 = 0.0, s1 = 0.0;
-    if (i < stride) {
-        int p = p0;
-        for (; p + 1 < p1; p += 2) {
-            s0 += (double)partial[(size_t)p * stride + i];
-            s1 += (double)partial[(size_t)(p + 1) * stride + i];
-        }
-        if (p < p1) s0 += (double)partial[(size_t)p * stride + i];
-    }
-    sq[grp][il] = s0 + s1;
-    __syncthreads();
-    if (grp != 0 || i >= stride) return;
-    const float s = (float)((sq[0][il] + sq[1][il]) + (sq[2][il] + sq[3][il]));
-    if (i < KW * 4096) {
-        const int tap = i / 4096, out = (i / 64) % 64, in = i % 64;
-        const int dst = (mode == 0) ? (out * 64 + in) * KW + tap : (in * 64 + out) * KW + (KW - 1 - tap);
-        dw[dst] = accumulate ? dw[dst] + s : s;
-    } else if (dbias) {
-        const int c = i - KW * 4096;
-        dbias[c] = accumulate ? dbias[c] + s : s;
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // bf16x6 variant of the k3 convolution: fp32-grade results on the bf16 matrix cores.
@@ -584,9 +15,6 @@ __global__ __launch_bounds__(256) void wgrad64_reduce_kernel(const float* __rest
 // LDS images are channel-minor ([time][channel] and [tap][cout][cin], 144-B pitch) so that an MFMA fragment
 // (8 consecutive k = 8 input channels) is one aligned ds_read_b128.
 // ---------------------------------------------------------------------------------------------
-#ifndef WM_LOADPOS
-#define WM_LOADPOS 1
-#endif
 template <int PRO, int EPI, bool STATS>
 __global__ __launch_bounds__(256) void conv64bf_kernel(Conv64Args a) {
     constexpr int KW = 3, PAD = 1, NT = 128, ROWS = NT + 2, PITCH = 72, NP = 3;
@@ -813,10 +241,7 @@ int launch_conv64bf(const Conv64Args& a, hipStream_t stream) {
     constexpr size_t lds = (size_t)(3 * 3 * 64 * 72 + 3 * 130 * 72) * 2 + 6 * 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = conv64bf_kernel<PRO, EPI, STATS>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     if (STATS && grid < kNumCU) WM_TRY(hipMemsetAsync(a.stats, 0, sizeof(float) * 128 * kNumCU, stream));
@@ -836,42 +261,6 @@ int launch_conv64bf(const Conv64Args& a, hipStream_t stream) {
 // same instruction stream, a few VALU/DS instructions after every MFMA, splits tile i+1 into image B and then
 // issues the global loads of tile i+2: one LDS-only barrier per tile, output stores stay in flight across it.
 // ---------------------------------------------------------------------------------------------
-#ifndef WM_LOAD_H
-#define WM_LOAD_H 17
-#endif
-#ifndef WM_XCD_MAP
-#define WM_XCD_MAP 1
-#endif
-#ifndef WM_TILE_CONTIG
-#define WM_TILE_CONTIG 0
-#endif
-#ifndef WM_NT_STORE
-#define WM_NT_STORE 0
-#endif
-#ifndef WM_BF3_MANUAL
-#define WM_BF3_MANUAL 1
-#endif
-#ifndef WM_BF3_PIN_W
-#define WM_BF3_PIN_W 1
-#endif
-#ifndef WM_BF7_PIPE
-#define WM_BF7_PIPE 1        // 7-tap convolution: 1 = register-resident weights, pipelined (T % 128 == 0), 0 = LDS weights, phase-serial
-#endif
-#ifndef WM_WGRAD_PIPE
-#define WM_WGRAD_PIPE 1      // k3 weight gradient: 1 = pipelined 64-step tiles (wgrad64bfp_kernel), 0 = phase-serial 128-step tiles
-#endif
-// XCD-aware workgroup -> tile-slot map.  Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with its
-// own L2.  Giving XCD x the 1/8 of the tile sequence [x*G/8, (x+1)*G/8) makes time-adjacent tiles share an L2, so the
-// halo columns (a 128-B line per channel per side, +50 % fetched bytes otherwise) and the neighbours' lines hit in L2.
-__device__ __forceinline__ int xcd_slot() {
-    const int g = gridDim.x, b = blockIdx.x;
-    return (g & 7) ? b : (b & 7) * (g >> 3) + (b >> 3);
-}
-
-__device__ __forceinline__ void lds_barrier() {          // s_barrier without draining vmcnt (global stores/prefetches stay in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // H = true: the f16 two-piece build (pieces hi = f16(x), lo = f16(x - hi); three products lo hi, hi lo, hi hi on v_mfma_f32_32x32x16_f16;
 // weight image from wm_pack_w64_h: w * ws with ws a power of two, the accumulators are multiplied by 1 / ws in the epilogue)
 template <int PRO, int EPI, bool STATS, bool H = false>
@@ -1326,354 +715,11 @@ int launch_conv64bf3(const Conv64Args& a, hipStream_t stream) {
     constexpr size_t lds = (size_t)(2 * (H ? 2 : 3) * 130 * 72) * 2 + 6 * 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = conv64bf3_kernel<PRO, EPI, STATS, H>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     if (STATS && grid < kNumCU) WM_TRY(hipMemsetAsync(a.stats, 0, sizeof(float) * 128 * kNumCU, stream));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Inference ResBlock in ONE launch:  out = relu(x + BN2(conv2(relu(BN1(conv1(x))))))  with both BatchNorms in eval
-// mode (running statistics folded into per-channel scale / shift), py/main16.py:112-125.  Frame passes over HBM: x in,
-// out out -- the intermediate never leaves the CU.
-// A workgroup walks 124-column output tiles.  Its x window is the 128 columns [w0, w0+128), w0 = 124 k - 4: exactly 32
-// aligned float4 per channel, no halo loads.  conv1 runs over MFMA columns j = 0..127 (a1 at time w0 + 1 + j, valid for
-// j < 126), its epilogue applies BN1 + ReLU (and the zero padding of conv2: a1 = 0 outside the clip), splits the result
-// into its three bf16 pieces and writes them to a second LDS image; conv2 reads that image (output column i = time
-// w0 + 2 + i, valid for i < 124) and its epilogue adds BN2 and the residual x (re-read from L2 in accumulator layout) and
-// stores.  Both convolutions keep the weight fragments of the wave's 32 output rows in registers (2 x 144 VGPRs of the
-// 512 a lone wave may use), so LDS holds only the two activation images (2 x 55 KB).  While conv2 runs, the same
-// instruction stream splits the NEXT tile's x window into the (by then free) x image; while conv1 runs, it fetches the
-// residual operand.
-// ---------------------------------------------------------------------------------------------
-struct RbeArgs {
-    const float* x;       // [B,64,T]
-    const void* w1;       // packed bf16 image [3 pieces][3 taps][64 out][64 in] of w * sc[out] (wm_pack_w64_bf_scaled)
-    const void* w2;
-    const float* b1; const float* sc1; const float* sh1;     // conv bias, folded BN scale / shift
-    const float* b2; const float* sc2; const float* sh2;
-    float* y;             // [B,64,T]
-    int B, T;
-};
-
-// H = true: f16 two-piece build (three products per product): w1 / w2 = wm_pack_w64_h_scaled images (w * sc[out] * ws, {ws, 1 / ws} behind
-// the image), x and the intermediate a1 split into hi / lo f16 pieces unscaled, accumulators times 1 / ws in both epilogues
-template <bool H>
-__global__ __launch_bounds__(256) void resblock_eval_kernel(RbeArgs a) {
-    constexpr int KW = 3, NTO = 124, ROWS = 130, PITCH = 72, NP = H ? 2 : 3, NC = 4;
-    constexpr int XBUF = NP * ROWS * PITCH;               // bf16 elements per image
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    unsigned short* Xb = reinterpret_cast<unsigned short*>(smem_raw);              // x window: row r = time w0 + r
-    unsigned short* Ab = Xb + XBUF;                                                // a1: row j = time w0 + 1 + j
-    float* Cs = reinterpret_cast<float*>(Ab + XBUF);                               // [2][64]: k1 k2 (offsets; the scales ride in the weights)
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mt = wave & 1, nh = wave >> 1;
-    const int T = a.T;
-    const int tilesPerClip = (T + 2 + NTO - 1) / NTO, ntiles = a.B * tilesPerClip;
-
-    u32x4 W1[12][NP], W2[12][NP];
-    {
-        const uint4* wg1 = reinterpret_cast<const uint4*>(a.w1);
-        const uint4* wg2 = reinterpret_cast<const uint4*>(a.w2);
-#pragma unroll
-        for (int s = 0; s < 12; ++s)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const int e = ((p * KW + (s >> 2)) * 64 + 32 * mt + l31) * 64 + 16 * (s & 3) + 8 * half;
-                // the second convolution's fragments are pinned into AGPRs (the MFMA reads its A operand from there in place):
-                // 288 fragment registers do not fit the 256 VGPRs, and fragments the allocator spills are copied back per use
-                u32x4 w2_ = __builtin_bit_cast(u32x4, wg2[e >> 3]);
-                asm volatile("" : "+a"(w2_));
-                W1[s][p] = __builtin_bit_cast(u32x4, wg1[e >> 3]);
-                W2[s][p] = w2_;
-            }
-    }
-    const float winv1 = H ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.w1) + NP * KW * 4096)[1] : 1.f;
-    const float winv2 = H ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.w2) + NP * KW * 4096)[1] : 1.f;
-    // staging map (fixed per thread): channel pair cp, time quads q0 + 8 i
-    const int cp = wave * 8 + (lane & 7), c0 = 2 * cp, q0 = lane >> 3;
-    float4 sa[NC], sb[NC];
-    auto load_combo = [&](int tile, int i) {      // branch-free: clamped address, masked when written to LDS
-        const int b = tile / tilesPerClip, w0 = (tile - b * tilesPerClip) * NTO - 4;
-        const int t = min(max(w0 + 4 * (q0 + 8 * i), 0), T - 4);
-        const size_t o = ((size_t)b * 64 + c0) * T + t;
-        sa[i] = *reinterpret_cast<const float4*>(a.x + o);
-        sb[i] = *reinterpret_cast<const float4*>(a.x + o + T);
-    };
-    auto split_unit = [&](int w0, int i, int e) {  // two channels x one time step of the window starting at w0 -> 3 dwords
-        const int t = w0 + 4 * (q0 + 8 * i);
-        const bool ok = (t >= 0) && (t < T);        // T % 4 == 0 and w0 % 4 == 0: a quad is inside or outside as a whole
-        const float4 fa = sa[i], fb = sb[i];
-        float va = (e == 0) ? fa.x : (e == 1) ? fa.y : (e == 2) ? fa.z : fa.w;
-        float vb = (e == 0) ? fb.x : (e == 1) ? fb.y : (e == 2) ? fb.z : fb.w;
-        va = ok ? va : 0.f; vb = ok ? vb : 0.f;
-        unsigned* X32 = reinterpret_cast<unsigned*>(Xb);
-        const int o = (4 * (q0 + 8 * i) + e) * (PITCH / 2) + cp;
-        if (H) {
-            const h16x2 h_ = __builtin_convertvector(f32x2{va, vb}, h16x2);
-            const h16x2 l_ = __builtin_convertvector(f32x2{va - (float)h_.x, vb - (float)h_.y}, h16x2);
-            X32[o] = __builtin_bit_cast(unsigned, h_); X32[(ROWS * PITCH >> 1) + o] = __builtin_bit_cast(unsigned, l_);
-        } else {
-            unsigned p0, p1, p2;
-            split3_pair(va, vb, p0, p1, p2);
-            X32[o] = p0; X32[(ROWS * PITCH >> 1) + o] = p1; X32[2 * (ROWS * PITCH >> 1) + o] = p2;
-        }
-    };
-
-    const int tstep = gridDim.x;
-    int tile = xcd_slot();                                         // grid <= ntiles
-#pragma unroll
-    for (int i = 0; i < NC; ++i) load_combo(tile, i);
-    if (tid < 64) {
-        Cs[tid] = fmaf(a.b1 ? a.b1[tid] : 0.f, a.sc1[tid], a.sh1[tid]);
-        Cs[64 + tid] = fmaf(a.b2 ? a.b2[tid] : 0.f, a.sc2[tid], a.sh2[tid]);
-    }
-    // rows 128, 129 of both images are read by the discarded MFMA columns only: keep them finite (zero)
-    for (int i = tid; i < NP * 2 * (PITCH / 2); i += 256) {
-        const int p = i / (2 * (PITCH / 2)), rem = i - p * (2 * (PITCH / 2));
-        const int o = (p * ROWS + 128) * (PITCH / 2) + rem;
-        reinterpret_cast<unsigned*>(Xb)[o] = 0u;
-        reinterpret_cast<unsigned*>(Ab)[o] = 0u;
-    }
-    {
-        const int w0 = (tile % tilesPerClip) * NTO - 4;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) split_unit(w0, u >> 2, u & 3);
-    }
-    __syncthreads();
-    // per-lane epilogue offsets: the 16 channels of this lane's accumulator rows (the same for both column blocks)
-    float k1[16], k2[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int co = 32 * mt + mfma_row(r, half);
-        k1[r] = Cs[co]; k2[r] = Cs[64 + co];
-    }
-
-    float e1r[32];
-#ifdef WM_STAMP
-    unsigned long long tm[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    unsigned* const X32 = reinterpret_cast<unsigned*>(Xb);
-    unsigned* const A32 = reinterpret_cast<unsigned*>(Ab);
-
-    // One k-step of a matrix phase: the fragment reads of the NEXT step, then the six piece products with one slice of side
-    // work (f0..f5: a handful of VALU / LDS / global instructions) pinned behind each of them.  The six MFMAs of a step
-    // chain on one accumulator, so each waits 8 passes for its predecessor: the slice between two of them is free.  The
-    // order is fixed by hand (sched_barrier fences): the group-barrier pattern conv64bf3 uses is not honoured here (the
-    // weight fragments of two convolutions overflow into AGPRs and their copies break the pattern; the side work then lands
-    // in one lump in front of six back-to-back MFMAs).
-#define FENCE __builtin_amdgcn_sched_barrier(0)
-    auto nop = []() {};
-    auto mma = [&](const u32x4& A_, const u32x4& B_, f32x16 c) -> f32x16 {
-        if (H) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, A_), __builtin_bit_cast(h16x8, B_), c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), c, 0, 0, 0);
-    };
-    auto kstep = [&](const u32x4 (&W)[12][NP], const unsigned short* img, f32x16& ac, u32x4 (&Bq)[2][NP], int nt, int s,
-                     auto&& f0, auto&& f1, auto&& f2, auto&& f3, auto&& f4, auto&& f5) __attribute__((always_inline)) {
-        if (s + 1 < 12) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-                Bq[(s + 1) & 1][p] = *reinterpret_cast<const u32x4*>(img + (p * ROWS + 32 * nt + ((s + 1) >> 2)) * PITCH + 16 * ((s + 1) & 3));
-        }
-        const u32x4* Bf = Bq[s & 1];
-        FENCE;
-        if (H) {                                         // lo hi, hi lo, hi hi: two slices behind every MFMA
-            ac = mma(W[s][1], Bf[0], ac); FENCE; f0(); FENCE; f1(); FENCE;
-            ac = mma(W[s][0], Bf[1], ac); FENCE; f2(); FENCE; f3(); FENCE;
-            ac = mma(W[s][0], Bf[0], ac); FENCE; f4(); FENCE; f5(); FENCE;
-        } else {
-            ac = mma(W[s][1], Bf[1], ac); FENCE; f0(); FENCE;
-            ac = mma(W[s][0], Bf[NP - 1], ac); FENCE; f1(); FENCE;
-            ac = mma(W[s][NP - 1], Bf[0], ac); FENCE; f2(); FENCE;
-            ac = mma(W[s][0], Bf[1], ac); FENCE; f3(); FENCE;
-            ac = mma(W[s][1], Bf[0], ac); FENCE; f4(); FENCE;
-            ac = mma(W[s][0], Bf[0], ac); FENCE; f5(); FENCE;
-        }
-    };
-    // the bf16x3 split of a value pair in three stages (one slice each)
-    float sva = 0.f, svb = 0.f;
-    unsigned sp0 = 0, sp1 = 0, sp2 = 0;
-    auto st1 = [&]() {
-        if (H) {
-            const h16x2 h = __builtin_convertvector(f32x2{sva, svb}, h16x2);
-            sp0 = __builtin_bit_cast(unsigned, h);
-            sva -= (float)h.x; svb -= (float)h.y;
-        } else {
-            const bf16x2 h = {(__bf16)sva, (__bf16)svb};
-            sp0 = __builtin_bit_cast(unsigned, h);
-            sva -= __uint_as_float(sp0 << 16); svb -= __uint_as_float(sp0 & 0xffff0000u);
-        }
-        asm volatile("" : "+v"(sva), "+v"(svb), "+v"(sp0));      // pins the stage into its slice (pure arithmetic sinks to its use otherwise)
-    };
-    auto st2 = [&]() {
-        if (H) return;                                   // two pieces: no middle one
-        const bf16x2 m = {(__bf16)sva, (__bf16)svb};
-        sp1 = __builtin_bit_cast(unsigned, m);
-        sva -= __uint_as_float(sp1 << 16); svb -= __uint_as_float(sp1 & 0xffff0000u);
-        asm volatile("" : "+v"(sva), "+v"(svb), "+v"(sp1));
-    };
-    auto st3 = [&](unsigned* img32, int o) {
-        if (H) {
-            sp2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sva, svb}, h16x2));
-            img32[o] = sp0; img32[(ROWS * PITCH >> 1) + o] = sp2;
-            return;
-        }
-        const bf16x2 l = {(__bf16)sva, (__bf16)svb};
-        sp2 = __builtin_bit_cast(unsigned, l);
-        img32[o] = sp0; img32[(ROWS * PITCH >> 1) + o] = sp1; img32[2 * (ROWS * PITCH >> 1) + o] = sp2;
-    };
-
-    while (tile < ntiles) {
-        const int next = min(tile + tstep, ntiles - 1);
-        const int b = tile / tilesPerClip, w0 = (tile - b * tilesPerClip) * NTO - 4, o0 = w0 + 2;
-        const int nw0 = (next % tilesPerClip) * NTO - 4;
-        // output column of accumulator block nt of this lane: byte offset inside a channel row, 0xffffffff (dropped by the
-        // buffer unit / read as 0) when the column is not an output of this tile; in1[nt]: the a1 column lies inside the clip
-        unsigned tcl[2];
-        bool in1[2];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int i = 64 * nh + 32 * nt + l31, t = o0 + i, u = w0 + 1 + i;
-            const bool ok = (i < NTO) && (t >= 0) && (t < T);
-            tcl[nt] = ok ? (unsigned)(t + 4 * half * T) * 4u : 0xffffffffu;
-            in1[nt] = (u >= 0) && (u < T);
-        }
-        // this wave's 32 channel rows of clip b, as buffer descriptors (scalar); row r sits at the scalar offset roff(r)
-        const size_t slab = ((size_t)b * 64 + 32 * mt) * T;
-        const wm_srd_t sxr = make_srd(a.x + slab, (size_t)32 * T * sizeof(float));
-        const wm_srd_t syr = make_srd(a.y + slab, (size_t)32 * T * sizeof(float));
-        auto roff = [&](int r) { return (unsigned)(((r & 3) + 8 * (r >> 2)) * T) * 4u; };                  // wave-uniform
-        auto e1_load = [&](int idx) { e1r[idx] = buf_load(sxr, tcl[idx >> 4], roff(idx & 15)); };
-        // epilogue 1 of accumulator pair pi (rows 2 pi, 2 pi + 1 = two adjacent channels) of block nt, in slices:
-        // BN1 offset + ReLU + zero padding -> split stages -> a1 image
-        auto e1_act = [&](const f32x16& ac, int nt, int pi) {
-            const float v0 = fmaxf(H ? fmaf(ac[2 * pi], winv1, k1[2 * pi]) : ac[2 * pi] + k1[2 * pi], 0.f),
-                        v1 = fmaxf(H ? fmaf(ac[2 * pi + 1], winv1, k1[2 * pi + 1]) : ac[2 * pi + 1] + k1[2 * pi + 1], 0.f);
-            sva = in1[nt] ? v0 : 0.f; svb = in1[nt] ? v1 : 0.f;
-            asm volatile("" : "+v"(sva), "+v"(svb));
-        };
-        auto e1_out = [&](int nt, int pi) {
-            const int j = 64 * nh + 32 * nt + l31, co = 32 * mt + mfma_row(2 * pi, half);
-            st3(A32, (j * PITCH + co) >> 1);
-        };
-        // split of unit (combo i, element e) of the next tile's x window, in slices
-        auto x_pick = [&](int i, int e) {
-            const int t = nw0 + 4 * (q0 + 8 * i);
-            const bool ok = (t >= 0) && (t < T);
-            const float4 fa = sa[i], fb = sb[i];
-            const float va = (e == 0) ? fa.x : (e == 1) ? fa.y : (e == 2) ? fa.z : fa.w;
-            const float vb = (e == 0) ? fb.x : (e == 1) ? fb.y : (e == 2) ? fb.z : fb.w;
-            sva = ok ? va : 0.f; svb = ok ? vb : 0.f;
-            asm volatile("" : "+v"(sva), "+v"(svb));
-        };
-        auto x_out = [&](int i, int e) { st3(X32, (4 * (q0 + 8 * i) + e) * (PITCH / 2) + cp); };
-        // epilogue 2 of accumulator row r of block nt: BN2 offset + residual + ReLU + store
-        auto e2_value = [&](const f32x16& ac, int nt, int r) {
-            const float v = fmaxf(e1r[nt * 16 + r] + (H ? fmaf(ac[r], winv2, k2[r]) : ac[r] + k2[r]), 0.f);
-            buf_store(syr, v, tcl[nt], roff(r));
-        };
-
-        f32x16 acc[2];
-        u32x4 Bq[2][NP];
-        STAMP(ts0);
-        // ---------------- conv1 from the x image
-        const unsigned short* xrow = Xb + (64 * nh + l31) * PITCH + 8 * half;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) Bq[0][p] = *reinterpret_cast<const u32x4*>(xrow + p * ROWS * PITCH);
-        // column block 0; side work: fetch the next tile's x window (split during conv2)
-#pragma unroll
-        for (int s = 0; s < 12; ++s) {
-            if (s < 4) kstep(W1, xrow, acc[0], Bq, 0, s, [&]() { load_combo(next, s); }, nop, nop, nop, nop, nop);
-            else kstep(W1, xrow, acc[0], Bq, 0, s, nop, nop, nop, nop, nop, nop);
-        }
-        STAMP(ts1);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) Bq[0][p] = *reinterpret_cast<const u32x4*>(xrow + (p * ROWS + 32) * PITCH);
-        // column block 1; side work: epilogue 1 of block 0
-#pragma unroll
-        for (int s = 0; s < 12; ++s) {
-            if (s < 8)
-                kstep(W1, xrow, acc[1], Bq, 1, s, [&]() { e1_act(acc[0], 0, s); }, st1, st2, [&]() { e1_out(0, s); }, nop, nop);
-            else kstep(W1, xrow, acc[1], Bq, 1, s, nop, nop, nop, nop, nop, nop);
-        }
-        // epilogue 1 of block 1 (serial)
-        STAMP(ts2);
-#pragma unroll
-        for (int pi = 0; pi < 8; ++pi) { e1_act(acc[1], 1, pi); st1(); st2(); e1_out(1, pi); }
-        STAMP(ts3);
-        lds_barrier();          // a1 image complete; every wave is done with the x image
-        STAMP(ts4);
-        // ---------------- conv2 from the a1 image
-        const unsigned short* arow = Ab + (64 * nh + l31) * PITCH + 8 * half;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) Bq[0][p] = *reinterpret_cast<const u32x4*>(arow + p * ROWS * PITCH);
-        // column block 0; side work: first half of the next tile's x window, residual operand of block 0
-#pragma unroll
-        for (int s = 0; s < 12; ++s) {
-            if (s < 8)
-                kstep(W2, arow, acc[0], Bq, 0, s, [&]() { x_pick(s >> 2, s & 3); }, st1, st2, [&]() { x_out(s >> 2, s & 3); },
-                      [&]() { e1_load(2 * s); }, [&]() { e1_load(2 * s + 1); });
-            else kstep(W2, arow, acc[0], Bq, 0, s, nop, nop, nop, nop, nop, nop);
-        }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) Bq[0][p] = *reinterpret_cast<const u32x4*>(arow + (p * ROWS + 32) * PITCH);
-        // column block 1; side work: second half of the window, residual operand of block 1, epilogue 2 of block 0
-#pragma unroll
-        for (int s = 0; s < 12; ++s) {
-            if (s < 4)
-                kstep(W2, arow, acc[1], Bq, 1, s, [&]() { x_pick(2 + (s >> 2), s & 3); }, st1, st2, [&]() { x_out(2 + (s >> 2), s & 3); },
-                      [&]() { e1_load(16 + 4 * s); e1_load(17 + 4 * s); }, [&]() { e1_load(18 + 4 * s); e1_load(19 + 4 * s); });
-            else if (s < 8)
-                kstep(W2, arow, acc[1], Bq, 1, s, [&]() { x_pick(2 + (s >> 2), s & 3); }, st1, st2, [&]() { x_out(2 + (s >> 2), s & 3); },
-                      [&]() { e2_value(acc[0], 0, 2 * (s - 4)); }, [&]() { e2_value(acc[0], 0, 2 * (s - 4) + 1); });
-            else
-                kstep(W2, arow, acc[1], Bq, 1, s, nop, nop, nop, nop,
-                      [&]() { e2_value(acc[0], 0, 2 * (s - 4)); }, [&]() { e2_value(acc[0], 0, 2 * (s - 4) + 1); });
-        }
-        // epilogue 2 of block 1 (serial)
-        STAMP(ts5);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) e2_value(acc[1], 1, r);
-        lds_barrier();          // next x image complete; a1 image free
-        STAMP(ts6);
-#ifdef WM_STAMP
-        tm[0] += ts1 - ts0; tm[1] += ts2 - ts1; tm[2] += ts3 - ts2; tm[3] += ts4 - ts3; tm[4] += ts5 - ts4; tm[5] += ts6 - ts5;
-#endif
-        tile += tstep;
-    }
-#undef FENCE
-#ifdef WM_STAMP
-    if (g_wm_stamp && lane == 0) {
-        unsigned long long* d = g_wm_stamp + ((size_t)blockIdx.x * 4 + wave) * 6;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = tm[i];
-    }
-#endif
-}
-
-template <bool H>
-static int launch_resblock_eval(const RbeArgs& a, hipStream_t stream) {
-    constexpr size_t lds = (size_t)(2 * (H ? 2 : 3) * 130 * 72) * 2 + 2 * 64 * sizeof(float);
-    static wm::DevOnce attr_done;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resblock_eval_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
-    const int ntiles = a.B * ((a.T + 2 + 123) / 124);
-    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    hipLaunchKernelGGL(resblock_eval_kernel<H>, dim3(grid), dim3(256), lds, stream, a);
     WM_CHECK_LAUNCH();
     return 0;
 }
@@ -1834,10 +880,7 @@ int launch_conv64bf7(const Conv64Args& a, hipStream_t stream) {
     constexpr size_t lds = (size_t)(3 * 7 * 32 * 72 + 3 * 134 * 72) * 2 + 32 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = conv64bf7_kernel<PRO, EPI>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = 2 * (ntiles < kNumCU / 2 ? ntiles : kNumCU / 2);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
@@ -2088,10 +1131,7 @@ int launch_conv64bf7p(const Conv64Args& a, hipStream_t stream) {
     constexpr size_t lds = (size_t)(2 * (H ? 2 : 3) * 134 * 72) * 2 + 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = conv64bf7p_kernel<PRO, EPI, H>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * (a.T / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
@@ -2641,10 +1681,7 @@ int launch_wgrad64bfp(const Wgrad64Args& a, int* grid_out, hipStream_t stream) {
     constexpr size_t lds = (size_t)(2 * 3 * 64 * 72 + 2 * 3 * 64 * 88) * 2 + 6 * 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = wgrad64bfp_kernel<GPRO, XPRO>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 63) / 64);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     *grid_out = grid;
@@ -2825,10 +1862,7 @@ int launch_wgrad64bf_small(const Wgrad64Args& a, int* grid_out, hipStream_t stre
     constexpr size_t lds = (size_t)(3 * 64 * 136 + 3 * 64 * 152) * 2 + 6 * 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = wgrad64bf_small_kernel<GPRO, XPRO>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     *grid_out = grid;
@@ -2845,10 +1879,7 @@ int launch_wgrad64bf(const Wgrad64Args& a, int* grid_out, hipStream_t stream) {
     constexpr size_t lds = (size_t)(3 * 64 * 136 + 3 * 64 * 152) * 2 + 6 * 64 * sizeof(float);
     static wm::DevOnce attr_done;
     auto kern = wgrad64bf_kernel<GPRO, XPRO>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     *grid_out = grid;
@@ -3053,10 +2084,7 @@ int launch_wgrad64bf7(const Wgrad64Args& a, int* grid_out, hipStream_t stream) {
     constexpr size_t lds = (size_t)((H ? 2 : 3) * 64 * 136 + (H ? 2 : 3) * 64 * 152) * 2;
     static wm::DevOnce attr_done;
     auto kern = wgrad64bf7_kernel<XPRO, H>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * ((a.T + 127) / 128);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
     *grid_out = grid;
@@ -3141,755 +2169,6 @@ __global__ __launch_bounds__(1024) void pack_w64_h7_kernel(const float* __restri
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Data gradient AND weight gradient of a k3 convolution in ONE launch (ResBlock backward, py/main16.py:112-125 under
-// autograd).  Both read the same gradient frames (dz, and y for the BatchNorm-backward rebuild g = A dz + B + C y): as two
-// launches the pair moves 7 frames, fused 4 (conv2: dz2 y2 y1 in, dz1 out) or 5 (conv1: dz1 y1 x dz2 in, dx out).
-// A workgroup walks 64-step tiles.  The staging thread holds two channels x four steps of the gradient, rebuilds g once and
-// splits it once: time pairs of bf16 pieces go into the [channel][time] image of the weight gradient (phase A); the
-// [time][channel] image of the data gradient takes channel pairs, which are the same pieces re-paired by v_perm (phase B).
-// The data gradient is accumulated transposed (rows = time, columns = channel), so that a lane's accumulator quads are four
-// consecutive steps of one channel: epilogue operand and result move as dwordx4.  Per tile and wave:
-//   phase A: 72 MFMAs of the data gradient (weight fragments of its 32 output rows resident in registers, as conv64bf3)
-//            out of image D(i); side work: tile i+1 -> images G'(i+1), X'(i+1) (double-buffered), the epilogue operand of tile i
-//   barrier
-//   phase B: 72 MFMAs of the weight gradient (one 32 x 32 block of each tap per wave, as wgrad64bf_small) out of G'(i), X'(i);
-//            side work: tile i+1 -> image D (single-buffered), epilogue of the data gradient of tile i, refill for tile i+2
-//   barrier
-// One slice of side work pinned behind every MFMA.  LDS: 28 + 2 x 27 + 2 x 33 KB.  T % 64 == 0.
-// ---------------------------------------------------------------------------------------------
-struct DWArgs {
-    const float* g;  const float* g2;                   // gradient dz and the BN input y [B,64,T]
-    const float* ga; const float* gb; const float* gc;  // g = ga[c] dz + gb[c] (+ gb[64+c]) + gc[c] y
-    const void* wp;                                     // data-gradient weight image (wm_pack_w64_bf mode 1)
-    const float* x;  const float* xa; const float* xb;  // weight-gradient input operand (+ BN+ReLU constants when XPRO = BNRELU)
-    const float* e1; const float* ea; const float* eb;  // data-gradient epilogue tensor (RELUMASK: pre-BN activation + its scale/shift; ADD: addend)
-    float* y;                                           // data gradient out [B,64,T]
-    float* stats;                                       // [grid][2][64] (RELUMASK) or null
-    float* partial;                                     // weight-gradient slabs [grid][3*4096 + 64]
-    int B, T;
-    const unsigned* gmask;                              // GM: sign bits of the ReLU the incoming gradient passes (bit t % 32 of dword
-                                                        // [row][t / 32]): applied to g (conv2 pair) / to e1 (conv1 pair) on load
-    const unsigned* pmask; const float* py2;            // EPI_ADDSTATS: sign bits / pre-BatchNorm activation y2 of the block BEFORE this
-                                                        // one: y = (data gradient + e1) masked, stats = (sum y, sum y py2)
-    const float* gscale;                                // H (f16 two-piece split): {gs, 1 / gs}, the power-of-two scale of the rebuilt
-                                                        // gradient (wm_bn_bwd_finalize); the weight image carries its own scale
-    float* dzmax;                                       // H, epi 1 / 2 / 8: max |y| per workgroup [grid] (sizes the NEXT launch's scale)
-};
-
-// H = false: bf16 three-piece split, six piece products per product (bf16x6).  H = true: f16 TWO-piece split (hi = RNE_f16(x s),
-// lo = RNE_f16(x s - hi): 22 bits), three products hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16 -- half the matrix work, two
-// thirds of the split / LDS work.  The f16 range is met by power-of-two scales: the weights' (chosen by the pack kernel from
-// max |w|, stored behind the image), the gradient's (gs from wm_bn_bwd_finalize: max |A| max |dz| -> 2^9, applied through the
-// BatchNorm-backward constants, i.e. for free; the rebuilt value is clamped to +-6e4 so that a pathological element saturates
-// instead of becoming an infinity); activations need none.  Results are unscaled in the epilogue / at the slab write.
-template <int EPI, int XPRO, bool GM, bool H>
-__global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
-    static_assert((EPI == EPI_RELUMASK && XPRO == PRO_BNRELU) || ((EPI == EPI_ADD || EPI == EPI_ADDSTATS) && XPRO == PRO_NONE), "conv2 pair or conv1 pair");
-    constexpr int KW = 3, NT = 64, NP = H ? 2 : 3, ROWS = NT + 2, PITCH = 72, PG = 72, PX = 88, XO = 8;
-    constexpr int NPR = H ? 3 : 6, SPM = 6 / NPR;          // piece products per product; side-work slices per MFMA
-    constexpr bool STATS = (EPI == EPI_RELUMASK || EPI == EPI_ADDSTATS);
-    constexpr bool FOLD = (EPI == EPI_ADDSTATS);          // conv1 pair that also does the previous block's ReLU backward + BN sums
-    constexpr int DIMG = NP * ROWS * PITCH, GIMG = NP * 64 * PG, XIMG = NP * 64 * PX;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    unsigned short* Db = reinterpret_cast<unsigned short*>(smem_raw);          // [NP][ROWS][PITCH]   row r = time t0 - 1 + r
-    unsigned short* Gb0 = Db + DIMG;                                           // [2][NP][64][PG]
-    unsigned short* Xb0 = Gb0 + 2 * GIMG;                                      // [2][NP][64][PX]     element XO + (t - t0)
-    float* Cs = reinterpret_cast<float*>(Xb0 + 2 * XIMG);                      // [8][64]
-    // H: a wave-private [32 channels][32 steps (+4)] exchange tile.  In the accumulator layout a lane owns one channel, so a dwordx4
-    // access touches 32 rows with 16 bytes each; such a store (load) holds the wave at issue for ~300 cycles (measured: the four
-    // epilogue stores were 1 200 of a tile's 7 000 cycles).  Epilogue operands and results therefore cross HBM in ROW layout (a lane
-    // = 4 steps, 8 lanes = one 128-byte row segment, 8 rows per instruction) and change layout through this tile.
-    constexpr bool XL = H;
-    constexpr int EXP = 36;
-    float* Ex = Cs + 8 * 64 + (threadIdx.x >> 6) * (32 * EXP);
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mt = wave & 1, nh = wave >> 1;           // data gradient: 32 output rows x 32 columns; weight gradient: block (mt, nt = nh)
-    const int T = a.T;
-    const int tilesPerClip = T / NT, ntiles = a.B * tilesPerClip;
-
-    // ---- resident data-gradient weight fragments
-    u32x4 Wr[12][NP];
-    // H: {ws, 1 / ws} behind the [NP][KW][64][64] image
-    const float winv = H ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.wp) + NP * KW * 4096)[1] : 1.f;
-    const float gs = H ? a.gscale[0] : 1.f, ginv = H ? a.gscale[1] : 1.f;
-    const float dinv = ginv * winv;                        // data gradient: (g gs) (w ws) -> g w
-    {
-        const uint4* wg = reinterpret_cast<const uint4*>(a.wp);
-#pragma unroll
-        for (int s = 0; s < 12; ++s)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const int e = ((p * KW + (s >> 2)) * 64 + 32 * mt + l31) * 64 + 16 * (s & 3) + 8 * half;
-                u32x4 w_ = __builtin_bit_cast(u32x4, wg[e >> 3]);
-                // pinned to the AGPR half of the register file: the MFMA reads its A operand from there directly.  Left to the
-                // allocator the fragments are SPILLED to AGPRs and copied back (v_accvgpr_read) in front of every k-step.
-                asm volatile("" : "+a"(w_));
-                Wr[s][p] = w_;
-            }
-    }
-    // ---- staging map: channel pair cp (channels c0, c0 + 1), unit u = time quad q0 + 8 u; halo: channel hc, side hh
-    const int cp = wave * 8 + (lane & 7), c0 = 2 * cp, q0 = lane >> 3;
-    const int hc = (tid & 127) >> 1, hh = tid & 1;
-    float4 ra_[2], rb_[2], ya_[2], yb_[2], xa_[2], xb_[2];     // raw, per unit: dz / y of channel c0 (a) and c0 + 1 (b); x of both
-    float4 gz_;                                                // the rebuilt gradient of the (unit, channel) being split
-    unsigned gp_[2][2][6];                                     // its bf16 pieces [unit][channel][piece * 2 + time pair] (phase A -> phase B)
-    float hg = 0.f, hy = 0.f, hxv = 0.f;
-    wm_srd_t dsg = make_srd(a.g, 0), dsy = dsg, dsx = dsg, dsm = dsg;
-    unsigned voff = 0, hoff = 0;
-    bool okh = true;
-    constexpr bool GMG = GM && EPI == EPI_RELUMASK;      // the mask belongs to the gradient operand g (else, with GM, to e1)
-    unsigned mk_[2][2] = {{0u, 0u}, {0u, 0u}}, hmk = 0u; // mask dwords of (unit, channel) / of the halo step, as loaded
-    unsigned voffm = 0, hoffm = 0, hsh = 0, hsh_cur = 0;
-    const unsigned nwm = (unsigned)T >> 5;               // mask dwords per row (T % 64 == 0)
-    auto set_tile = [&](int tile) {
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        const size_t clip = (size_t)b * 64 * T, bytes = (size_t)64 * T * sizeof(float);
-        dsg = make_srd(a.g + clip, bytes);
-        dsy = make_srd(a.g2 + clip, bytes);
-        dsx = make_srd(a.x + clip, bytes);
-        voff = (unsigned)(c0 * T + t0 + 4 * q0) * 4u;
-        const int th = hh ? t0 + NT : t0 - 1;
-        hoff = (unsigned)(hc * T + min(max(th, 0), T - 1)) * 4u;
-        okh = th >= 0 && th < T;
-        if (GMG) {
-            dsm = make_srd(reinterpret_cast<const float*>(a.gmask) + (size_t)b * 64 * nwm, (size_t)64 * nwm * sizeof(unsigned));
-            voffm = ((unsigned)c0 * nwm + ((unsigned)t0 >> 5)) * 4u;
-            const int thc = min(max(th, 0), T - 1);
-            hoffm = ((unsigned)hc * nwm + ((unsigned)thc >> 5)) * 4u;
-            hsh = (unsigned)thc & 31u;
-        }
-    };
-    const unsigned rowT = (unsigned)T * 4u;
-    auto load_g = [&](int u) {
-        ra_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, 0u));
-        rb_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, rowT));
-        ya_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, 0u));
-        yb_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, rowT));
-    };
-    auto load_x = [&](int u) {
-        xa_[u] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u * u, 0u));
-        xb_[u] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u * u, rowT));
-    };
-    // The refills of the raw staging registers are dealt ONE load at a time over both phases (a register set is free from the slice
-    // that consumed it until the same slice of the next tile): a burst of four 1-KB loads from one wave stalls that wave at issue
-    // whenever the CU's miss queue is full, a different wave every tile -- measured as 430 of 8 250 cycles per tile spent at the
-    // phase-A barrier waiting for whichever wave was hit.
-    auto refillA = [&](int m) {                     // phase-A slice m
-        if (m == 14) ra_[0] = __builtin_bit_cast(float4, buf_load4(dsg, voff, 0u));
-        if (m == 20) rb_[0] = __builtin_bit_cast(float4, buf_load4(dsg, voff, rowT));
-        if (m == 26) ya_[0] = __builtin_bit_cast(float4, buf_load4(dsy, voff, 0u));
-        if (m == 32) yb_[0] = __builtin_bit_cast(float4, buf_load4(dsy, voff, rowT));
-        if (m == 38) ra_[1] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u, 0u));
-        if (m == 44) rb_[1] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u, rowT));
-        if (m == 50) ya_[1] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u, 0u));
-        if (m == 56) yb_[1] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u, rowT));
-        if (GMG) {
-            if (m == 16) mk_[0][0] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm, 0u));
-            if (m == 22) mk_[0][1] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm, nwm * 4u));
-            if (m == 40) mk_[1][0] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u, 0u));
-            if (m == 46) mk_[1][1] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u, nwm * 4u));
-        }
-    };
-    auto refillB = [&](int v) {                     // phase-B free slice v
-        if (v == 1) xa_[0] = __builtin_bit_cast(float4, buf_load4(dsx, voff, 0u));
-        if (v == 7) xb_[0] = __builtin_bit_cast(float4, buf_load4(dsx, voff, rowT));
-        if (v == 13) xa_[1] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u, 0u));
-        if (v == 19) xb_[1] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u, rowT));
-    };
-    auto load_ghalo = [&]() {
-        hg = buf_load(dsg, hoff, 0u); hy = buf_load(dsy, hoff, 0u);
-        if (GMG) hmk = __builtin_bit_cast(unsigned, buf_load(dsm, hoffm, 0u));
-    };
-    auto load_gmask = [&](int u) {
-        mk_[u][0] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u * u, 0u));
-        mk_[u][1] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u * u, nwm * 4u));
-    };
-    auto load_xhalo = [&]() { hxv = buf_load(dsx, hoff, 0u); };
-
-    const int tstep = gridDim.x;
-    int tile = WM_XCD_MAP ? xcd_slot() : (int)blockIdx.x;          // grid <= ntiles
-    set_tile(tile);
-    bool okh_cur = okh;
-    load_g(0); load_g(1); load_x(0); load_x(1); load_ghalo(); load_xhalo();
-    if (GMG) { load_gmask(0); load_gmask(1); }
-    hsh_cur = hsh;
-    if (tid < 64) {
-        Cs[tid] = a.ga[tid];
-        Cs[64 + tid] = a.gb[tid];
-        Cs[128 + tid] = a.gc[tid];
-        Cs[192 + tid] = a.gb[64 + tid];                  // low word of the BatchNorm-backward offset
-        Cs[256 + tid] = (XPRO == PRO_BNRELU) ? a.xa[tid] : 0.f;
-        Cs[320 + tid] = (XPRO == PRO_BNRELU) ? a.xb[tid] : 0.f;
-        Cs[384 + tid] = (EPI == EPI_RELUMASK) ? a.ea[tid] : 0.f;
-        Cs[448 + tid] = (EPI == EPI_RELUMASK) ? a.eb[tid] : 0.f;
-    }
-    // the element right of the right halo only feeds bits that the funnel shift drops: keep it defined in both images
-    for (int i = tid; i < 2 * NP * 64; i += 256) Xb0[(i / (NP * 64)) * XIMG + (i % (NP * 64)) * PX + XO + NT + 1] = 0;
-    __syncthreads();
-    // per-thread constants (the staging channels never change)
-    float kga[2], kgb[2], kgc[2], kgl[2], kxa[2], kxb[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        kga[j] = Cs[c0 + j] * gs; kgb[j] = Cs[64 + c0 + j] * gs; kgc[j] = Cs[128 + c0 + j] * gs; kgl[j] = Cs[192 + c0 + j] * gs;   // gs = 1 | 2^k: exact
-        kxa[j] = Cs[256 + c0 + j]; kxb[j] = Cs[320 + c0 + j];
-    }
-    const float hga = Cs[hc] * gs, hgb = Cs[64 + hc] * gs, hgc = Cs[128 + hc] * gs, hgl = Cs[192 + hc] * gs, hxa = Cs[256 + hc], hxb = Cs[320 + hc];
-
-    // ---- split stages on a value pair (va, vb) -> pieces (p0, p1, [lo]) and a second pair (vc, vd) -> (q0_, q1_, [lo])
-    float va = 0.f, vb = 0.f, vc = 0.f, vd = 0.f;
-    unsigned p0 = 0, p1 = 0, r0 = 0, r1 = 0;
-    float bsum[2] = {0.f, 0.f};
-    float bflag = 1.f;
-    auto s1a = [&]() {
-        if (H) {
-            const h16x2 h_ = __builtin_convertvector(f32x2{va, vb}, h16x2);
-            p0 = __builtin_bit_cast(unsigned, h_);
-            va -= (float)h_.x; vb -= (float)h_.y;
-        } else {
-            const bf16x2 h_ = {(__bf16)va, (__bf16)vb};
-            p0 = __builtin_bit_cast(unsigned, h_);
-            va -= __uint_as_float(p0 << 16); vb -= __uint_as_float(p0 & 0xffff0000u);
-        }
-        asm volatile("" : "+v"(va), "+v"(vb), "+v"(p0));
-    };
-    auto s2a = [&]() {
-        if (H) return;                                   // two pieces: no middle one
-        const bf16x2 m_ = {(__bf16)va, (__bf16)vb};
-        p1 = __builtin_bit_cast(unsigned, m_);
-        va -= __uint_as_float(p1 << 16); vb -= __uint_as_float(p1 & 0xffff0000u);
-        asm volatile("" : "+v"(va), "+v"(vb), "+v"(p1));
-    };
-    auto s1b = [&]() {
-        if (H) {
-            const h16x2 h_ = __builtin_convertvector(f32x2{vc, vd}, h16x2);
-            r0 = __builtin_bit_cast(unsigned, h_);
-            vc -= (float)h_.x; vd -= (float)h_.y;
-        } else {
-            const bf16x2 h_ = {(__bf16)vc, (__bf16)vd};
-            r0 = __builtin_bit_cast(unsigned, h_);
-            vc -= __uint_as_float(r0 << 16); vd -= __uint_as_float(r0 & 0xffff0000u);
-        }
-        asm volatile("" : "+v"(vc), "+v"(vd), "+v"(r0));
-    };
-    auto s2b = [&]() {
-        if (H) return;
-        const bf16x2 m_ = {(__bf16)vc, (__bf16)vd};
-        r1 = __builtin_bit_cast(unsigned, m_);
-        vc -= __uint_as_float(r1 << 16); vd -= __uint_as_float(r1 & 0xffff0000u);
-        asm volatile("" : "+v"(vc), "+v"(vd), "+v"(r1));
-    };
-    unsigned l0 = 0, l1 = 0;
-    auto lo_pair = [&](float x0, float x1) -> unsigned {         // the last piece of a value pair
-        if (H) return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, h16x2));
-        const bf16x2 l_ = {(__bf16)x0, (__bf16)x1};
-        return __builtin_bit_cast(unsigned, l_);
-    };
-    auto out4 = [&](unsigned short* dst, int stride_p) {         // two time pairs of one channel row: 8-byte writes
-        l0 = lo_pair(va, vb); l1 = lo_pair(vc, vd);
-        *reinterpret_cast<uint2*>(dst) = make_uint2(p0, r0);
-        if (!H) *reinterpret_cast<uint2*>(dst + stride_p) = make_uint2(p1, r1);
-        *reinterpret_cast<uint2*>(dst + (NP - 1) * stride_p) = make_uint2(l0, l1);
-    };
-    // gradient rebuild of channel j of unit u from the raw staging registers (free for the refill afterwards): one value per slice
-    // (a slice must stay within the shadow of one MFMA, about seven instructions: a twelve-instruction slice costs its excess in full)
-    auto g_build = [&](int u, int j, int e) {
-        const float4 dz = j ? rb_[u] : ra_[u], yy = j ? yb_[u] : ya_[u];
-        float4& gz = gz_;
-        float d = (e == 0) ? dz.x : (e == 1) ? dz.y : (e == 2) ? dz.z : dz.w;
-        const float yv = (e == 0) ? yy.x : (e == 1) ? yy.y : (e == 2) ? yy.z : yy.w;
-        if (GMG) {                          // dz = g_out where the block output was positive: its bit, sign-extended, ANDed in
-            if (e == 0) mk_[u][j] >>= 4 * q0;
-            d = __uint_as_float(__float_as_uint(d) & (unsigned)__builtin_amdgcn_sbfe((int)mk_[u][j], e, 1));
-        }
-        float v = pro_apply<PRO_BNBWD>(d, yv, kga[j], kgb[j], kgc[j], kgl[j]);
-        if (H) v = __builtin_amdgcn_fmed3f(v, -6.0e4f, 6.0e4f);      // a spike saturates; it never becomes an f16 infinity
-        bsum[j] = fmaf(bflag, v, bsum[j]);
-        asm volatile("" : "+v"(v), "+v"(bsum[j]));
-        if (e == 0) gz.x = v; else if (e == 1) gz.y = v; else if (e == 2) gz.z = v; else gz.w = v;
-    };
-    auto g_pick_t = [&](int u, int j) {                         // time pairs of channel j of unit u
-        const float4 gz = gz_;
-        va = gz.x; vb = gz.y; vc = gz.z; vd = gz.w;
-        asm volatile("" : "+v"(va), "+v"(vb), "+v"(vc), "+v"(vd));
-    };
-    auto x_pick_t = [&](int u, int j) {
-        float4 xx = j ? xb_[u] : xa_[u];
-        if (XPRO == PRO_BNRELU) {
-            xx.x = pro_apply<PRO_BNRELU>(xx.x, 0.f, kxa[j], kxb[j], 0.f); xx.y = pro_apply<PRO_BNRELU>(xx.y, 0.f, kxa[j], kxb[j], 0.f);
-            xx.z = pro_apply<PRO_BNRELU>(xx.z, 0.f, kxa[j], kxb[j], 0.f); xx.w = pro_apply<PRO_BNRELU>(xx.w, 0.f, kxa[j], kxb[j], 0.f);
-        }
-        va = xx.x; vb = xx.y; vc = xx.z; vd = xx.w;
-        asm volatile("" : "+v"(va), "+v"(vb), "+v"(vc), "+v"(vd));
-    };
-    // image D wants channel pairs (c0, c0 + 1) at ONE time step; the pieces of a value do not depend on what it is paired with, so
-    // they are taken from the time-pair dwords of the two channels with one v_perm each instead of splitting the gradient again
-    auto d_out = [&](int u, int e) {
-        const unsigned sel = (e & 1) ? 0x07060302u : 0x05040100u;   // high | low halves of (channel c0 + 1 : channel c0)
-        const int pr = e >> 1;
-        const unsigned d0 = __builtin_amdgcn_perm(gp_[u][1][pr], gp_[u][0][pr], sel);
-        const unsigned d1 = __builtin_amdgcn_perm(gp_[u][1][2 + pr], gp_[u][0][2 + pr], sel);
-        const unsigned d2 = __builtin_amdgcn_perm(gp_[u][1][4 + pr], gp_[u][0][4 + pr], sel);
-        unsigned* D32 = reinterpret_cast<unsigned*>(Db);
-        const int o = (1 + 4 * (q0 + 8 * u) + e) * (PITCH / 2) + cp;
-        D32[o] = d0;
-        if (!H) D32[(ROWS * PITCH >> 1) + o] = d1;
-        D32[(NP - 1) * (ROWS * PITCH >> 1) + o] = d2;
-    };
-    // halos: the gradient's for image D (rows 0 and 65), the input operand's for image X' (elements XO - 1, XO + 64)
-    auto hx_pick = [&]() {
-        float v = hxv;
-        if (XPRO == PRO_BNRELU) v = pro_apply<PRO_BNRELU>(v, 0.f, hxa, hxb, 0.f);
-        va = okh_cur ? v : 0.f; vb = 0.f;
-        asm volatile("" : "+v"(va), "+v"(vb));
-    };
-    auto hx_out = [&](unsigned short* X) {
-        const unsigned la = lo_pair(va, vb);
-        if (tid < 128) {
-            const int o = hc * PX + (hh ? XO + NT : XO - 1);
-            X[o] = (unsigned short)p0;
-            if (!H) X[64 * PX + o] = (unsigned short)p1;
-            X[(NP - 1) * 64 * PX + o] = (unsigned short)la;
-        }
-    };
-    auto hg_pick = [&]() {
-        float hgm = hg;
-        if (GMG) hgm = __uint_as_float(__float_as_uint(hg) & (unsigned)__builtin_amdgcn_sbfe((int)(hmk >> hsh_cur), 0, 1));
-        float v = pro_apply<PRO_BNBWD>(hgm, hy, hga, hgb, hgc, hgl);
-        if (H) v = __builtin_amdgcn_fmed3f(v, -6.0e4f, 6.0e4f);
-        va = okh_cur ? v : 0.f; vb = 0.f;
-        asm volatile("" : "+v"(va), "+v"(vb));
-    };
-    auto hg_out = [&]() {
-        const unsigned la = lo_pair(va, vb);
-        if (tid < 128) {
-            const int o = (hh ? NT + 1 : 0) * PITCH + hc;
-            Db[o] = (unsigned short)p0;
-            if (!H) Db[ROWS * PITCH + o] = (unsigned short)p1;
-            Db[(NP - 1) * ROWS * PITCH + o] = (unsigned short)la;
-        }
-    };
-    // phase-A side work, slice v of 64 (the other 8 slices fetch the epilogue operand): the operands in the registers -> images G', X'
-    //   v 0..35  gradient: per (unit, channel) 9 slices: rebuild x 4 | pick | hi a | mid a + hi b | mid b | lo + write
-    //   v 36..59 input:    per (unit, channel) 6 slices: pick (+ BN + ReLU) | hi a | mid a | hi b | mid b | lo + write
-    //   v 60..63 input halo
-    constexpr int NSA = 64;
-    auto sideA = [&](int v, unsigned short* G, unsigned short* X) __attribute__((always_inline)) {
-        if (v < 36) {
-            const int uj = v / 9, st = v % 9, u = uj >> 1, j = uj & 1;
-            if (st < 4) g_build(u, j, st);
-            if (st == 4) g_pick_t(u, j);
-            if (st == 5) s1a();
-            if (st == 6) { s2a(); s1b(); }
-            if (st == 7) s2b();
-            if (st == 8) {
-                out4(G + (c0 + j) * PG + 4 * (q0 + 8 * u), 64 * PG);
-                gp_[u][j][0] = p0; gp_[u][j][1] = r0; gp_[u][j][2] = p1; gp_[u][j][3] = r1; gp_[u][j][4] = l0; gp_[u][j][5] = l1;
-            }
-        } else if (v < 60) {
-            const int w = v - 36, uj = w / 6, st = w % 6, u = uj >> 1, j = uj & 1;
-            if (st == 0) x_pick_t(u, j);
-            if (st == 1) s1a();
-            if (st == 2) s2a();
-            if (st == 3) s1b();
-            if (st == 4) s2b();
-            if (st == 5) out4(X + (c0 + j) * PX + XO + 4 * (q0 + 8 * u), 64 * PX);
-        } else {
-            const int st = v - 60;
-            if (st == 0) { hx_pick(); load_xhalo(); }
-            if (st == 1) s1a();
-            if (st == 2) s2a();
-            if (st == 3) hx_out(X);
-        }
-    };
-    // phase-B side work, slice v of 12: the gradient's pieces -> image D (channel pairs by v_perm)
-    //   v 0..7  one slice per (unit, time step): 3 perms + 3 writes;   v 8..11 gradient halo
-    constexpr int NSB = 12;
-    auto sideB = [&](int v) __attribute__((always_inline)) {
-        if (v < 8) {
-            d_out(v >> 2, v & 3);
-        } else {
-            const int st = v - 8;
-            if (st == 0) { hg_pick(); load_ghalo(); }
-            if (st == 1) s1a();
-            if (st == 2) s2a();
-            if (st == 3) hg_out();
-        }
-    };
-    {   // first tile: all images serially; the refills inside the slices already fetch the second tile
-        set_tile(min(tile + tstep, ntiles - 1));
-        const bool okh_n = okh;
-#pragma unroll
-        for (int v = 0; v < NSA; ++v) { sideA(v, Gb0, Xb0); refillA(v); }
-        const unsigned hsh_n = hsh;
-#pragma unroll
-        for (int v = 0; v < 2 * NSB; ++v) { if ((v & 1) == 0) sideB(v >> 1); else refillB(v); }
-        okh_cur = okh_n; hsh_cur = hsh_n;
-    }
-    __syncthreads();
-
-    f32x16 wacc[KW];
-#pragma unroll
-    for (int k = 0; k < KW; ++k)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) wacc[k][r] = 0.f;
-    // The data gradient is accumulated TRANSPOSED (gradient image = A operand, weights = B operand): a lane then owns ONE output
-    // channel (32 mt + l31) and, per accumulator quad, four consecutive time steps -- the epilogue operand comes in and the
-    // result goes out as dwordx4 (8 memory instructions per tile instead of 32), the ReLU-mask constants and the two BatchNorm
-    // sums are one register each instead of sixteen.
-    float s1 = 0.f, s2 = 0.f;
-    f32x4 e1q[4];
-    // conv2 pair: the epilogue operand IS the input operand of the weight gradient (the pre-BatchNorm activation), read a second
-    // time in the accumulator layout.  Fetched one tile AHEAD (e1n, for the next tile, while this one is in phase A) it follows
-    // the staging loads of the same tile by less than one tile's worth of traffic and is served by the XCD's L2 instead of HBM
-    // (fetched as late as the tile needs it, 32 % of the kernel's HBM traffic was this re-read).
-    // (round 3, f16 build: with half the MFMAs per phase an operand fetched in phase A no longer has a phase's worth of time to arrive
-    // before the epilogue in phase B needs it -- EVERY epilogue operand of every form is now fetched one tile ahead: e1, the mask words,
-    // the previous block's y2)
-    constexpr bool EAHEAD = true;
-    f32x4 e1n[4];
-    unsigned emk = 0u, pmk = 0u, emkn = 0u, pmkn = 0u;
-    f32x4 pyq[FOLD ? 4 : 1], pyn[FOLD ? 4 : 1];
-    f32x4 ec[XL ? 4 : 1], pyc[(XL && FOLD) ? 4 : 1];     // row-layout staging of the next tile's epilogue operands
-    const int xrow = lane >> 3, xcol = 4 * (lane & 7);       // row layout: lane -> (row xrow + 8 r, steps xcol .. xcol + 3)
-    const unsigned xlane = (unsigned)(xrow * T + xcol) * 4u;
-    unsigned row8T[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) row8T[r] = (unsigned)(8 * r * T) * 4u;
-    const float kea = (EPI == EPI_RELUMASK) ? Cs[384 + 32 * mt + l31] : 0.f, keb = (EPI == EPI_RELUMASK) ? Cs[448 + 32 * mt + l31] : 0.f;
-    int buf = 0;
-#ifdef WM_STAMP
-    unsigned long long tm[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    {                                                    // the first tile's epilogue operands
-        const int b0 = tile / tilesPerClip, t00 = (tile - b0 * tilesPerClip) * NT;
-        const size_t slab0 = ((size_t)b0 * 64 + 32 * mt) * T;
-        const unsigned eo0 = (unsigned)(l31 * T + t00 + 32 * nh + 4 * half) * 4u, mo0 = ((unsigned)l31 * nwm + ((unsigned)t00 >> 5) + (unsigned)nh) * 4u;
-        const wm_srd_t s0 = make_srd(a.e1 + slab0, (size_t)32 * T * sizeof(float));
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) e1q[q4] = buf_load4(s0, eo0 + 32u * q4, 0u);
-        if (GM && (EPI == EPI_ADD || EPI == EPI_ADDSTATS))
-            emk = __builtin_bit_cast(unsigned, buf_load(make_srd(reinterpret_cast<const float*>(a.gmask) + ((size_t)b0 * 64 + 32 * mt) * nwm,
-                                                                 (size_t)32 * nwm * sizeof(unsigned)), mo0, 0u));
-        if (FOLD) {
-            pmk = __builtin_bit_cast(unsigned, buf_load(make_srd(reinterpret_cast<const float*>(a.pmask) + ((size_t)b0 * 64 + 32 * mt) * nwm,
-                                                                 (size_t)32 * nwm * sizeof(unsigned)), mo0, 0u));
-            const wm_srd_t sp0 = make_srd(a.py2 + slab0, (size_t)32 * T * sizeof(float));
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) pyq[q4] = buf_load4(sp0, eo0 + 32u * q4, 0u);
-        }
-    }
-#define FENCE __builtin_amdgcn_sched_barrier(0)
-    // one piece product on raw 128-bit fragments; the j-th product of a k-step pairs piece PA(j) of the first operand with piece PB(j)
-    // of the second, small terms first (bf16x6: mid mid, hi lo, lo hi, hi mid, mid hi, hi hi; f16: lo hi, hi lo, hi hi)
-    auto mma = [&](const u32x4& A_, const u32x4& B_, f32x16 c) -> f32x16 {
-        if (H) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, A_), __builtin_bit_cast(h16x8, B_), c, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), c, 0, 0, 0);
-    };
-    auto PA = [](int j) { return H ? (j == 0 ? 1 : 0) : ((j == 0 || j == 4) ? 1 : (j == 2 ? 2 : 0)); };
-    auto PB = [](int j) { return H ? (j == 1 ? 1 : 0) : ((j == 0 || j == 3) ? 1 : (j == 1 ? 2 : 0)); };
-    float vmax = 0.f;                                    // H: running max |y| of the data-gradient values this lane stores
-    while (tile < ntiles) {
-        // registers: the raw operands of tile + tstep (clamped: the duplicate of the last tile is split but never used)
-        const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        bflag = (tile + tstep < ntiles) ? 1.f : 0.f;
-        set_tile(min(tile + 2 * tstep, ntiles - 1));       // what the refills inside the slices fetch
-        const bool okh_n = okh;
-        const unsigned hsh_n = hsh;
-        const unsigned short* Gc = Gb0 + buf * GIMG;
-        const unsigned short* Xc = Xb0 + buf * XIMG;
-        unsigned short* Gn = Gb0 + (buf ^ 1) * GIMG;
-        unsigned short* Xn = Xb0 + (buf ^ 1) * XIMG;
-        // data-gradient output / epilogue operand of this lane: channel 32 mt + l31, steps t0 + 32 nh + 8 q + 4 half + (0..3) for quad q
-        const size_t slab = ((size_t)b * 64 + 32 * mt) * T;
-        const wm_srd_t sye = make_srd(a.y + slab, (size_t)32 * T * sizeof(float));
-        const wm_srd_t se1 = make_srd(a.e1 + slab, (size_t)32 * T * sizeof(float));
-        const unsigned eoff = (unsigned)(l31 * T + t0 + 32 * nh + 4 * half) * 4u;
-        const int tnx = min(tile + tstep, ntiles - 1), bnx = tnx / tilesPerClip, t0nx = (tnx - bnx * tilesPerClip) * NT;
-        const wm_srd_t se1n = EAHEAD ? make_srd(a.e1 + ((size_t)bnx * 64 + 32 * mt) * T, (size_t)32 * T * sizeof(float)) : se1;
-        const unsigned eoffn = (unsigned)(l31 * T + t0nx + 32 * nh + 4 * half) * 4u;
-        // GM, conv1 pair: e1 is the gradient that reaches the block output; its ReLU bits: dword t0 / 32 + nh of the lane's row
-        constexpr bool GME = GM && (EPI == EPI_ADD || EPI == EPI_ADDSTATS);
-        const wm_srd_t spm = FOLD ? make_srd(reinterpret_cast<const float*>(a.pmask) + ((size_t)b * 64 + 32 * mt) * nwm,
-                                             (size_t)32 * nwm * sizeof(unsigned)) : se1;
-        const wm_srd_t spy = FOLD ? make_srd(a.py2 + slab, (size_t)32 * T * sizeof(float)) : se1;
-        const wm_srd_t sme = GME ? make_srd(reinterpret_cast<const float*>(a.gmask) + ((size_t)b * 64 + 32 * mt) * nwm,
-                                            (size_t)32 * nwm * sizeof(unsigned)) : se1;
-        const size_t slabn = ((size_t)bnx * 64 + 32 * mt) * T;
-        const wm_srd_t spmn = FOLD ? make_srd(reinterpret_cast<const float*>(a.pmask) + ((size_t)bnx * 64 + 32 * mt) * nwm,
-                                              (size_t)32 * nwm * sizeof(unsigned)) : se1;
-        const wm_srd_t spyn = FOLD ? make_srd(a.py2 + slabn, (size_t)32 * T * sizeof(float)) : se1;
-        const wm_srd_t smen = GME ? make_srd(reinterpret_cast<const float*>(a.gmask) + ((size_t)bnx * 64 + 32 * mt) * nwm,
-                                             (size_t)32 * nwm * sizeof(unsigned)) : se1;
-        const unsigned emoffn = ((unsigned)l31 * nwm + ((unsigned)t0nx >> 5) + (unsigned)nh) * 4u;
-        const unsigned xoffn = xlane + (unsigned)(t0nx + 32 * nh) * 4u, xoff = xlane + (unsigned)(t0 + 32 * nh) * 4u;
-
-        STAMP(ts0);
-        // ---------------- phase A: data gradient out of image D
-        f32x16 dacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-        {
-            const unsigned short* drow = Db + (32 * nh + l31) * PITCH + 8 * half;
-            u32x4 Bq[2][NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) Bq[0][p] = *reinterpret_cast<const u32x4*>(drow + p * ROWS * PITCH);
-#pragma unroll
-            for (int s = 0; s < 12; ++s) {
-                if (s + 1 < 12) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        Bq[(s + 1) & 1][p] = *reinterpret_cast<const u32x4*>(drow + (p * ROWS + ((s + 1) >> 2)) * PITCH + 16 * ((s + 1) & 3));
-                }
-                const u32x4* Bf = Bq[s & 1];
-                // the weight-gradient accumulators stay where they are across this phase: left alone, the allocator lends a[0:15] of
-                // one of them to dacc and copies it out and back around every phase A (32 v_accvgpr moves per tile)
-                if ((s & 3) == 1) asm volatile("" : "+a"(wacc[0]), "+a"(wacc[1]), "+a"(wacc[2]));
-#pragma unroll
-                for (int j = 0; j < NPR; ++j) {
-                    FENCE;
-                    dacc = mma(Bf[PB(j)], Wr[s][PA(j)], dacc);      // D^T: rows = time, columns = channel (gradient piece PB, weight piece PA)
-                    FENCE;
-                    // SPM slices of side work behind this MFMA (72 slices per phase whatever the arithmetic)
-#pragma unroll
-                    for (int i_ = 0; i_ < SPM; ++i_) {
-                        const int m = (s * NPR + j) * SPM + i_;          // 0..71
-                        if (XL && m < 8 && (m & 1)) ec[m >> 1] = buf_load4(se1n, xoffn, row8T[m >> 1]);
-                        if (XL && FOLD && m >= 8 && m < 16 && (m & 1)) pyc[(m - 8) >> 1] = buf_load4(spyn, xoffn, row8T[(m - 8) >> 1]);
-                        if (m < NSA) {
-                            sideA(m, Gn, Xn); refillA(m);
-                            if (GME && m == 61) emkn = __builtin_bit_cast(unsigned, buf_load(smen, emoffn, 0u));
-                            if (FOLD && m == 62) pmkn = __builtin_bit_cast(unsigned, buf_load(spmn, emoffn, 0u));
-                        }
-                        else if (XL) { }
-                        else if (((m - NSA) & 1) == 0) e1n[(m - NSA) >> 1] = buf_load4(se1n, eoffn + 32u * ((m - NSA) >> 1), 0u);
-                        else if (FOLD) pyn[(m - NSA) >> 1] = buf_load4(spyn, eoffn + 32u * ((m - NSA) >> 1), 0u);
-                    }
-                    FENCE;
-                }
-            }
-        }
-        STAMP(ts1);
-#ifdef WM_STAMP
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        STAMP(ts1b);
-        asm volatile("s_barrier" ::: "memory");
-#else
-        lds_barrier();          // every wave is done with image D; images G', X' of the next tile are complete
-#endif
-        STAMP(ts2);
-        // ---------------- phase B: weight gradient out of images G', X'; image D of the next tile, epilogue of this one
-        {
-            const int e0 = 8 * half;
-            u32x4 A[2][NP];
-            uint4 f[2][NP];
-            unsigned Lw[2][NP], Rw[2][NP];
-            u32x4 Bl[NP], Br[NP];
-            auto read_kb = [&](int kb, int set) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    A[set][p] = *reinterpret_cast<const u32x4*>(Gc + (p * 64 + mt * 32 + l31) * PG + kb * 16 + e0);
-                    const unsigned short* xr = Xc + (p * 64 + nh * 32 + l31) * PX + XO + kb * 16 + e0;
-                    f[set][p] = *reinterpret_cast<const uint4*>(xr);
-                    Lw[set][p] = *reinterpret_cast<const unsigned*>(xr - 2);
-                    Rw[set][p] = *reinterpret_cast<const unsigned*>(xr + 8);
-                }
-            };
-            auto shl = [&](int set, int p) {
-                const uint4 g = f[set][p];
-                uint4 s_ = make_uint4(__builtin_amdgcn_alignbit(g.x, Lw[set][p], 16), __builtin_amdgcn_alignbit(g.y, g.x, 16),
-                                      __builtin_amdgcn_alignbit(g.z, g.y, 16), __builtin_amdgcn_alignbit(g.w, g.z, 16));
-                asm volatile("" : "+v"(s_.x), "+v"(s_.y), "+v"(s_.z), "+v"(s_.w));
-                Bl[p] = __builtin_bit_cast(u32x4, s_);
-            };
-            auto shr = [&](int set, int p) {
-                const uint4 g = f[set][p];
-                uint4 s_ = make_uint4(__builtin_amdgcn_alignbit(g.y, g.x, 16), __builtin_amdgcn_alignbit(g.z, g.y, 16),
-                                      __builtin_amdgcn_alignbit(g.w, g.z, 16), __builtin_amdgcn_alignbit(Rw[set][p], g.w, 16));
-                asm volatile("" : "+v"(s_.x), "+v"(s_.y), "+v"(s_.z), "+v"(s_.w));
-                Br[p] = __builtin_bit_cast(u32x4, s_);
-            };
-            // epilogue of accumulator registers 2 i, 2 i + 1 of the data gradient (two time steps of the lane's channel); every second
-            // call completes a quad and stores it
-            auto epi2 = [&](int i) {
-                const int r0 = 2 * i, r1 = 2 * i + 1;
-                float v0 = dacc[r0], v1 = dacc[r1];
-                if (H) { v0 *= dinv; v1 *= dinv; }                // undo the gradient's and the weights' scales (a power of two: exact)
-                const float q0_ = e1q[r0 >> 2][r0 & 3], q1_ = e1q[r1 >> 2][r1 & 3];
-                if (EPI == EPI_RELUMASK) {
-                    // both compares first, both selects after: a select right behind its compare costs two wait states
-                    const bool k0 = fmaf(q0_, kea, keb) > 0.f, k1 = fmaf(q1_, kea, keb) > 0.f;
-                    v0 = k0 ? v0 : 0.f; v1 = k1 ? v1 : 0.f;
-                    s1 += v0; s2 = fmaf(v0, q0_, s2);
-                    s1 += v1; s2 = fmaf(v1, q1_, s2);
-                    asm volatile("" : "+v"(s1), "+v"(s2));
-                } else if (GM) {
-                    // bits 8 q + 4 half + e of the row's dword: shifted by 4 half once (first call), then constant field positions
-                    if (i == 0) emk >>= 4 * half;
-                    v0 += __uint_as_float(__float_as_uint(q0_) & (unsigned)__builtin_amdgcn_sbfe((int)emk, 8 * (r0 >> 2) + (r0 & 3), 1));
-                    v1 += __uint_as_float(__float_as_uint(q1_) & (unsigned)__builtin_amdgcn_sbfe((int)emk, 8 * (r1 >> 2) + (r1 & 3), 1));
-                } else {
-                    v0 += q0_; v1 += q1_;
-                }
-                if (FOLD) {
-                    // what leaves is dz2 of the PREVIOUS block: its output's ReLU mask on the gradient just formed, and the two sums its
-                    // BatchNorm backward needs (sum dz2, sum dz2 y2) -- that block then has no reduction pass of its own
-                    if (i == 0) pmk >>= 4 * half;
-                    v0 = __uint_as_float(__float_as_uint(v0) & (unsigned)__builtin_amdgcn_sbfe((int)pmk, 8 * (r0 >> 2) + (r0 & 3), 1));
-                    v1 = __uint_as_float(__float_as_uint(v1) & (unsigned)__builtin_amdgcn_sbfe((int)pmk, 8 * (r1 >> 2) + (r1 & 3), 1));
-                    s1 += v0; s2 = fmaf(v0, pyq[r0 >> 2][r0 & 3], s2);
-                    s1 += v1; s2 = fmaf(v1, pyq[r1 >> 2][r1 & 3], s2);
-                    asm volatile("" : "+v"(s1), "+v"(s2));
-                }
-                dacc[r0] = v0; dacc[r1] = v1;
-                if (H && (STATS || EPI == EPI_ADD)) vmax = fmaxf(vmax, fmaxf(fabsf(v0), fabsf(v1)));   // one v_max3 per pair
-                if (i & 1) {
-                    const int q4 = i >> 1;
-                    const f32x4 quad = {dacc[4 * q4], dacc[4 * q4 + 1], dacc[4 * q4 + 2], dacc[4 * q4 + 3]};
-                    if (XL) *reinterpret_cast<f32x4*>(Ex + l31 * EXP + 8 * q4 + 4 * half) = quad;
-                    else buf_store4(sye, quad, eoff + 32u * q4, 0u);
-                }
-            };
-            read_kb(0, 0);
-            // the slice behind old-style MFMA index m (18 per k-block): shifts of the X fragments first, then 12 free slices per k-block
-            // = 48: image D of the next tile in every second one of the first 24, the epilogue quads in the last 24
-            auto sliceB = [&](int m) __attribute__((always_inline)) {
-                const int kb = m / 18, mm = m % 18, set = kb & 1;
-                if (mm < 3) { if (mm < NP) shl(set, mm); }
-                else if (mm < 6) { if (mm - 3 < NP) shr(set, mm - 3); }
-                else {
-                    const int v = kb * 12 + (mm - 6);             // 0..47
-                    if (v < 2 * NSB) {
-                        if ((v & 1) == 0) sideB(v >> 1); else refillB(v);
-                        if (XL) {       // the next tile's epilogue operands: row layout -> exchange tile -> accumulator layout
-                            if (v == 3) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x4*>(Ex + (xrow + 8 * r) * EXP + xcol) = ec[r];
-                            }
-                            if (v == 5) {
-#pragma unroll
-                                for (int q4 = 0; q4 < 4; ++q4) e1n[q4] = *reinterpret_cast<const f32x4*>(Ex + l31 * EXP + 8 * q4 + 4 * half);
-                            }
-                            if (FOLD && v == 9) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x4*>(Ex + (xrow + 8 * r) * EXP + xcol) = pyc[r];
-                            }
-                            if (FOLD && v == 11) {
-#pragma unroll
-                                for (int q4 = 0; q4 < 4; ++q4) pyn[q4] = *reinterpret_cast<const f32x4*>(Ex + l31 * EXP + 8 * q4 + 4 * half);
-                            }
-                        }
-                    }
-                    else if (XL) {      // epilogue quads every second slice, then the result tile leaves in row layout
-                        if (v < 40) { if ((v & 1) == 0) epi2((v - 24) >> 1); }
-                        else if ((v & 1) == 0) {
-                            const int r = (v - 40) >> 1;
-                            buf_store4(sye, *reinterpret_cast<const f32x4*>(Ex + (xrow + 8 * r) * EXP + xcol), xoff, row8T[r]);
-                        }
-                    }
-                    else if (v >= 24 && ((v - 24) % 3) == 0) epi2((v - 24) / 3);
-                }
-                // the next k-block's fragments (the other register set is free since this k-block began); with two slices per MFMA the
-                // old place (slice 12 of 18) left them only three MFMAs to arrive
-                if (mm == (H ? 4 : 12) && kb + 1 < 4) read_kb(kb + 1, set ^ 1);
-            };
-#pragma unroll
-            for (int m = 0; m < 12 * NPR; ++m) {
-                const int kb = m / (3 * NPR), tg = (m % (3 * NPR)) / NPR, j = m % NPR, set = kb & 1;
-                FENCE;
-                if (tg == 0)
-                    wacc[1] = mma(A[set][PA(j)], __builtin_bit_cast(u32x4, f[set][PB(j)]), wacc[1]);
-                else if (tg == 1)
-                    wacc[0] = mma(A[set][PA(j)], Bl[PB(j)], wacc[0]);
-                else
-                    wacc[2] = mma(A[set][PA(j)], Br[PB(j)], wacc[2]);
-                FENCE;
-#pragma unroll
-                for (int i_ = 0; i_ < SPM; ++i_) sliceB(m * SPM + i_);
-                FENCE;
-#ifdef WM_STAMP
-                if (m == 6 * NPR - 1) { STAMP(tsh); tm[5] += tsh - ts2; }     // end of the second k-block: first half of phase B
-#endif
-            }
-            okh_cur = okh_n; hsh_cur = hsh_n;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) { e1q[q4] = e1n[q4]; if (FOLD) pyq[q4] = pyn[q4]; }
-            emk = emkn; pmk = pmkn;
-        }
-        STAMP(ts3);
-        lds_barrier();          // image D of the next tile is complete; images G', X' of this tile are free
-        STAMP(ts4);
-#ifdef WM_STAMP
-        tm[0] += ts1 - ts0; tm[1] += ts2 - ts1; tm[2] += ts3 - ts2; tm[3] += ts4 - ts3; tm[4] += ts1b - ts1;
-#endif
-        tile += tstep;
-        buf ^= 1;
-    }
-#undef FENCE
-
-#ifdef WM_STAMP
-    if (g_wm_stamp && lane == 0) {
-        unsigned long long* d = g_wm_stamp + ((size_t)blockIdx.x * 4 + wave) * 6;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) d[i] = tm[i];
-    }
-#endif
-    // ---- outputs: weight-gradient slab (every wave owns its block), bias sums, BatchNorm sums of the data gradient
-    float* out = a.partial + (size_t)blockIdx.x * (KW * 4096 + 64);
-#pragma unroll
-    for (int k = 0; k < KW; ++k)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[(k * 64 + mt * 32 + mfma_row(r, half)) * 64 + nh * 32 + l31] = wacc[k][r] * ginv;   // x is unscaled
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {       // the eight lanes of a channel pair sit 8 apart
-        float v = bsum[j] * ginv;
-        v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-        if (lane < 8) out[KW * 4096 + c0 + j] = v;
-    }
-    if (STATS) {
-        float* red = reinterpret_cast<float*>(smem_raw);          // [2 column halves][2][64]
-        s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);       // the two time halves of the lane's channel
-        __syncthreads();
-        if (half == 0) {
-            red[nh * 128 + 32 * mt + l31] = s1;
-            red[nh * 128 + 64 + 32 * mt + l31] = s2;
-        }
-        __syncthreads();
-        if (tid < 128) a.stats[(size_t)blockIdx.x * 128 + tid] = red[tid] + red[128 + tid];
-    }
-    if (H && (STATS || EPI == EPI_ADD) && a.dzmax) {          // max |y| of this workgroup's output: the next consumer's gradient scale
-        float* red = reinterpret_cast<float*>(smem_raw);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        __syncthreads();
-        if (lane == 0) red[wave] = vmax;
-        __syncthreads();
-        if (tid == 0) a.dzmax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    }
-}
-
-template <int EPI, int XPRO, bool GM, bool H>
-int launch_dwgrad64bf(const DWArgs& a, int* grid_out, hipStream_t stream) {
-    constexpr int NP = H ? 2 : 3;
-    constexpr size_t lds = (size_t)(NP * 66 * 72 + 2 * NP * 64 * 72 + 2 * NP * 64 * 88) * 2 + 8 * 64 * sizeof(float) +
-                           (H ? (size_t)4 * 32 * 36 * sizeof(float) : 0);
-    static wm::DevOnce attr_done;
-    auto kern = dwgrad64bf_kernel<EPI, XPRO, GM, H>;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
-    const int ntiles = a.B * (a.T / 64);
-    const int grid = ntiles < kNumCU ? ntiles : kNumCU;
-    *grid_out = grid;
-    if (a.stats && grid < kNumCU) WM_TRY(hipMemsetAsync(a.stats, 0, sizeof(float) * 128 * kNumCU, stream));
-    if (H && a.dzmax && grid < kNumCU) WM_TRY(hipMemsetAsync(a.dzmax, 0, sizeof(float) * kNumCU, stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace
 
 // =============================================================================================
@@ -3897,45 +2176,7 @@ int launch_dwgrad64bf(const DWArgs& a, int* grid_out, hipStream_t stream) {
 // =============================================================================================
 extern "C" {
 
-#ifdef WM_STAMP
-int wm_debug_set_stamp_buffer(unsigned long long* buf) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wm_stamp), &buf, sizeof(buf));
-}
-#endif
-
-int wm_pack_w64(const float* w, float* wp, int KW, int mode, hipStream_t stream) {
-    if ((KW != 3 && KW != 7) || mode < 0 || mode > 3) return (int)hipErrorInvalidValue;
-    const int n = KW * 4096;
-    hipLaunchKernelGGL(pack_w64_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, w, wp, KW, mode);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-// Generic 64->64 'same' convolution on [B,64,T] (T % 4 == 0).
-//   pro: 0 none | 1 relu(x*pa[c]+pb[c]) | 2 x+pa[b*64+c] | 3 pa[c]*x + pb[c] + pc[c]*x2
-//   epi: 0 +bias | 1 mask by (e1*ea[c]+eb[c] > 0), stats = (sum v, sum v*e1) | 2 +e1 | 3 none
-//   stats (may be NULL; epi 0: (sum y, sum y^2)): [256][2][64] partial sums, reduce with wm_bn_finalize*.
-int wm_conv64(const float* x, const float* x2, const float* wp, const float* pa, const float* pb, const float* pc,
-              const float* bias, const float* e1, const float* ea, const float* eb, float* y, float* stats,
-              int B, int T, int KW, int pro, int epi, hipStream_t stream) {
-    if (B <= 0 || T <= 0 || (T & 3)) return (int)hipErrorInvalidValue;
-    Conv64Args a{x, x2, wp, pa, pb, pc, bias, e1, ea, eb, y, stats, B, T};
-    const bool st = stats != nullptr;
-    if (KW == 3) {
-        if (pro == PRO_NONE && epi == EPI_BIAS)
-            return st ? launch_conv64<3, 256, PRO_NONE, EPI_BIAS, true>(a, stream) : launch_conv64<3, 256, PRO_NONE, EPI_BIAS, false>(a, stream);
-        if (pro == PRO_BNRELU && epi == EPI_BIAS)
-            return st ? launch_conv64<3, 256, PRO_BNRELU, EPI_BIAS, true>(a, stream) : launch_conv64<3, 256, PRO_BNRELU, EPI_BIAS, false>(a, stream);
-        if (pro == PRO_BNBWD && epi == EPI_RELUMASK && st) return launch_conv64<3, 128, PRO_BNBWD, EPI_RELUMASK, true>(a, stream);
-        if (pro == PRO_BNBWD && epi == EPI_ADD && !st) return launch_conv64<3, 128, PRO_BNBWD, EPI_ADD, false>(a, stream);
-        if (pro == PRO_BNBWD && epi == EPI_NONE && !st) return launch_conv64<3, 128, PRO_BNBWD, EPI_NONE, false>(a, stream);
-    } else if (KW == 7 && !st) {
-        if (pro == PRO_ADDVEC && epi == EPI_BIAS) return launch_conv64<7, 128, PRO_ADDVEC, EPI_BIAS, false>(a, stream);
-        if (pro == PRO_NONE && epi == EPI_BIAS) return launch_conv64<7, 128, PRO_NONE, EPI_BIAS, false>(a, stream);
-        if (pro == PRO_NONE && epi == EPI_NONE) return launch_conv64<7, 128, PRO_NONE, EPI_NONE, false>(a, stream);
-    }
-    return (int)hipErrorInvalidValue;
-}
+WM_STAMP_SETTER(wm_debug_set_stamp_buffer)
 
 // bf16x6 build of the k3 convolution (fp32-grade results on the bf16 matrix cores); wpb from wm_pack_w64_bf.
 // Same pro / epi / stats contract as wm_conv64 with KW = 3.
@@ -3993,15 +2234,6 @@ int wm_conv64_bf(const float* x, const float* x2, const void* wpb, const float* 
     if (pro == PRO_BNBWD && epi == EPI_ADD && !st) return launch_conv64bf<PRO_BNBWD, EPI_ADD, false>(a, stream);
     if (pro == PRO_BNBWD && epi == EPI_NONE && !st) return launch_conv64bf<PRO_BNBWD, EPI_NONE, false>(a, stream);
     return (int)hipErrorInvalidValue;
-}
-
-// inference ResBlock in one launch (both BatchNorms folded): see resblock_eval_kernel
-int wm_resblock_eval_bf(const float* x, const void* w1pb, const void* w2pb, const float* b1, const float* sc1, const float* sh1,
-                        const float* b2, const float* sc2, const float* sh2, float* y, int B, int T, int arith, hipStream_t stream) {
-    if (B <= 0 || T <= 0 || (T & 3) || (arith != 0 && arith != 1)) return (int)hipErrorInvalidValue;
-    if (!x || !w1pb || !w2pb || !sc1 || !sh1 || !sc2 || !sh2 || !y) return (int)hipErrorInvalidValue;
-    RbeArgs a{x, w1pb, w2pb, b1, sc1, sh1, b2, sc2, sh2, y, B, T};
-    return arith == 1 ? launch_resblock_eval<true>(a, stream) : launch_resblock_eval<false>(a, stream);
 }
 
 // bf16x6 build of the 7-tap ConvTranspose1d (forward: mode 2 image, pro 0|2, epi 0; data gradient: mode 3 image, pro 0, epi 3)
@@ -4085,7 +2317,6 @@ int wm_wgrad64_bf(const float* g, const float* g2, const float* ga, const float*
     return 0;
 }
 
-// data gradient + weight gradient of a k3 convolution in one launch (dwgrad64bf_kernel); T % 64 == 0
 // f16 two-piece weight image for wm_dwgrad64_bf arith 1: 2 * 3 * 4096 f16 + 2 floats (mode 0 forward | 1 data gradient, as wm_pack_w64_bf)
 int wm_pack_w64_h(const float* w, void* wph, int mode, hipStream_t stream) {
     if (!w || !wph || mode < 0 || mode > 1) return (int)hipErrorInvalidValue;
@@ -4097,53 +2328,6 @@ int wm_pack_w64_h(const float* w, void* wph, int mode, hipStream_t stream) {
 int wm_pack_w64_h_scaled(const float* w, const float* row_scale, void* wph, hipStream_t stream) {
     if (!w || !row_scale || !wph) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(pack_w64_h_kernel, dim3(1), dim3(1024), 0, stream, w, row_scale, reinterpret_cast<unsigned short*>(wph), 0);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-int wm_dwgrad64_bf(const float* g, const float* g2, const float* ga, const float* gb, const float* gc, const void* wpb,
-                   const float* x, const float* xa, const float* xb, const float* e1, const float* ea, const float* eb,
-                   float* y, float* stats, float* partial, float* dw, float* dbias, int B, int T, int xpro, int epi, int accumulate,
-                   const void* gmask, int arith, const float* gscale, float* dzmax, hipStream_t stream) {
-    if (B <= 0 || T <= 0 || (T & 63)) return (int)hipErrorInvalidValue;
-    if (!g || !g2 || !ga || !gb || !gc || !wpb || !x || !e1 || !y || !partial || !dw) return (int)hipErrorInvalidValue;
-    if (arith != 0 && (arith != 1 || !gscale)) return (int)hipErrorInvalidValue;
-    DWArgs a{g, g2, ga, gb, gc, wpb, x, xa, xb, e1, ea, eb, y, stats, partial, B, T, reinterpret_cast<const unsigned*>(gmask),
-             epi == EPI_ADDSTATS ? reinterpret_cast<const unsigned*>(eb) : nullptr, epi == EPI_ADDSTATS ? ea : nullptr, gscale, dzmax};
-    int grid = 0, rc = (int)hipErrorInvalidValue;
-#define WM_DW(E, X, G) (arith ? launch_dwgrad64bf<E, X, G, true>(a, &grid, stream) : launch_dwgrad64bf<E, X, G, false>(a, &grid, stream))
-    if (epi == EPI_RELUMASK && xpro == PRO_BNRELU && stats && xa && xb && ea && eb)
-        rc = gmask ? WM_DW(EPI_RELUMASK, PRO_BNRELU, true) : WM_DW(EPI_RELUMASK, PRO_BNRELU, false);
-    else if (epi == EPI_ADD && xpro == PRO_NONE && !stats)
-        rc = gmask ? WM_DW(EPI_ADD, PRO_NONE, true) : WM_DW(EPI_ADD, PRO_NONE, false);
-    else if (epi == EPI_ADDSTATS && xpro == PRO_NONE && stats && ea && eb && gmask)
-        rc = WM_DW(EPI_ADDSTATS, PRO_NONE, true);
-#undef WM_DW
-    if (rc) return rc;
-    const int n = 3 * 4096 + 64;
-    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, (const float*)partial, grid, 3, 0, dw,
-                       dbias, accumulate & 1);
-    WM_CHECK_LAUNCH();
-    return 0;
-}
-
-// Weight gradient of a 64->64 convolution.  partial: [256][KW*4096+64] scratch.
-//   gpro: 0 g as is | 3 ga[c]*g + gb[c] + gc[c]*g2     xpro: 0 | 1 relu(x*xa+xb) | 2 x+xa[b*64+c]
-//   layout: 0 Conv1d weight [out][in][KW] | 1 ConvTranspose1d weight [in][out][KW]
-int wm_wgrad64(const float* g, const float* g2, const float* ga, const float* gb, const float* gc,
-               const float* x, const float* xa, const float* xb, float* partial, float* dw, float* dbias,
-               int B, int T, int KW, int gpro, int xpro, int layout, int accumulate, hipStream_t stream) {
-    if (B <= 0 || T <= 0 || (T & 3)) return (int)hipErrorInvalidValue;
-    Wgrad64Args a{g, g2, ga, gb, gc, x, xa, xb, partial, B, T};
-    int grid = 0, rc = (int)hipErrorInvalidValue;
-    if (KW == 3 && gpro == PRO_BNBWD && xpro == PRO_BNRELU) rc = launch_wgrad64<3, PRO_BNBWD, PRO_BNRELU>(a, &grid, stream);
-    else if (KW == 3 && gpro == PRO_BNBWD && xpro == PRO_NONE) rc = launch_wgrad64<3, PRO_BNBWD, PRO_NONE>(a, &grid, stream);
-    else if (KW == 7 && gpro == PRO_NONE && xpro == PRO_ADDVEC) rc = launch_wgrad64<7, PRO_NONE, PRO_ADDVEC>(a, &grid, stream);
-    else if (KW == 7 && gpro == PRO_NONE && xpro == PRO_NONE) rc = launch_wgrad64<7, PRO_NONE, PRO_NONE>(a, &grid, stream);
-    if (rc) return rc;
-    const int n = KW * 4096 + 64;
-    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, (const float*)partial, grid, KW,
-                       layout, dw, dbias, accumulate);
     WM_CHECK_LAUNCH();
     return 0;
 }

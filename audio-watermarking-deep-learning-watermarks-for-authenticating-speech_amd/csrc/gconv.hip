@@ -324,10 +324,7 @@ int launch_gconv2(GConvArgs a, hipStream_t stream) {
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
     auto kern = gconv2_kernel<MW, WM, WN, VECW>;
     static wm::DevOnce once;
-    if (!wm::dev_done(once)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        wm::dev_mark(once);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, once)) return rc;
     dim3 grid((a.Nout + BN - 1) / BN, (a.Mtot + BM - 1) / BM, a.NB);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a);
     WM_CHECK_LAUNCH();
@@ -601,10 +598,7 @@ int launch_gconvh_x(GConvHArgs ha, hipStream_t stream) {
     if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
     auto kern = gconvh_kernel<MW, WM, WN, XRH>;
     static wm::DevOnce once;
-    if (!wm::dev_done(once)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        wm::dev_mark(once);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, once)) return rc;
     dim3 grid((a.Nout + BN - 1) / BN, (a.Mtot + BM - 1) / BM, a.NB);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, ha);
     WM_CHECK_LAUNCH();
@@ -972,10 +966,7 @@ template <int WA, int NS, bool GEO1>
 int launch_gwgrad2(const GWArgs& g, dim3 grid, size_t lds, hipStream_t stream) {
     auto kern = gwgrad2_kernel<WA, NS, GEO1>;
     static wm::DevOnce once;
-    if (!wm::dev_done(once)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        wm::dev_mark(once);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), 150 * 1024, once)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, g);
     WM_CHECK_LAUNCH();
     return 0;

@@ -1553,19 +1553,13 @@ int wm_lstm_fwd_fused(const float* x, const float* w_ih, const float* b_ih, cons
                       float* gates, float* cst, int B, int T, hipStream_t stream) {
     if ((T & 3) || T < 8) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)2 * 32 * 257 * sizeof(float) + (size_t)3 * 32 * 72 * 2 + 128 * sizeof(float);
-    static wm::DevOnce done;
-    if (!wm::dev_done(done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_fwd_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_fwd_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(done);
-    }
+    static wm::DevOnce done[2];
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_fused_kernel<true>), lds, done[0])) return rc;
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_fused_kernel<false>), lds, done[1])) return rc;
     if (g_lstm_fwd_ws) {                            // wave-specialised build: the projection on four helper waves (default)
-        static wm::DevOnce donew;
-        if (!wm::dev_done(donew)) {
-            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            wm::dev_mark(donew);
-        }
+        static wm::DevOnce donew[2];
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<true>), lds, donew[0])) return rc;
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<false>), lds, donew[1])) return rc;
         if (gates && cst) hipLaunchKernelGGL(lstm_fwd_ws_kernel<true>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
         else hipLaunchKernelGGL(lstm_fwd_ws_kernel<false>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
         WM_CHECK_LAUNCH();
@@ -1590,10 +1584,7 @@ int wm_lstm_bwd_fused(float* gates, const float* cst, const float* dh_out, const
     if ((T & 3) || T < 4) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)2 * 4 * 3 * 32 * 72 * 2 + (size_t)(4 * 64 * 33 + 4 * 64 + 2 * 64 * 4) * sizeof(float);
     static wm::DevOnce done;
-    if (!wm::dev_done(done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_bwd_fused_kernel), lds, done)) return rc;
     hipLaunchKernelGGL(lstm_bwd_fused_kernel, dim3(B), dim3(256), lds, stream, gates, cst, dh_out, w_hh, w_ih, dx, T);
     WM_CHECK_LAUNCH();
     return 0;
@@ -1607,10 +1598,7 @@ int wm_lstm_bwd_wgrad(float* gates, const float* cst, const float* dh_out, const
     if (B <= 0 || (T & 31) || T < 64) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)(2 * 256 * 36 + 2 * 64 * 4) * sizeof(float);
     static wm::DevOnce done;
-    if (!wm::dev_done(done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_bwd_ws_kernel), lds, done)) return rc;
     hipLaunchKernelGGL(lstm_bwd_ws_kernel, dim3(B), dim3(512), lds, stream, gates, cst, dh_out, w_hh, x, h, partial, T);
     WM_CHECK_LAUNCH();
     hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3(kWgradSlab / 64), dim3(512), 0, stream, (const float*)partial, B,
@@ -1627,14 +1615,14 @@ int wm_lstm_dx(const float* da, const float* w_ih, float* dx, int B, int T, hipS
     if (g_lstm_dx_bf) {
         constexpr size_t ldsb = (size_t)3 * 64 * 264 * 2;
         static wm::DevOnce doneb;
-        if (!wm::dev_done(doneb)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_dx_bf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); wm::dev_mark(doneb); }
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_dx_bf_kernel), ldsb, doneb)) return rc;
         hipLaunchKernelGGL(lstm_dx_bf_kernel, dim3(ntiles < kNumCU ? ntiles : kNumCU), dim3(256), ldsb, stream, da, w_ih, dx, B, T);
         WM_CHECK_LAUNCH();
         return 0;
     }
     constexpr size_t lds = (size_t)(256 * 64 + 64 * 257) * sizeof(float);
     static wm::DevOnce done;
-    if (!wm::dev_done(done)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); wm::dev_mark(done); }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_dx_kernel), lds, done)) return rc;
     hipLaunchKernelGGL(lstm_dx_kernel, dim3(ntiles < kNumCU ? ntiles : kNumCU), dim3(256), lds, stream, da, w_ih, dx, B, T);
     WM_CHECK_LAUNCH();
     return 0;
@@ -1647,14 +1635,14 @@ int wm_lstm_wgrad(const float* da, const float* x, const float* h, float* partia
     if (g_lstm_dx_bf) {                           // same switch as wm_lstm_dx: bf16x6 (default) | native fp32 MFMA
         constexpr size_t ldsb = (size_t)(3 * 32 * 264 + 3 * 128 * 40) * 2;
         static wm::DevOnce doneb;
-        if (!wm::dev_done(doneb)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_wgrad_bf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); wm::dev_mark(doneb); }
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_wgrad_bf_kernel), ldsb, doneb)) return rc;
         const int ntiles = B * ((T + 31) / 32);
         grid = ntiles < kNumCU ? ntiles : kNumCU;
         hipLaunchKernelGGL(lstm_wgrad_bf_kernel, dim3(grid), dim3(256), ldsb, stream, da, x, h, partial, B, T);
     } else {
         constexpr size_t lds = (size_t)(64 * 256 + 128 * 67) * sizeof(float);
         static wm::DevOnce done;
-        if (!wm::dev_done(done)) { WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); wm::dev_mark(done); }
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_wgrad_kernel), lds, done)) return rc;
         const int ntiles = B * ((T + 63) / 64);
         grid = ntiles < kNumCU ? ntiles : kNumCU;
         hipLaunchKernelGGL(lstm_wgrad_kernel, dim3(grid), dim3(256), lds, stream, da, x, h, partial, B, T);

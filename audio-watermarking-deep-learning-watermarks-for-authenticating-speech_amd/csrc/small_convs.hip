@@ -636,10 +636,7 @@ int wm_stem_bwd(const float* g, const float* s, const float* w, float* ds, float
     if (T & 3) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)(64 * 264 + 296 + 4 * 256) * sizeof(float);
     static wm::DevOnce attr_done;
-    if (!wm::dev_done(attr_done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(attr_done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(stem_bwd_kernel), lds, attr_done)) return rc;
     const int ntiles = B * ((T + 255) / 256);
     const int grid = ntiles < WM_STEM_WGS_PER_CU * kNumCU ? ntiles : WM_STEM_WGS_PER_CU * kNumCU;
     hipLaunchKernelGGL(stem_bwd_kernel, dim3(grid), dim3(256), lds, stream, g, s, w, ds, partial, B, T, nds);
@@ -700,10 +697,7 @@ int launch_headN_fwd(const HeadNFwd& a, hipStream_t stream) {
     const size_t lds = (size_t)256 * (NOC > 0 ? NOC : (a.NO | 1)) * sizeof(float);
     if constexpr (NOC == 0) {                                   // up to 65 KB of staging rows
         static wm::DevOnce done;
-        if (!wm::dev_done(done)) {
-            WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_fwd_kernel<NOC, TAIL, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 65 * (int)sizeof(float)));
-            wm::dev_mark(done);
-        }
+        if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(headN_fwd_kernel<NOC, TAIL, LOSS>), 256 * 65 * sizeof(float), done)) return rc;
     }
     const unsigned magic = (unsigned)((0x100000000ull + a.NO - 1) / a.NO);
     hipLaunchKernelGGL((headN_fwd_kernel<NOC, TAIL, LOSS>), dim3(a.R * ((a.T + 255) / 256)), dim3(256), lds, stream, a.x, a.y2, a.scale,
@@ -763,10 +757,7 @@ template <int NOC, int NT, bool DL>
 int launch_headN_bwd(const HeadNBwd& a, int grid, hipStream_t stream) {
     constexpr size_t lds = (size_t)(64 * 257 + 256 * (32 * NT + 1) + 32 * NT * 64) * sizeof(float);
     static wm::DevOnce done;
-    if (!wm::dev_done(done)) {
-        WM_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(headN_bwd_kernel<NOC, NT, DL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        wm::dev_mark(done);
-    }
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(headN_bwd_kernel<NOC, NT, DL>), lds, done)) return rc;
     const unsigned magic = a.NO > 1 ? (unsigned)((0x100000000ull + a.NO - 1) / a.NO) : 0u;
     hipLaunchKernelGGL((headN_bwd_kernel<NOC, NT, DL>), dim3(grid), dim3(256), lds, stream, a.g, a.x, a.w, a.dx, a.partial, a.R, a.T, a.NO,
                        magic, a.message, a.g_loc, a.g_bce, a.BL);

@@ -26,6 +26,13 @@ inline void dev_mark(DevOnce& d) {
     if (hipGetDevice(&dev) != hipSuccess) return;
     d.mask.fetch_or(1ull << (dev & 63), std::memory_order_release);
 }
+// the opt-in itself, once per device and kernel (one DevOnce per kernel); 0 or the hipError_t of the attribute call
+inline int lds_opt_in(const void* kern, size_t lds, DevOnce& once) {
+    if (dev_done(once)) return 0;
+    WM_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    dev_mark(once);
+    return 0;
+}
 
 // host only: do [a, a + na) and [b, b + nb) share a byte?  The launchers refuse in-place calls with it.
 inline bool overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {

@@ -1,4 +1,5 @@
-"""diagnostic: where a conv64 workgroup spends its cycles (needs the -DWM_STAMP build libwm_hip_stamp.so)"""
+"""diagnostic: where a conv64 workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64_fp32.hip and csrc/conv64.hip:
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64_fp32.hip csrc/conv64.hip -o libwm_hip_stamp.so)"""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 so = os.environ.get("WM_STAMP_LIB") or os.path.join(ROOT, "audio-watermarking-deep-learning-watermarks-for-authenticating-speech_amd", "libwm_hip_stamp.so")
@@ -10,7 +11,7 @@ c = [torch.rand(128, device=dev) for _ in range(5)]
 stats = torch.empty(256 * 128, device=dev)
 buf = torch.zeros(256 * 4 * 6, dtype=torch.int64, device=dev)
 vp = ctypes.c_void_p
-L.wm_debug_set_stamp_buffer(vp(buf.data_ptr()))
+L.wm_debug_set_stamp_buffer_fp32(vp(buf.data_ptr())); L.wm_debug_set_stamp_buffer(vp(buf.data_ptr()))      # one copy per unit
 L.wm_pack_w64(vp(w.data_ptr()), vp(wp.data_ptr()), 3, 0, None)
 wpb = torch.empty(3 * 3 * 4096, dtype=torch.int16, device=dev)
 L.wm_pack_w64_bf(vp(w.data_ptr()), vp(wpb.data_ptr()), 0, None)

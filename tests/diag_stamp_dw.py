@@ -1,5 +1,6 @@
-"""diagnostic: where a dwgrad64bf workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64.hip:
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64.hip -o libwm_hip_stamp.so)"""
+"""diagnostic: where a dwgrad64bf workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64_dwgrad.hip, with
+csrc/conv64.hip for the weight images:
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64_dwgrad.hip csrc/conv64.hip -o libwm_hip_stamp.so)"""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 so = os.environ.get("WM_STAMP_LIB") or os.path.join(ROOT, "audio-watermarking-deep-learning-watermarks-for-authenticating-speech_amd", "libwm_hip_stamp.so")
@@ -17,7 +18,7 @@ stats = torch.empty(256 * 128, device=dev); wpart = torch.empty(256 * (3 * 4096 
 dw = torch.empty(64, 64, 3, device=dev); db = torch.empty(64, device=dev)
 buf = torch.zeros(256 * 4 * 6, dtype=torch.int64, device=dev)
 vp = ctypes.c_void_p
-L.wm_debug_set_stamp_buffer(vp(buf.data_ptr()))
+L.wm_debug_set_stamp_buffer_dwgrad(vp(buf.data_ptr()))
 ARITH = 1 if os.environ.get("WM_DIAG_ARITH", "1") == "1" else 0       # 1: f16 two-piece split (default backward), 0: bf16x6
 wpb = torch.empty(3 * 3 * 4096 + 4, dtype=torch.int16, device=dev)
 gsc = torch.tensor([1.0, 1.0], device=dev)

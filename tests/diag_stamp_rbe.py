@@ -1,5 +1,6 @@
-"""diagnostic: where a resblock_eval workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64.hip:
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWM_STAMP -shared csrc/conv64.hip -o libwm_hip_stamp.so)"""
+"""diagnostic: where a resblock_eval workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64_eval.hip, with
+csrc/conv64.hip for the weight images:
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64_eval.hip csrc/conv64.hip -o libwm_hip_stamp.so)"""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 so = os.environ.get("WM_STAMP_LIB") or os.path.join(ROOT, "audio-watermarking-deep-learning-watermarks-for-authenticating-speech_amd", "libwm_hip_stamp.so")
@@ -11,7 +12,7 @@ c = [torch.rand(64, device=dev) for _ in range(6)]
 wm_scaled = True
 buf = torch.zeros(256 * 4 * 6, dtype=torch.int64, device=dev)
 vp = ctypes.c_void_p
-L.wm_debug_set_stamp_buffer(vp(buf.data_ptr()))
+L.wm_debug_set_stamp_buffer_eval(vp(buf.data_ptr()))
 wp1 = torch.empty(3 * 3 * 4096, dtype=torch.int16, device=dev); wp2 = torch.empty_like(wp1)
 L.wm_pack_w64_bf_scaled(vp(w1.data_ptr()), vp(c[1].data_ptr()), vp(wp1.data_ptr()), None); L.wm_pack_w64_bf_scaled(vp(w2.data_ptr()), vp(c[4].data_ptr()), vp(wp2.data_ptr()), None)
 args = [vp(x.data_ptr()), vp(wp1.data_ptr()), vp(wp2.data_ptr())] + [vp(t.data_ptr()) for t in c] + [vp(y.data_ptr()), B, T, 0, None]
