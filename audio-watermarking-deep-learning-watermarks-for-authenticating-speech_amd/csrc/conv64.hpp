@@ -13,7 +13,7 @@
 //   packed weights [tap][cin][cout] live in LDS for the whole kernel --> MFMA A operand
 //   D tile (cout x time) leaves the accumulators as 128-B row segments (time is contiguous).
 //
-// This header: what the conv64*.hip units (one kernel family or more each) share, and nothing else.  Each unit
+// This header: what the conv64*.hip units (one kernel family each) share, and nothing else.  Each unit
 // compiles its own copy.  For those units only: it opens namespace wm and defines file-local typedefs and knob defaults.
 #pragma once
 #include "wm_common.hpp"
@@ -24,7 +24,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef WM_STAMP
 // diagnostic build only (-DWM_STAMP): per-wave cycle totals of the kernel's phases.  A device global cannot span translation units
-// without relocatable device code: every unit has its own copy and defines its own setter with WM_STAMP_SETTER
+// without relocatable device code: every unit has its own copy, and one that stamps defines its own setter with WM_STAMP_SETTER
 static __device__ unsigned long long* g_wm_stamp = nullptr;
 #define STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
 #define WM_STAMP_SETTER(name) int name(unsigned long long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wm_stamp), &buf, sizeof(buf)); }
@@ -64,9 +64,9 @@ static __device__ unsigned long long* g_wm_stamp = nullptr;
 namespace {
 enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_ADDVEC = 2, PRO_BNBWD = 3 };
 enum { EPI_BIAS = 0, EPI_RELUMASK = 1, EPI_ADD = 2, EPI_NONE = 3, EPI_BNADDRELU = 4,    // 4: relu(e1 + (acc + bias) * ea + eb), conv64bf3 only
-       EPI_BIASELU = 5, EPI_BIASADDELU = 6, EPI_MULDELU = 7,
-       EPI_ADDSTATS = 8 };    // dwgrad64bf only: EPI_ADD, then the ReLU mask of the PREVIOUS block and its two BatchNorm sums   // main14b_2's 64-channel blocks (conv64bf_kernel only): elu(acc + bias),
+       EPI_BIASELU = 5, EPI_BIASADDELU = 6, EPI_MULDELU = 7,    // main14b_2's 64-channel blocks (conv64bf_kernel only): elu(acc + bias),
                                                                  // elu(acc + bias + e1), acc * ELU'(e1) with e1 = the ELU output y
+       EPI_ADDSTATS = 8 };    // dwgrad64bf only: EPI_ADD, then the ReLU mask of the PREVIOUS block and its two BatchNorm sums
 
 struct Conv64Args {
     const float* x;     // [B,64,T] primary input

@@ -234,7 +234,7 @@ __device__ __forceinline__ float elu1(float v) {
 
 
 
-// ---- bf16x6 split arithmetic (see conv64.hip): x = hi + mid + lo as three bf16 pieces, exact to 24 bits
+// ---- bf16x6 split arithmetic (see conv64_fwd.hip): x = hi + mid + lo as three bf16 pieces, exact to 24 bits
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 

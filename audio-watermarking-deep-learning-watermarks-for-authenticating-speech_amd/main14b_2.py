@@ -71,7 +71,7 @@ def _gconv_raw(x, wp, bias, K, S, P, Mtot, Nout, st, shp, Cout, Lout, act=0, res
 
 
 # ---- the 64 -> 64, k3, stride-1 convolutions of this variant (conv2 of the first encoder block, the 64-channel decoder blocks) are
-# the SAME shape as main16's ResBlock convolution: they run on its bf16x6 kernels (csrc/conv64.hip, fp32-grade arithmetic on the
+# the SAME shape as main16's ResBlock convolution: they run on its bf16x6 kernels (csrc/conv64_fwd.hip, fp32-grade arithmetic on the
 # bf16 matrix cores, ~1.7x the rate of the generic fp32-MFMA kernel), with ELU-family epilogues instead of BatchNorm ones.
 def _c64_ok(w, stride, padding, L):
     return (tuple(w.shape) == (64, 64, 3) and stride == 1 and padding == 1 and L % 4 == 0 and L >= 4 and ops.conv_bf16x6())

@@ -244,7 +244,7 @@ def switches(**values):
 
 
 def set_conv_bf_schedule(schedule: int):
-    """0: phase-serial kernel, 2: register-resident weights + interleaved split (csrc/conv64.hip)."""
+    """0: phase-serial kernel, 2: register-resident weights + interleaved split (csrc/conv64_fwd.hip)."""
     set_switch("schedule", schedule)
 
 

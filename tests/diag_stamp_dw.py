@@ -1,6 +1,6 @@
 """diagnostic: where a dwgrad64bf workgroup spends its cycles (needs the -DWM_STAMP build of csrc/conv64_dwgrad.hip, with
-csrc/conv64.hip for the weight images:
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64_dwgrad.hip csrc/conv64.hip -o libwm_hip_stamp.so)"""
+csrc/conv64_fwd.hip for the weight images:
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -pragma-unroll-threshold=100000 -DWM_STAMP -shared csrc/conv64_dwgrad.hip csrc/conv64_fwd.hip -o libwm_hip_stamp.so)"""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 so = os.environ.get("WM_STAMP_LIB") or os.path.join(ROOT, "audio-watermarking-deep-learning-watermarks-for-authenticating-speech_amd", "libwm_hip_stamp.so")
