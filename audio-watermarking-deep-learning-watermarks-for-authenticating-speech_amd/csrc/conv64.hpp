@@ -62,7 +62,8 @@ static __device__ unsigned long long* g_wm_stamp = nullptr;
 #endif
 
 namespace {
-enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_ADDVEC = 2, PRO_BNBWD = 3 };
+enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_ADDVEC = 2, PRO_BNBWD = 3,
+       PRO_TAIL = 4 };    // conv64bf3 (f16 build) only: the previous ResBlock's tail relu(x + x2 * pa + pb), also stored to tout / tmask
 enum { EPI_BIAS = 0, EPI_RELUMASK = 1, EPI_ADD = 2, EPI_NONE = 3, EPI_BNADDRELU = 4,    // 4: relu(e1 + (acc + bias) * ea + eb), conv64bf3 only
        EPI_BIASELU = 5, EPI_BIASADDELU = 6, EPI_MULDELU = 7,    // main14b_2's 64-channel blocks (conv64bf_kernel only): elu(acc + bias),
                                                                  // elu(acc + bias + e1), acc * ELU'(e1) with e1 = the ELU output y
@@ -82,6 +83,8 @@ struct Conv64Args {
     float* y;           // [B,64,T]
     float* stats;       // [gridDim.x][2][64] partial sums or nullptr
     int B, T;
+    float* tout = nullptr;       // [B,64,T] PRO_TAIL: the formed input, as wm_bn_add_relu_mask writes it
+    unsigned* tmask = nullptr;   // [B*64][T/32] PRO_TAIL: its sign bits (wm_bn_add_relu_mask's layout) or nullptr
 };
 
 template <int PRO>
@@ -89,6 +92,7 @@ __device__ __forceinline__ float pro_apply(float v, float v2, float ca, float cb
     if (PRO == PRO_BNRELU) return fmaxf(fmaf(v, ca, cb), 0.f);
     if (PRO == PRO_ADDVEC) return v + ca;
     if (PRO == PRO_BNBWD) return fmaf(ca, v, fmaf(cc, v2, cb)) + cl;      // cb + cl: offset as hi + lo words (pb[0..63], pb[64..127])
+    if (PRO == PRO_TAIL) return fmaxf(v + fmaf(v2, ca, cb), 0.f);         // bn_add_relu_kernel's expression (bn.hip), to the letter
     return v;
 }
 

@@ -266,7 +266,9 @@ template <int PRO, int EPI, bool STATS, bool H = false>
 __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     constexpr int KW = 3, NT = 128, ROWS = NT + 2, PITCH = 72, NP = H ? 2 : 3, NC = 4;
     constexpr int XBUF = NP * ROWS * PITCH;               // bf16 elements per input image
-    constexpr bool TWO = (PRO == PRO_BNBWD);
+    constexpr bool TAIL = (PRO == PRO_TAIL);              // the input is the previous ResBlock's tail, formed here from x and x2 = y2
+    constexpr bool TWO = (PRO == PRO_BNBWD || TAIL);
+    static_assert(!TAIL || H, "the tail prologue exists in the f16 build only");
     constexpr bool E1 = (EPI == EPI_RELUMASK || EPI == EPI_ADD || EPI == EPI_BNADDRELU);
     extern __shared__ __align__(16) unsigned char smem_raw[];
     unsigned short* Xb0 = reinterpret_cast<unsigned short*>(smem_raw);             // 2 x [NP][ROWS][PITCH]
@@ -333,8 +335,8 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
 #endif
     load_tile(min(tile, ntiles - 1));
     if (tid < 64) {
-        Cs[tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pa[tid] : 0.f;
-        Cs[64 + tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pb[tid] : 0.f;
+        Cs[tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD || TAIL) ? a.pa[tid] : 0.f;
+        Cs[64 + tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD || TAIL) ? a.pb[tid] : 0.f;
         Cs[128 + tid] = (PRO == PRO_BNBWD) ? a.pc[tid] : 0.f;
         Cs[192 + tid] = (PRO == PRO_BNBWD) ? a.pb[64 + tid] : (((EPI == EPI_BIAS || EPI == EPI_BNADDRELU) && a.bias) ? a.bias[tid] : 0.f);
         Cs[256 + tid] = (EPI == EPI_RELUMASK || EPI == EPI_BNADDRELU) ? a.ea[tid] : 0.f;
@@ -343,8 +345,27 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     __syncthreads();
     // per-thread prologue constants (the staging channels never change)
     const float ka0 = Cs[c0], ka1 = Cs[c0 + 1], kb0 = Cs[64 + c0], kb1 = Cs[64 + c0 + 1];
-    const float kc0 = Cs[128 + c0], kc1 = Cs[128 + c0 + 1], kl0 = TWO ? Cs[192 + c0] : 0.f, kl1 = TWO ? Cs[192 + c0 + 1] : 0.f;
-    const float ha = Cs[hc], hb = Cs[64 + hc], hcc = Cs[128 + hc], hlo = TWO ? Cs[192 + hc] : 0.f;
+    const float kc0 = Cs[128 + c0], kc1 = Cs[128 + c0 + 1];
+    const float kl0 = (PRO == PRO_BNBWD) ? Cs[192 + c0] : 0.f, kl1 = (PRO == PRO_BNBWD) ? Cs[192 + c0 + 1] : 0.f;
+    const float ha = Cs[hc], hb = Cs[64 + hc], hcc = Cs[128 + hc], hlo = (PRO == PRO_BNBWD) ? Cs[192 + hc] : 0.f;
+
+    // PRO_TAIL: the formed value goes back into its staging register, and tail_store() writes the combo's two rows x one time quad
+    // to `tout` as the tail kernel would have (16-B stores), with their sign bits: the eight lanes that share lane & 7 hold the 32
+    // steps of one mask word of each row; lane >> 3 == 0 stores the first row's word, == 1 the second's (a null tmask: a descriptor
+    // of zero bytes, every store dropped).  A halo column is rebuilt from x and x2 and never stored.
+    auto keep_formed = [&](int i, int e, float va, float vb) {
+        if (e == 0) { sa[i].x = va; sb[i].x = vb; } else if (e == 1) { sa[i].y = va; sb[i].y = vb; }
+        else if (e == 2) { sa[i].z = va; sb[i].z = vb; } else { sa[i].w = va; sb[i].w = vb; }
+    };
+    const wm_srd_t smask = make_srd(reinterpret_cast<const float*>(a.tmask), (TAIL && a.tmask) ? (size_t)a.B * 64 * (T >> 5) * 4 : 0);
+    auto tail_store = [&](int tb, int tt0, int i) {
+        const size_t o = ((size_t)tb * 64 + c0) * T + tt0 + 4 * (q0 + 8 * i);
+        *reinterpret_cast<float4*>(a.tout + o) = sa[i];
+        *reinterpret_cast<float4*>(a.tout + o + T) = sb[i];
+        const unsigned ma = mask_merge8(sign_nibble(sa[i]) << (4 * q0)), mb = mask_merge8(sign_nibble(sb[i]) << (4 * q0));
+        const unsigned word = (unsigned)(tb * 64 + c0 + (q0 & 1)) * (unsigned)(T >> 5) + (unsigned)((tt0 >> 5) + i);
+        __builtin_amdgcn_raw_buffer_store_b32((q0 & 1) ? mb : ma, smask, (int)(q0 < 2 ? word * 4u : 0xFFFFFF00u), 0, 0);
+    };
 
     // one (combo i, element e) unit of the split: two channels x one time step -> 3 dwords
     auto split_unit = [&](unsigned* X32, int t0, int i, int e) {
@@ -360,6 +381,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
             }
             va = pro_apply<PRO>(va, wa, ka0, kb0, kc0, kl0);
             vb = pro_apply<PRO>(vb, wb, ka1, kb1, kc1, kl1);
+            if (TAIL) keep_formed(i, e, va, vb);
         }
         const int o = (1 + 4 * (q0 + 8 * i) + e) * (PITCH / 2) + cp;
         if (H) {
@@ -406,6 +428,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
             }
             va = pro_apply<PRO>(va, wa, ka0, kb0, kc0, kl0);
             vb = pro_apply<PRO>(vb, wb, ka1, kb1, kc1, kl1);
+            if (TAIL) keep_formed(i, e, va, vb);
         }
         sva = va; svb = vb;
         asm volatile("" : "+v"(sva), "+v"(svb));
@@ -457,6 +480,10 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
 #pragma unroll
         for (int u = 0; u < 16; ++u) split_unit(reinterpret_cast<unsigned*>(Xb0), t0, u >> 2, u & 3);
         split_halo(Xb0, t0);
+        if (TAIL) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) tail_store(min(tile, ntiles - 1) / tilesPerClip, t0, i);
+        }
     }
     load_tile(min(tile + tstep, ntiles - 1));
     __syncthreads();
@@ -536,7 +563,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         // tiles past the end are clamped: their (valid) data lands in the image nobody reads again
         const int next = min(tile + tstep, ntiles - 1), next2 = min(tile + 2 * tstep, ntiles - 1);
         const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
-        const int nt0 = (next % tilesPerClip) * NT;
+        const int nb_ = next / tilesPerClip, nt0 = (next - nb_ * tilesPerClip) * NT;
         const wm_srd_t se1c = E1 ? row_srd(a.e1, b) : syp;
         const unsigned vcolc = lcol + (unsigned)(t0 + 64 * nh) * 4u;
         const unsigned short* xcur = Xb0 + buf * XBUF;
@@ -561,7 +588,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         if (h < 16) {                                                                                                           \
             if ((k) == 0) split_pick(h >> 2, h & 3);                                                                            \
             if ((k) == 1) split_st1();                                                                                          \
-            if ((k) == 2) split_st2();                                                                                          \
+            if ((k) == 2) { split_st2(); if (TAIL && (h & 3) == 3) tail_store(nb_, nt0, h >> 2); }                              \
             if ((k) == 3) { split_out(reinterpret_cast<unsigned*>(xnxt), h >> 2, h & 3); if ((h & 3) == 3) load_combo(next2, h >> 2); } \
         } else if (h == 16) {                                                                                                   \
             if ((k) == 0) halo_pick(nt0);                                                                                       \
@@ -589,8 +616,13 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
             FENCE;
             if (H) {                                     // lo hi, hi lo, hi hi: two slices behind every MFMA
                 acc[nt] = mma(Wr[s][1], Bf[0], acc[nt]); FENCE; BF3_SLICE(0) FENCE; BF3_SLICE(1) FENCE;
-                acc[nt] = mma(Wr[s][0], Bf[1], acc[nt]); FENCE; BF3_SLICE(3) FENCE; BF3_SLICE(4) FENCE;
-                acc[nt] = mma(Wr[s][0], Bf[0], acc[nt]); FENCE; BF3_SLICE(5) FENCE;
+                if (TAIL) {                              // slice 2 (free in this build) stores a finished combo of the formed tile
+                    acc[nt] = mma(Wr[s][0], Bf[1], acc[nt]); FENCE; BF3_SLICE(2) FENCE; BF3_SLICE(3) FENCE;
+                    acc[nt] = mma(Wr[s][0], Bf[0], acc[nt]); FENCE; BF3_SLICE(4) FENCE; BF3_SLICE(5) FENCE;
+                } else {
+                    acc[nt] = mma(Wr[s][0], Bf[1], acc[nt]); FENCE; BF3_SLICE(3) FENCE; BF3_SLICE(4) FENCE;
+                    acc[nt] = mma(Wr[s][0], Bf[0], acc[nt]); FENCE; BF3_SLICE(5) FENCE;
+                }
             } else {
                 acc[nt] = mma(Wr[s][1], Bf[1], acc[nt]); FENCE; BF3_SLICE(0) FENCE;
                 acc[nt] = mma(Wr[s][0], Bf[2], acc[nt]); FENCE; BF3_SLICE(1) FENCE;
@@ -840,6 +872,20 @@ int wm_conv64_bf(const float* x, const float* x2, const void* wpb, const float* 
     if (pro == PRO_BNBWD && epi == EPI_ADD && !st) return launch_conv64bf<PRO_BNBWD, EPI_ADD, false>(a, stream);
     if (pro == PRO_BNBWD && epi == EPI_NONE && !st) return launch_conv64bf<PRO_BNBWD, EPI_NONE, false>(a, stream);
     return (int)hipErrorInvalidValue;
+}
+
+// A training ResBlock's conv1 whose input is the PREVIOUS block's tail, formed on load: out = relu(x + y2 * sc2 + sh2) and its sign
+// bits leave as side products exactly as wm_bn_add_relu_mask writes them (mask may be null), y = conv(out) + bias and stats exactly as
+// wm_conv64_bf(pro 0, epi 0, arith 1) on that out.  wpb_h from wm_pack_w64_h (mode 0).  The pipelined f16 build only: anything else
+// (T % 128 != 0, schedule 0, no stats) is hipErrorInvalidValue and nothing is written.
+int wm_conv64_bf_tail(const float* x, const float* y2, const void* wpb_h, const float* sc2, const float* sh2, const float* bias,
+                      float* out, void* mask, float* y, float* stats, int B, int T, hipStream_t stream) {
+    if (B <= 0 || T <= 0 || (T & 127) || g_bf_schedule != 2) return (int)hipErrorInvalidValue;
+    if (!x || !y2 || !wpb_h || !sc2 || !sh2 || !out || !y || !stats) return (int)hipErrorInvalidValue;
+    if ((unsigned long long)B * 64ull * (unsigned long long)(T >> 5) * 4ull >= 0xfffff000ull) return (int)hipErrorInvalidValue;   // mask offsets are 32-bit
+    Conv64Args a{x, y2, reinterpret_cast<const float*>(wpb_h), sc2, sh2, nullptr, bias, nullptr, nullptr, nullptr, y, stats, B, T,
+                 out, reinterpret_cast<unsigned*>(mask)};
+    return launch_conv64bf3<PRO_TAIL, EPI_BIAS, true, true>(a, stream);
 }
 
 // f16 two-piece weight image for wm_dwgrad64_bf arith 1: 2 * 3 * 4096 f16 + 2 floats (mode 0 forward | 1 data gradient, as wm_pack_w64_bf)

@@ -491,11 +491,22 @@ __global__ __launch_bounds__(256) void lstm_fwd_fused_kernel(const float* __rest
 // into the other half of the double-buffered LDS table.  The helpers execute the recurrence's one barrier per step and use those
 // barriers as their own phase separators: slot 0 of a chunk splits the x tile into the LDS image, slots 1..24 issue two MFMAs each,
 // slot 26 stores the table.  Same arithmetic and summation order as the fused kernel: bit-identical results.
-template <bool SAVE>
+// TAIL (T % 32 == 0): x is the input of the ResBlock in front of the LSTM and the helpers form that block's tail while they stage it,
+// v = relu(x + y2 * sc2 + sh2) in bn_add_relu_kernel's expression (bn.hip), split v as before, and in the idle slot 27 store the
+// chunk's v to `out` and its sign bits to `mask` (wm_bn_add_relu_mask's layout; the staging map is conv64bf3's, see sign_nibble)
+template <bool TAIL>
+struct LstmTailArgs {};
+template <>
+struct LstmTailArgs<true> {
+    const float* y2; const float* sc2; const float* sh2;   // [B,64,T], [64], [64]
+    float* out; unsigned* mask;                            // [B,64,T], [B*64][T/32] or nullptr
+};
+template <bool SAVE, bool TAIL = false>
 __global__ __launch_bounds__(512) void lstm_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ w_ih,
                                                           const float* __restrict__ b_ih, const float* __restrict__ b_hh,
                                                           const float* __restrict__ w_hh, float* __restrict__ hout,
-                                                          float* __restrict__ gates, float* __restrict__ cst, int T) {
+                                                          float* __restrict__ gates, float* __restrict__ cst, int T,
+                                                          LstmTailArgs<TAIL> tl) {
     constexpr int CH = 32, XPP = 257, PITCH = 72, NP = 3;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     float* xps = reinterpret_cast<float*>(smem_raw);                                  // [2][CH][XPP]
@@ -587,14 +598,36 @@ __global__ __launch_bounds__(512) void lstm_fwd_ws_kernel(const float* __restric
     const int cp = hw * 8 + (lane & 7), tq = lane >> 3;    // x tile staging: channel pair cp, time quad tq of the chunk
     const float* xc = x + ((size_t)b * 64 + 2 * cp) * T + 4 * tq;
     float4 sa, sb;
+    [[maybe_unused]] float4 sa2, sb2, oa, ob;      // TAIL: the y2 quads in flight, the formed quads until their store
+    [[maybe_unused]] const float* yc = nullptr;
+    [[maybe_unused]] float* oc = nullptr;
+    [[maybe_unused]] float tsc0 = 0.f, tsc1 = 0.f, tsh0 = 0.f, tsh1 = 0.f;
+    if constexpr (TAIL) {
+        yc = tl.y2 + ((size_t)b * 64 + 2 * cp) * T + 4 * tq;
+        oc = tl.out + ((size_t)b * 64 + 2 * cp) * T + 4 * tq;
+        tsc0 = tl.sc2[2 * cp]; tsc1 = tl.sc2[2 * cp + 1]; tsh0 = tl.sh2[2 * cp]; tsh1 = tl.sh2[2 * cp + 1];
+    }
     auto load_x = [&](int t0) {                    // clamped: chunks past the end re-read the last valid quad
         const int t = min(t0, T - 4 - 4 * tq);
         sa = *reinterpret_cast<const float4*>(xc + max(t, -4 * tq));
         sb = *reinterpret_cast<const float4*>(xc + T + max(t, -4 * tq));
+        if constexpr (TAIL) {
+            sa2 = *reinterpret_cast<const float4*>(yc + max(t, -4 * tq));
+            sb2 = *reinterpret_cast<const float4*>(yc + T + max(t, -4 * tq));
+        }
     };
     auto split_x = [&]() {
         unsigned* X32 = reinterpret_cast<unsigned*>(Xb);
-        const float va[4] = {sa.x, sa.y, sa.z, sa.w}, vb[4] = {sb.x, sb.y, sb.z, sb.w};
+        float va[4] = {sa.x, sa.y, sa.z, sa.w}, vb[4] = {sb.x, sb.y, sb.z, sb.w};
+        if constexpr (TAIL) {
+            const float wa[4] = {sa2.x, sa2.y, sa2.z, sa2.w}, wb[4] = {sb2.x, sb2.y, sb2.z, sb2.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                va[e] = fmaxf(va[e] + fmaf(wa[e], tsc0, tsh0), 0.f);
+                vb[e] = fmaxf(vb[e] + fmaf(wb[e], tsc1, tsh1), 0.f);
+            }
+            oa = make_float4(va[0], va[1], va[2], va[3]); ob = make_float4(vb[0], vb[1], vb[2], vb[3]);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             unsigned p0, p1, p2;
@@ -625,10 +658,24 @@ __global__ __launch_bounds__(512) void lstm_fwd_ws_kernel(const float* __restric
 #pragma unroll
             for (int r = 0; r < 16; ++r) dst[mt * 32 + (r & 3) + 8 * (r >> 2)] = acc[mt][r];
     };
+    // TAIL: the formed chunk at steps [tc, tc + 32) (tc < T, so nothing was clamped): two 16-B stores, and the two rows' mask words
+    // from the lanes with tq == 0 / 1 (a null mask: a descriptor of zero bytes, the stores are dropped)
+    [[maybe_unused]] auto store_tail = [&](int tc) {
+        if constexpr (TAIL) {
+            *reinterpret_cast<float4*>(oc + tc) = oa;
+            *reinterpret_cast<float4*>(oc + T + tc) = ob;
+            const wm_srd_t smask = make_srd(reinterpret_cast<const float*>(tl.mask) + (size_t)b * 64 * (T >> 5),
+                                            tl.mask ? (size_t)64 * (T >> 5) * 4 : 0);
+            const unsigned ma = mask_merge8(sign_nibble(oa) << (4 * tq)), mb = mask_merge8(sign_nibble(ob) << (4 * tq));
+            const unsigned word = (unsigned)(2 * cp + (tq & 1)) * (unsigned)(T >> 5) + (unsigned)(tc >> 5);
+            __builtin_amdgcn_raw_buffer_store_b32((tq & 1) ? mb : ma, smask, (int)(tq < 2 ? word * 4u : 0xFFFFFF00u), 0, 0);
+        }
+    };
     // ---- prologue: projection of chunk 0, x tile of chunk 1 in flight (three barriers, matched by the recurrence waves)
     load_x(0);
     __syncthreads();
     split_x();
+    store_tail(0);
     load_x(CH);
     __syncthreads();
 #pragma unroll
@@ -642,6 +689,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_ws_kernel(const float* __restric
             if (s == 0) { split_x(); load_x(t0 + 2 * CH); }
             if (s >= 1 && s <= 24) { mfma_one(2 * (s - 1)); mfma_one(2 * (s - 1) + 1); }
             if (s == 26) store_xp(cbuf ^ 1);
+            if (TAIL && s == 27 && t0 + CH < T) store_tail(t0 + CH);
             if (t0 + s < T) __syncthreads();           // = the barrier of one recurrence step
         }
     }
@@ -1560,13 +1608,32 @@ int wm_lstm_fwd_fused(const float* x, const float* w_ih, const float* b_ih, cons
         static wm::DevOnce donew[2];
         if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<true>), lds, donew[0])) return rc;
         if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<false>), lds, donew[1])) return rc;
-        if (gates && cst) hipLaunchKernelGGL(lstm_fwd_ws_kernel<true>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
-        else hipLaunchKernelGGL(lstm_fwd_ws_kernel<false>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
+        if (gates && cst) hipLaunchKernelGGL(lstm_fwd_ws_kernel<true>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T, LstmTailArgs<false>{});
+        else hipLaunchKernelGGL(lstm_fwd_ws_kernel<false>, dim3(B), dim3(512), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T, LstmTailArgs<false>{});
         WM_CHECK_LAUNCH();
         return 0;
     }
     if (gates && cst) hipLaunchKernelGGL(lstm_fwd_fused_kernel<true>, dim3(B), dim3(256), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
     else hipLaunchKernelGGL(lstm_fwd_fused_kernel<false>, dim3(B), dim3(256), lds, stream, x, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// wm_lstm_fwd_fused on out = relu(xres + y2 * sc2 + sh2), the tail of the ResBlock in front of the LSTM, which the wave-specialised
+// kernel's helper waves form while they stage it: `out` and its sign bits (`mask`, may be null) are written exactly as
+// wm_bn_add_relu_mask writes them, hout / gates / cst exactly as wm_lstm_fwd_fused on that out.  Always the wave-specialised build;
+// T % 32 != 0 is hipErrorInvalidValue and nothing is written (no fallback inside: the caller keeps the two launches).
+int wm_lstm_fwd_tail(const float* xres, const float* y2, const float* sc2, const float* sh2, float* out, void* mask, const float* w_ih,
+                     const float* b_ih, const float* b_hh, const float* w_hh, float* hout, float* gates, float* cst, int B, int T,
+                     hipStream_t stream) {
+    if (B <= 0 || T < 32 || (T & 31) || !xres || !y2 || !sc2 || !sh2 || !out) return (int)hipErrorInvalidValue;
+    constexpr size_t lds = (size_t)2 * 32 * 257 * sizeof(float) + (size_t)3 * 32 * 72 * 2 + 128 * sizeof(float);
+    static wm::DevOnce done[2];
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<true, true>), lds, done[0])) return rc;
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_fwd_ws_kernel<false, true>), lds, done[1])) return rc;
+    const LstmTailArgs<true> tl{y2, sc2, sh2, out, reinterpret_cast<unsigned*>(mask)};
+    if (gates && cst) hipLaunchKernelGGL((lstm_fwd_ws_kernel<true, true>), dim3(B), dim3(512), lds, stream, xres, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T, tl);
+    else hipLaunchKernelGGL((lstm_fwd_ws_kernel<false, true>), dim3(B), dim3(512), lds, stream, xres, w_ih, b_ih, b_hh, w_hh, hout, gates, cst, T, tl);
     WM_CHECK_LAUNCH();
     return 0;
 }

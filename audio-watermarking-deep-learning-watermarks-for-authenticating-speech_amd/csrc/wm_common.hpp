@@ -283,4 +283,19 @@ __device__ __forceinline__ void buf_store(wm_srd_t srd, float v, unsigned voff_b
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), srd, (int)voff_bytes, (int)soff_bytes, 0);
 }
 
+// ---- sign bits of a staged frame tile (the ResBlock tail formed in its consumer: conv64bf3's PRO_TAIL, lstm_fwd_ws's TAIL)
+// In the staging map shared by those kernels (channel pair = lane & 7, time quad = lane >> 3) the eight lanes with one lane & 7 hold
+// the 32 steps of one word of wm_bn_add_relu_mask's layout.  nibble: bit e = (element e > 0); mask_merge8: OR over lane >> 3 without a
+// trip through LDS (one DPP rotate inside the 16-lane row, then the two gfx950 row / half swaps), valid in every lane.
+__device__ __forceinline__ unsigned sign_nibble(const float4& v) {
+    return ((v.x > 0.f) ? 1u : 0u) | ((v.y > 0.f) ? 2u : 0u) | ((v.z > 0.f) ? 4u : 0u) | ((v.w > 0.f) ? 8u : 0u);
+}
+__device__ __forceinline__ unsigned mask_merge8(unsigned m) {
+    m |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xf, 0xf, true);          // row_ror:8 = lane ^ 8
+    const auto r16 = __builtin_amdgcn_permlane16_swap(m, m, false, false);                  // lane ^ 16
+    m = r16[0] | r16[1];
+    const auto r32 = __builtin_amdgcn_permlane32_swap(m, m, false, false);                  // lane ^ 32
+    return r32[0] | r32[1];
+}
+
 }  // namespace wm

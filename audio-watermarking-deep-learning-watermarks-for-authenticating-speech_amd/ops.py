@@ -351,6 +351,40 @@ def set_tail_in_head(on: bool):
     _HEADS["tail_in_head"] = bool(on)
 
 
+# A ResBlock followed by another consumer of its output inside one tape node (encoder.1 -> encoder.2 -> LSTM, model.1 -> model.2)
+# leaves its tail to that consumer's forward kernel, which forms relu(x + sc2 * y2 + sh2) while it stages its input and writes `out`
+# and the sign bits as side products: the next block's conv1 (wm_conv64_bf_tail) and the LSTM's helper waves (wm_lstm_fwd_tail).
+# WM_TAIL_IN_CONSUMER=0/1 sets the default ("1" = on, else off).  Kept outside SWITCHES like _HEADS.
+def read_tail_in_consumer(environ) -> bool:
+    """what the switch starts with under `environ` (pure, as read_switches)"""
+    return environ.get("WM_TAIL_IN_CONSUMER", "1") == "1"
+
+
+_TAILC = {"on": read_tail_in_consumer(os.environ)}
+
+
+def set_tail_in_consumer(on: bool):
+    """1 (default): the tails of encoder.1, encoder.2 and model.1 are formed by the kernel that reads them next, where
+    tail_in_consumer_applies(); 0: each of them is a wm_bn_add_relu(_mask) launch.  Bit-identical either way: the same expression
+    element by element, no sum is regrouped."""
+    _TAILC["on"] = bool(on)
+
+
+def _tail_in_consumer_launches(x, lstm: bool = False) -> bool:
+    """the switch and what the two launches need: the f16 pipelined forward (the tail prologue exists in that build only, so
+    T % 128 == 0); lstm=True adds the wave-specialised fused LSTM forward.  What a tape node asks inside its forward, where autograd
+    has gradients switched off."""
+    ok = (_TAILC["on"] and x.is_cuda and x.dim() == 3 and x.shape[-1] % 128 == 0 and _CONV["bf16x6"] and _CONV["fwd_f16x3"]
+          and _CONV["schedule"] == 2)
+    return bool(ok and (not lstm or (_LSTM["fused"] and _LSTM["fwd_ws"])))
+
+
+def tail_in_consumer_applies(x, lstm: bool = False) -> bool:
+    """_tail_in_consumer_launches and the pair node's own precondition (pair_node_applies).  The caller adds: training-mode blocks, no
+    forward hooks."""
+    return _tail_in_consumer_launches(x, lstm) and bool(pair_node_applies(x))
+
+
 def set_gconv_f16x3(on: bool):
     """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
     two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
@@ -446,12 +480,18 @@ def pack_w64(w: torch.Tensor, kw: int, mode: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ ResBlock
-def _resblock_fwd(x, params, training, want_grad, tail=True):
+def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None):
     """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for params = (w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2).
     Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx.
-    tail=False (training mode only): stop in front of the tail -- (None, saved) with mask = None; the head kernel that follows forms
-    out = relu(x + y2 * cst[4] + cst[5]) and the mask (ResBlockHead1Fn, DetectorTailFn)."""
+    tail=False (training mode only): stop in front of the tail -- (None, saved) with mask = None; the kernel that follows forms
+    out = relu(x + y2 * cst[4] + cst[5]) and the mask (ResBlockHead1Fn, DetectorTailFn, or the next block through `pending`).
+    pending (training mode, tail_in_consumer_applies): the `saved` of the block in front, run with tail=False; x is ignored.  This
+    block's conv1 launch (wm_conv64_bf_tail) forms that block's tail on load and writes it -- this block's x -- and its mask; the
+    return value is then (out, saved, that mask)."""
     w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = params
+    if pending is not None:
+        px, py2, pcst = pending[0], pending[2], pending[4]
+        x, pmask = torch.empty_like(px), _tail_mask(px, want_grad)
     x = _frames(x, "ResBlock input", 64)
     B, _, T = x.shape
     dev, st = x.device, _stream()
@@ -461,7 +501,11 @@ def _resblock_fwd(x, params, training, want_grad, tail=True):
     if training:
         y1, y2 = torch.empty_like(x), torch.empty_like(x)
         stats = _f32(NCU * 128, device=dev)
-        _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, stats, B, T, 0, 0)
+        if pending is not None:
+            lib.wm_conv64_bf_tail(_p(px), _p(py2), _p(pack_w64_h(w1, 0)), _p(pcst[4]), _p(pcst[5]), _p(b1), _p(x), _p(pmask), _p(y1),
+                                  _p(stats), B, T, st)
+        else:
+            _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, stats, B, T, 0, 0)
         lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g1), _p(be1), _p(rm1), _p(rv1), _p(nbt1), BN_MOMENTUM, BN_EPS,
                            _p(sc1), _p(sh1), _p(mu1), _p(is1), st)
         _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, stats, B, T, 1, 0)
@@ -491,8 +535,9 @@ def _resblock_fwd(x, params, training, want_grad, tail=True):
         _conv3(y1, None, w2, 0, sc1, sh1, None, b2, None, None, None, y2, None, B, T, 1, 0)
         # saved (mean, invstd) for an eval-mode backward = running statistics
         mu1.copy_(rm1); is1.copy_(torch.rsqrt(rv1 + BN_EPS)); mu2.copy_(rm2); is2.copy_(torch.rsqrt(rv2 + BN_EPS))
+    more = () if pending is None else (pmask,)
     if not tail:
-        return None, (x, y1, y2, None, cst, w1, w2, g1, g2)
+        return (None, (x, y1, y2, None, cst, w1, w2, g1, g2)) + more
     if want_grad:
         # the backward needs only the SIGN of `out`: one bit per element, written beside it (a frame pass less in backward)
         mask = torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=dev)
@@ -500,7 +545,7 @@ def _resblock_fwd(x, params, training, want_grad, tail=True):
     else:
         mask = None
         lib.wm_bn_add_relu(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), B, T, st)
-    return out, (x, y1, y2, mask, cst, w1, w2, g1, g2)
+    return (out, (x, y1, y2, mask, cst, w1, w2, g1, g2)) + more
 
 
 class ResBlockFn(GradAwareFunction):
@@ -637,6 +682,19 @@ def pair_node_applies(x) -> bool:
             and _CONV["fused_bwd"] and _CONV["mask_on_load"] and _CONV["pair_fold"] and not _ASYNC["on"])
 
 
+def _pair_fwd(x, p1, p2, training, want_grad, tail=True):
+    """Two ResBlocks in a row, the second one up to `tail` (as _resblock_fwd's): (out | None, first, second), the two blocks' `saved`.
+    Where the tail-in-consumer launches apply, the first block's tail is formed by the second block's conv1 launch; same tensors
+    either way."""
+    if training and _tail_in_consumer_launches(x):
+        _, first = _resblock_fwd(x, p1, True, want_grad, tail=False)
+        out, second, pmask = _resblock_fwd(None, p2, True, want_grad, tail=tail, pending=first)
+        return out, first[:3] + (pmask,) + first[4:], second
+    mid, first = _resblock_fwd(x, p1, training, want_grad)
+    out, second = _resblock_fwd(mid, p2, training, want_grad, tail=tail)
+    return out, first, second
+
+
 class ResBlockPairFn(GradAwareFunction):
     """Two ResBlocks in a row (py/main16.py:135-136 encoder.1 -> encoder.2, :178-179 model.1 -> model.2) as one tape node.
     Forward = _resblock_fwd twice.  Backward: the second block's conv1 launch (data + weight gradient) applies the
@@ -647,8 +705,7 @@ class ResBlockPairFn(GradAwareFunction):
     @staticmethod
     def forward(ctx, x, *args):
         p1, p2, training = args[:14], args[14:28], args[28]
-        mid, first = _resblock_fwd(x, p1, training, wants_grad(ctx))
-        out, second = _resblock_fwd(mid, p2, training, wants_grad(ctx))
+        out, first, second = _pair_fwd(x, p1, p2, training, wants_grad(ctx))
         ctx.save_for_backward(*(first + second))
         ctx.training = bool(training)
         return out
@@ -797,9 +854,8 @@ class DetectorTailFn(GradAwareFunction):
     def forward(ctx, x, message, *args):
         p1, p2, hw, hb = args[:14], args[14:28], args[28], args[29]
         want = wants_grad(ctx)
-        mid, first = _resblock_fwd(x, p1, True, want)
-        _, second = _resblock_fwd(mid, p2, True, want, tail=False)
-        y2, cst = second[2], second[4]
+        _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False)
+        mid, y2, cst = second[0], second[2], second[4]
         R, _, T = mid.shape
         NO, B, dev = hw.shape[0], message.shape[0], mid.device
         out, mask = torch.empty_like(mid), _tail_mask(mid, want)
@@ -844,52 +900,103 @@ class LSTMFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        x = _frames(x, "LSTM input", 64)
-        B, _, T = x.shape
-        dev, st = x.device, _stream()
         need_grad = wants_grad(ctx)
-        h = torch.empty_like(x)
-        release_deferred_wgrads()                  # side stream: work queued for "beside the recurrence" starts now (eval_forward)
-        cst = _f32(B, T, 64, device=dev) if need_grad else None
-        if _LSTM["fused"] and T >= 8:               # input projection inside the recurrence kernel (no xp tensor)
-            gates = _f32(B, T, 256, device=dev) if need_grad else None
-            lib.wm_lstm_fwd_fused(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
-        else:
-            xp = _f32(B, T, 256, device=dev)
-            lib.wm_lstm_xproj(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(xp), B, T, st)
-            gates = xp if need_grad else None       # activations overwrite the projections in place
-            lib.wm_lstm_fwd(_p(xp), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
+        h, saved = _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, need_grad)
         if need_grad:
             ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
-            ctx.save_for_backward(x, h, gates, cst, w_ih, w_hh)
+            ctx.save_for_backward(*saved)
         return h
 
     @staticmethod
     def backward(ctx, dh):
-        x, h, gates, cst, w_ih, w_hh = ctx.saved_tensors
+        saved = ctx.saved_tensors
         _single_backward(ctx, "LSTMFn")
-        dh = dh.contiguous()
-        B, _, T = x.shape
-        dev, st = x.device, _stream()
-        dx = torch.empty_like(x)
-        release_deferred_wgrads()                  # side stream: the queued weight-gradient GEMMs run beside the recurrence
-        dst, acc, launch = _wgrad_dst(ctx.gdst, dev, w_ih.shape, w_hh.shape, (256,), (256,))     # dwi, dwh, dbi, dbh
-        if _LSTM["bwd_ws"] and not _LSTM["bwd_fused"] and T % 32 == 0 and T >= 64:
-            part = _f32(B * (256 * 128 + 256), device=dev)       # (this launch accumulates into the flat store from the main stream)
-            lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), st)
-            lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
-            return (dx,) + ((None,) * 4 if acc else dst)
-        if _LSTM["bwd_fused"]:                    # measured: no faster than the two launches; off by default
-            lib.wm_lstm_bwd_fused(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(w_ih), _p(dx), B, T, st)   # gates now holds da
-        else:
-            lib.wm_lstm_bwd(_p(gates), _p(cst), _p(dh), _p(w_hh), B, T, st)      # gates now holds da
-            lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
+        return _lstm_bwd(saved, ctx.gdst, dh)
 
-        def wg():
-            part = _f32(NCU * (256 * 128 + 256), device=dev)
-            lib.wm_lstm_wgrad(_p(gates), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), _stream())
-        launch((gates, x, h), wg)
+
+def _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, need_grad, tail=None):
+    """LSTMFn's forward: (h, saved) with saved = (x, h, gates, cst, w_ih, w_hh) for _lstm_bwd, None unless need_grad.  No ctx.
+    tail = (xres, y2, sc2, sh2, mask | None) of the ResBlock in front (tail_in_consumer_applies with lstm=True; x is ignored): the
+    launch (wm_lstm_fwd_tail) forms that block's output on load and writes it -- the LSTM's x -- and the mask."""
+    if tail is not None:
+        xres, y2, sc2, sh2, mask = tail
+        x = torch.empty_like(xres)
+    x = _frames(x, "LSTM input", 64)
+    B, _, T = x.shape
+    dev, st = x.device, _stream()
+    h = torch.empty_like(x)
+    release_deferred_wgrads()                  # side stream: work queued for "beside the recurrence" starts now (eval_forward)
+    cst = _f32(B, T, 64, device=dev) if need_grad else None
+    if tail is not None:
+        gates = _f32(B, T, 256, device=dev) if need_grad else None
+        lib.wm_lstm_fwd_tail(_p(xres), _p(y2), _p(sc2), _p(sh2), _p(x), _p(mask), _p(w_ih), _p(b_ih), _p(b_hh), _p(w_hh), _p(h),
+                             _p(gates), _p(cst), B, T, st)
+    elif _LSTM["fused"] and T >= 8:             # input projection inside the recurrence kernel (no xp tensor)
+        gates = _f32(B, T, 256, device=dev) if need_grad else None
+        lib.wm_lstm_fwd_fused(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
+    else:
+        xp = _f32(B, T, 256, device=dev)
+        lib.wm_lstm_xproj(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(xp), B, T, st)
+        gates = xp if need_grad else None       # activations overwrite the projections in place
+        lib.wm_lstm_fwd(_p(xp), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
+    return h, ((x, h, gates, cst, w_ih, w_hh) if need_grad else None)
+
+
+def _lstm_bwd(saved, gdst, dh):
+    """LSTMFn's backward on _lstm_fwd's saved tensors: (dx, dw_ih, dw_hh, db_ih, db_hh); gdst = the four destinations of _gdst"""
+    x, h, gates, cst, w_ih, w_hh = saved
+    dh = dh.contiguous()
+    B, _, T = x.shape
+    dev, st = x.device, _stream()
+    dx = torch.empty_like(x)
+    release_deferred_wgrads()                  # side stream: the queued weight-gradient GEMMs run beside the recurrence
+    dst, acc, launch = _wgrad_dst(gdst, dev, w_ih.shape, w_hh.shape, (256,), (256,))     # dwi, dwh, dbi, dbh
+    if _LSTM["bwd_ws"] and not _LSTM["bwd_fused"] and T % 32 == 0 and T >= 64:
+        part = _f32(B * (256 * 128 + 256), device=dev)       # (this launch accumulates into the flat store from the main stream)
+        lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), st)
+        lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
         return (dx,) + ((None,) * 4 if acc else dst)
+    if _LSTM["bwd_fused"]:                    # measured: no faster than the two launches (DESIGN.md section 9); off by default
+        lib.wm_lstm_bwd_fused(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(w_ih), _p(dx), B, T, st)   # gates now holds da
+    else:
+        lib.wm_lstm_bwd(_p(gates), _p(cst), _p(dh), _p(w_hh), B, T, st)      # gates now holds da
+        lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
+
+    def wg():
+        part = _f32(NCU * (256 * 128 + 256), device=dev)
+        lib.wm_lstm_wgrad(_p(gates), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), _stream())
+    launch((gates, x, h), wg)
+    return (dx,) + ((None,) * 4 if acc else dst)
+
+
+class EncoderLSTMFn(GradAwareFunction):
+    """encoder.1 -> encoder.2 -> lstm (py/main16.py:135-136, :152-154) as one tape node, for the train step where
+    tail_in_consumer_applies(x, lstm=True): encoder.1's tail is formed by encoder.2's conv1 launch (wm_conv64_bf_tail) and encoder.2's
+    by the LSTM forward's helper waves (wm_lstm_fwd_tail), so neither block has a tail launch of its own.  The saved tensors are
+    ResBlockPairFn's eighteen and LSTMFn's six; backward = LSTMFn's, then ResBlockPairFn's."""
+
+    @staticmethod
+    def forward(ctx, x, *args):
+        p1, p2, (w_ih, w_hh, b_ih, b_hh) = args[:14], args[14:28], args[28:32]
+        want = wants_grad(ctx)
+        _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False)
+        mid, y2, cst = second[0], second[2], second[4]
+        mask = _tail_mask(mid, want)
+        h, lsaved = _lstm_fwd(None, w_ih, w_hh, b_ih, b_hh, want, tail=(mid, y2, cst[4], cst[5], mask))
+        if want:
+            ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
+            ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + lsaved))
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        sv = ctx.saved_tensors
+        _single_backward(ctx, "EncoderLSTMFn")
+        s1_, s2_ = sv[:9], sv[9:18]
+        lgrads = _lstm_bwd(sv[18:], ctx.gdst, dh)
+        dmid, grads2, fout = _resblock_bwd_fused(s2_, True, lgrads[0], fold=(s1_[3], s1_[2]))
+        dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout)
+        return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + lgrads[1:]
 
 
 # ------------------------------------------------------------------------------------------ embedding + convT

@@ -70,6 +70,13 @@ int wm_conv64_bf(const float* x, const float* x2, const void* wpb, const float* 
  * schedule 2 with T % 128 == 0 -- the ResBlock forward convolutions -- hipErrorInvalidValue otherwise.  Activations are split unscaled: the
  * representation floor is 2^-25 ABSOLUTE (f16 subnormal spacing / 2) on top of 2^-22 relative, i.e. fp32-grade for the O(1)
  * activations BatchNorm + ReLU produce. */
+/* conv1 of a training ResBlock whose input is the tail of the block in front of it, formed while the tile is staged instead of by a
+ * wm_bn_add_relu_mask launch of its own: out = relu(x + y2 * sc2 + sh2) and its sign bits (mask: wm_bn_add_relu_mask's layout, may be
+ * NULL) are written as side products, bit for bit what that launch writes; y and stats are bit for bit wm_conv64_bf(pro 0, epi 0,
+ * arith 1) on that out.  wpb_h from wm_pack_w64_h(mode 0); stats is required.  The pipelined f16 build only: T % 128 != 0 or
+ * schedule 0 is hipErrorInvalidValue, and nothing is written. */
+int wm_conv64_bf_tail(const float* x, const float* y2, const void* wpb_h, const float* sc2, const float* sh2, const float* bias,
+                      float* out, void* mask, float* y, float* stats, int B, int T, wm_stream_t stream);
 
 /* Inference ResBlock as ONE launch (py/main16.py:112-125 with both BatchNorm1d in eval mode):
  *   y = relu(x + (conv2(relu((conv1(x) + b1) * sc1 + sh1)) + b2) * sc2 + sh2)
@@ -218,6 +225,13 @@ int wm_lstm_fwd_fused(const float* x, const float* w_ih, const float* b_ih, cons
  * 32-step chunk on four helper waves that share its one barrier per step; 0 the projection inside the recurrence's own waves.
  * Bit-identical results. */
 int wm_set_lstm_fwd_wave_specialised(int on, wm_stream_t stream);
+/* wm_lstm_fwd_fused (always the wave-specialised build) on out = relu(xres + y2 * sc2 + sh2), the tail of the ResBlock in front of the
+ * LSTM: the helper waves form it while they stage each 32-step chunk and store `out` and its sign bits (mask: wm_bn_add_relu_mask's
+ * layout, may be NULL) bit for bit as that launch writes them; hout / gates / cst are bit for bit wm_lstm_fwd_fused on that out.
+ * T % 32 != 0 is hipErrorInvalidValue, and nothing is written: the caller keeps the two launches. */
+int wm_lstm_fwd_tail(const float* xres, const float* y2, const float* sc2, const float* sh2, float* out, void* mask, const float* w_ih,
+                     const float* b_ih, const float* b_hh, const float* w_hh, float* hout, float* gates, float* cst, int B, int T,
+                     wm_stream_t stream);
 int wm_lstm_bwd(float* gates, const float* cst, const float* dh_out, const float* w_hh, int B, int T, wm_stream_t stream);
 int wm_lstm_dx(const float* da, const float* w_ih, float* dx, int B, int T, wm_stream_t stream);
 /* arithmetic of wm_lstm_dx and wm_lstm_wgrad (process-wide): 1 bf16x6 split on the bf16 matrix cores (default,
