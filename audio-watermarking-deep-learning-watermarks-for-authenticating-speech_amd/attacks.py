@@ -20,8 +20,14 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
                is unmeasured
   TimeWarp     the desynchronising channel: playback at another speed (tempo and pitch together), sinusoidal wow / flutter and a cut at
                the front, through a Hann-windowed sinc interpolator whose phase is computed per output sample -- one wm_time_warp launch
-               (ops.TimeWarpFn), its backward the same launch with adjoint=True.  No pitch-preserving stretch; survival against real
-               players and tapes is unmeasured
+               (ops.TimeWarpFn), its backward the same launch with adjoint=True.  Survival against real players and tapes is
+               unmeasured
+  TimeStretch  the pitch-preserving change of tempo: waveform-similarity overlap-add (WSOLA), frames copied from near their nominal
+               place to evenly spaced places of the output and cross-faded -- one wm_wsola launch (ops.WsolaFn), its backward the
+               same launch as a gather with the chosen positions held constant.  A piecewise copy with cross-faded jumps, a
+               rectangular search, no transient detection: parity with any real editor's stretch is unmeasured
+  PitchShift   the change of pitch at constant tempo: TimeStretch by 1 / beta followed by wm_time_warp at speed beta, no kernel of
+               its own
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
   Splice       the EDITING attack, and the only module here with two inputs: spans of the watermarked signal are cut out and replaced by
                the clean signal, by silence, or by clean audio moved from elsewhere in the same row -- one wm_splice launch
@@ -58,7 +64,7 @@ FAMILIES = {
     "param": (0xFFFFFFFF, 0xFFFFFFFF),          # o0..o2: Distortion's gain, SNR and noise coin; o3: TransformCodec's SNR
     "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry
     "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
-    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase
+    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones
     **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
     **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
 }
@@ -597,8 +603,8 @@ class TimeWarp(_RowDraws):
     p(t) = speed * t + shift + flutter, through a Hann-windowed sinc interpolator of `zeros` zero crossings a side whose cutoff follows the
     speed, so a faster playback does not alias (wm_time_warp in include/wm_hip.h has the definition).  It is a speed change -- tempo and
     pitch move together, as on a turntable or with a wrong clock --, plus sinusoidal wow / flutter, plus a cut of shift_s seconds at the
-    front (negative: silence in front).  A pitch-preserving stretch (phase vocoder, WSOLA) and a pitch shift at constant tempo are NOT
-    built, and A WATERMARK'S SURVIVAL AGAINST REAL PLAYERS AND TAPES IS UNMEASURED.
+    front (negative: silence in front).  The pitch-preserving stretch is TimeStretch (WSOLA) and the pitch shift at constant tempo is
+    PitchShift; a phase vocoder is not built, and A WATERMARK'S SURVIVAL AGAINST REAL PLAYERS AND TAPES IS UNMEASURED.
     THE OUTPUT KEEPS THE INPUT'S LENGTH AND THE LABELS ARE NOT MOVED: where the read position leaves the row the output is silence, and that
     silence -- like every warped sample -- is still labelled as its clip is; a per-sample localisation label stays at its output index.
     speed in [0.5, 2], shift_s, flutter_hz in (0, sample_rate / 4], flutter_depth in [0, 0.25] (the relative peak deviation of the
@@ -647,6 +653,166 @@ class TimeWarp(_RowDraws):
     def extra_repr(self):
         return (f"speed={self.speed}, shift_s={self.shift_s}, flutter_hz={self.flutter_hz}, flutter_depth={self.flutter_depth}, "
                 f"zeros={self.zeros}, sample_rate={self.sample_rate}, seed={self.seed}")
+
+
+def row_stretch_rates(seed, draw, rows, rate):
+    """TimeStretch's float32 rate of rows `rows` (an int array of row0 + r): word o1 of the counter (0xFFFFFFFC, 0xFFFFFFFF, row, draw) --
+    TimeWarp's flutter phase is its word o0 -- onto the pair `rate` as fmaf(high - low, u, low) in float32"""
+    return _affine(rate, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[1]))
+
+
+def row_pitch_params(seed, draw, rows, semitones):
+    """PitchShift's (semitones, beta, rate) of rows `rows`, three float32 arrays: word o2 of the counter (0xFFFFFFFC, 0xFFFFFFFF, row,
+    draw) onto the pair `semitones` as fmaf(high - low, u, low) in float32; beta = float32(2^(st / 12)) and rate = float32(1 / beta), each
+    formed in float64 from the float32 value before it"""
+    st = _affine(semitones, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[2]))
+    beta = np.exp2(st.astype(np.float64) / 12.0).astype(np.float32)
+    return st, beta, (1.0 / beta.astype(np.float64)).astype(np.float32)
+
+
+def _wsola_rows_host(x2, rates, n_out, L, S):
+    """wm_wsola's modes 0 and 1 on a (rows, n) float32 CPU tensor in torch ops: (y, delta).  The search runs on the values alone (the
+    float32 scores summed in torch's order, the tie order of the definition); the synthesis is a gather at the chosen positions --
+    constants -- and w u + (1 - w) v in float64 rounded to float32 once (u where u = v, bit for bit), which autograd differentiates
+    with the weights w and 1 - w of the adjoint's definition.  Row by row."""
+    rows, n = x2.shape
+    hs = L // 2
+    K = ops.wsola_frames(n_out, L)
+    win = ops.wsola_window(L)
+    cand = torch.arange(-S, S + 1)
+    order = torch.argsort(torch.where(cand == 0, 0, torch.where(cand < 0, -2 * cand - 1, 2 * cand)))     # 0, -1, +1, -2, +2, ...
+    j = torch.arange(hs)
+    delta = torch.zeros((rows, K), dtype=torch.int32)
+    out = []
+    for r in range(rows):
+        rate = float(np.float32(rates[r]))
+        if not (0.25 <= rate <= 4.0):
+            out.append(torch.zeros(n_out, dtype=torch.float32))
+            continue
+        xd = x2[r].detach()
+        a = np.floor(rate * ((np.arange(K, dtype=np.float64) - 1.0) * hs) + 0.5).astype(np.int64)
+        p = np.zeros(K, dtype=np.int64)
+        p[0] = a[0]
+        for k in range(1, K):
+            q, c0 = int(p[k - 1]) + hs, int(a[k]) - S
+            T, C = _gather_ext(xd, q + torch.arange(L), n), _gather_ext(xd, c0 + torch.arange(L + 2 * S), n)
+            d = T[None, :] - C.unfold(0, L, 1)
+            score = (d * d).sum(dim=1)[order]
+            score = torch.where(torch.isnan(score), torch.full_like(score, float("inf")), score)
+            dk = int(cand[order[int(torch.argmin(score))]])                      # the first of the smallest; all NaN: candidate 0
+            delta[r, k] = dk
+            p[k] = a[k] + dk
+        pt = torch.from_numpy(p)
+        u = _gather_ext(x2[r], (pt[1:, None] + j[None, :]).reshape(-1), n)
+        v = _gather_ext(x2[r], (pt[:-1, None] + hs + j[None, :]).reshape(-1), n)
+        w = win.double().repeat(K - 1)                                             # 1 - w is exact in float64
+        out.append((w * u.double() + (1.0 - w) * v.double()).to(torch.float32)[:n_out])
+    return torch.stack(out), delta
+
+
+def _gather_ext(xr, idx, n):
+    """xr[idx] with zeros where idx leaves [0, n)"""
+    inside = (idx >= 0) & (idx < n)
+    return torch.where(inside, xr[idx.clamp(0, n - 1)], torch.zeros((), dtype=xr.dtype))
+
+
+class _Wsola(_RowDraws):
+    """What TimeStretch and PitchShift share: the frame and the search range"""
+
+    def __init__(self, frame, search, seed):
+        super().__init__(seed)
+        ops._wsola_dims(frame, search)
+        self.frame, self.search = frame, search
+        self.last_params = self.last_delta = None
+
+    def _stretch(self, x2, rates, n_out):
+        """(rows, n) -> (rows, n_out) at the float32 rates; keeps the offsets in last_delta (on x2's device)"""
+        if x2.is_cuda:
+            y, delta = ops.WsolaFn.apply(x2, torch.from_numpy(rates).to(x2.device), n_out, self.frame, self.search)
+        else:
+            y, delta = _wsola_rows_host(x2, rates, n_out, self.frame, self.search)
+        self.last_delta = delta
+        return y
+
+
+class TimeStretch(_Wsola):
+    """A pitch-preserving change of tempo on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,), by waveform-similarity
+    overlap-add (WSOLA; wm_wsola in include/wm_hip.h has the definition): frames of `frame` samples are copied from the input to places
+    frame / 2 apart in the output, each taken within `search` samples of its nominal place rate * t where it continues its predecessor
+    best, and cross-faded over half a frame.  The spectrum stays and the time axis moves: the attack a per-sample detector is least
+    prepared for.  A stretch is a PIECEWISE COPY WITH CROSS-FADED JUMPS: the search is rectangular, there is no transient detection,
+    PARITY WITH ANY REAL EDITOR'S STRETCH IS UNMEASURED, and STOI under it says nothing.
+    THE OUTPUT KEEPS THE INPUT'S LENGTH AND THE LABELS ARE NOT MOVED (TimeWarp's contract): at rate > 1 the input runs out and the rest is
+    silence, at rate < 1 the end of the input is not reached; every sample is still labelled as its clip is.
+    rate in [0.5, 2], input samples consumed per output sample (above 1 plays faster): a number fixes it, a pair draws one per row,
+    reproducible from (seed, draw, row0 + r) (row_stretch_rates).  Every forward uses the next `draw`; reset(draw) rewinds; `row0`
+    numbers the first row, so that a batch cut into pieces draws what the whole batch would.  `last_params`: the (rows,) float32 rates of
+    the last call (a CPU tensor); `last_delta`: its (rows, K) int32 offsets, where they were computed.  The chosen positions are constants
+    of the graph: the gradient is that of the linear gather.  At rate 1 the output is the input bit for bit.
+    CUDA tensors run wm_wsola, one launch each way (ops.WsolaFn); CPU tensors the same definition in torch ops, differentiable by autograd."""
+
+    def __init__(self, rate=(0.9, 1.1), frame=512, search=128, seed=0):
+        super().__init__(frame, search, seed)
+        self.rate = _pair(rate, "rate")
+        if not 0.5 <= self.rate[0] <= self.rate[1] <= 2.0:
+            raise ValueError(f"rate: expected values in [0.5, 2], got {rate!r}")
+
+    def forward(self, x, row0=0):
+        x, rows = self._rows(x, row0)
+        draw = self._next_draw()
+        rates = row_stretch_rates(self.seed, draw, row0 + np.arange(rows), self.rate)
+        self.last_params = torch.from_numpy(rates)
+        x2 = x.to(torch.float32).reshape(rows, -1)
+        return self._stretch(x2, rates, x2.shape[1]).reshape(x.shape)
+
+    def extra_repr(self):
+        return f"rate={self.rate}, frame={self.frame}, search={self.search}, seed={self.seed}"
+
+
+class PitchShift(_Wsola):
+    """A change of pitch at constant tempo on every row of x, (B, 1, T), (C, N) or (N,): a TimeStretch that makes the row longer by the
+    factor beta = 2^(semitones / 12), played back beta times as fast through TimeWarp's interpolator, so the duration is the input's and
+    every frequency is multiplied by beta.  No second kernel: wm_wsola at rate float32(1 / beta) to m = max(n, ceil(beta n)) samples (a
+    row's samples past its own m are silence), wm_time_warp on these with {a = beta, off = 0, d = 0, w = 0, phi = 0, c = min(1, 1 /
+    beta)}, the first n samples.  TimeStretch's limits hold -- a piecewise copy with cross-faded jumps, PARITY WITH ANY REAL EDITOR'S
+    PITCH SHIFT IS UNMEASURED -- and formants move with the pitch.  The output keeps the input's length and the labels are not moved.
+    semitones in [-12, 12]: a number fixes it, a pair draws one per row from (seed, draw, row0 + r) (row_pitch_params).  `last_params`: the
+    (rows, 3) float32 {semitones, beta, rate} of the last call (a CPU tensor); `last_delta`: the stretch's offsets.  seed, draw, reset and
+    row0 as in TimeStretch.  CUDA tensors run the two launches (ops.WsolaFn, ops.TimeWarpFn), CPU tensors the same definitions in torch
+    ops, differentiable by autograd."""
+
+    RES = TimeWarp.RES
+
+    def __init__(self, semitones=(-1, 1), frame=512, search=128, zeros=16, seed=0):
+        super().__init__(frame, search, seed)
+        self.semitones = _pair(semitones, "semitones")
+        if not -12.0 <= self.semitones[0] <= self.semitones[1] <= 12.0:
+            raise ValueError(f"semitones: expected values in [-12, 12], got {semitones!r}")
+        ops.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
+        self.zeros = zeros
+
+    def forward(self, x, row0=0):
+        x, rows = self._rows(x, row0)
+        draw = self._next_draw()
+        st, beta, rates = row_pitch_params(self.seed, draw, row0 + np.arange(rows), self.semitones)
+        self.last_params = torch.from_numpy(np.stack([st, beta, rates], axis=1))
+        x2 = x.to(torch.float32).reshape(rows, -1)
+        n = x2.shape[1]
+        m = np.maximum(n, np.ceil(beta.astype(np.float64) * n)).astype(np.int64)
+        z = self._stretch(x2, rates, int(m.max()))
+        past = torch.arange(z.shape[1])[None, :] >= torch.from_numpy(m)[:, None]
+        if bool(past.any()):
+            z = z.masked_fill(past.to(z.device), 0.0)                             # every row ends at its own m
+        b64 = beta.astype(np.float64)
+        params = torch.from_numpy(np.stack([b64, 0 * b64, 0 * b64, 0 * b64, 0 * b64, np.minimum(1.0, 1.0 / b64)], axis=1).astype(np.float32))
+        if x.is_cuda:
+            y = ops.TimeWarpFn.apply(z, params.to(x.device), ops._time_warp_table_on(self.zeros, self.RES, x.device), self.zeros, self.RES)
+        else:
+            y = _warp_rows_host(z, params, ops.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
+        return y[:, :n].reshape(x.shape)
+
+    def extra_repr(self):
+        return f"semitones={self.semitones}, frame={self.frame}, search={self.search}, zeros={self.zeros}, seed={self.seed}"
 
 
 SPLICE_KINDS = ("original", "silence", "moved")           # the `kind` of a span: 0, 1, 2

@@ -1967,6 +1967,109 @@ class TimeWarpFn(torch.autograd.Function):
         return time_warp(g.contiguous(), params, table, adjoint=True, zeros=ctx.dims[0], res=ctx.dims[1]), None, None, None, None
 
 
+# ---------------------------------------------------------------------------------------------- pitch-preserving time stretch
+# Waveform-similarity overlap-add (wm_wsola, csrc/wsola.hip): frames of the input copied to evenly spaced places of the output, each
+# taken near its nominal place where it continues the one before best.  Given the chosen positions the map is a linear gather, so the
+# backward pass is exact with the positions held constant.
+WSOLA_MAX_N = 2 ** 30
+
+
+def _wsola_dims(L, S):
+    _chk_int(L, "L", 64, 1024)
+    if L & (L - 1):
+        raise ValueError(f"L: expected a power of two, got {L}")
+    _chk_int(S, "S", 1, L // 2)
+
+
+_WSOLA_HOST = {}         # L -> the rising half window (a CPU tensor)
+_WSOLA_DEV = {}          # (L, device) -> the same on the device
+
+
+def wsola_window(L=512):
+    """The rising half of the frame's Hann window, an (L / 2,) fp32 CPU tensor (cached; do not write to it): 0.5 - 0.5 cos(pi j / Hs),
+    Hs = L / 2, computed in float64.  Entry 0 is exactly 0, so a frame that continues its predecessor hands the samples on bit for bit."""
+    _wsola_dims(L, 1)
+    if L not in _WSOLA_HOST:
+        import numpy as np
+        hs = L // 2
+        w = 0.5 - 0.5 * np.cos(np.pi * np.arange(hs, dtype=np.float64) / hs)
+        w[0] = 0.0
+        _WSOLA_HOST[L] = torch.from_numpy(w.astype(np.float32))
+    return _WSOLA_HOST[L]
+
+
+def _wsola_window_on(L, device):
+    key = (L, str(device))
+    if key not in _WSOLA_DEV:
+        _WSOLA_DEV[key] = wsola_window(L).to(device)
+    return _WSOLA_DEV[key]
+
+
+def wsola_frames(n_out, L=512):
+    """K, the frames of a row of n_out output samples: ceil(n_out / Hs) + 1"""
+    return -(-n_out // (L // 2)) + 1
+
+
+def wsola(x, rate, n_out=None, delta=None, adjoint=False, L=512, S=128):
+    """One launch of wm_wsola along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows; include/wm_hip.h has the
+    definition).  rate: (rows,) fp32 CUDA tensor, input samples consumed per output sample; a row whose rate is outside [1/4, 4] comes
+    back as zeros.  n_out: the length of the result's last axis, None for that of x.
+    delta=None: the search (mode 0); returns (y, delta), delta the (rows, K) int32 offsets of the chosen positions, K = wsola_frames(n_out, L).
+    delta given: synthesis from these offsets (mode 1), clamped to [-S, S]; returns (y, delta).
+    adjoint=True (delta is needed): x is the gradient of a result of x's length, and the transposed map of mode 1 comes back, dx with
+    n_out samples a row -- here n_out is the FORWARD call's input length."""
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    _wsola_dims(L, S)
+    n_res = _chk_int(n if n_out is None else n_out, "n_out", 1, WSOLA_MAX_N)
+    if n > WSOLA_MAX_N or rows * max(n, n_res) > 2 ** 46:
+        raise ValueError(f"rows = {rows}, n = {n}, n_out = {n_res}: a row may have 2^30 samples and a launch 2^46")
+    rate = _chk(rate, "rate", 1)
+    if rate.shape[0] != rows:
+        raise ValueError(f"rate: expected ({rows},), one per row, got shape {tuple(rate.shape)}")
+    if adjoint and delta is None:
+        raise ValueError("delta: the adjoint needs the positions of the forward call")
+    K = wsola_frames(n if adjoint else n_res, L)
+    if delta is not None:
+        delta = _chk(delta, "delta", 2, torch.int32)
+        if tuple(delta.shape) != (rows, K):
+            raise ValueError(f"delta: expected ({rows}, {K}), one offset per frame, got shape {tuple(delta.shape)}")
+    for t, name in ((rate, "rate"), (delta, "delta")):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{name}: expected a tensor on {x.device}, got one on {t.device}")
+    mode = 2 if adjoint else (0 if delta is None else 1)
+    if delta is None:
+        delta = torch.empty((rows, K), dtype=torch.int32, device=x.device)
+    y = _f32(*x.shape[:-1], n_res, device=x.device)
+    n_in, n_o = (n_res, n) if adjoint else (n, n_res)
+    lib.wm_wsola(_p(x), _p(rate), _p(_wsola_window_on(L, x.device)), _p(y), _p(delta), rows, n_in, n_o, L, S, mode, _stream())
+    return y if adjoint else (y, delta)
+
+
+class WsolaFn(torch.autograd.Function):
+    """y, delta = wsola(x, rate, n_out) on the tape.  Saved for the backward: delta and rate alone; dx is the mode-2 launch on them.  The
+    positions are CONSTANTS of the graph: the map is differentiated as the linear gather it is once they are chosen, and no gradient
+    flows to the rate (it is drawn, not trained)."""
+
+    @staticmethod
+    def forward(ctx, x, rate, n_out, L, S):
+        y, delta = wsola(x, rate, n_out, L=L, S=S)
+        ctx.save_for_backward(delta, rate)
+        ctx.dims = (x.shape, L, S)
+        ctx.mark_non_differentiable(delta)
+        return y, delta
+
+    @staticmethod
+    def backward(ctx, g, _):
+        delta, rate = ctx.saved_tensors
+        shape, L, S = ctx.dims
+        dx = wsola(g.contiguous(), rate, shape[-1], delta, adjoint=True, L=L, S=S)
+        return dx.reshape(shape), None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- STOI
 # Short-time objective intelligibility of rows at 10 kHz (wm_stoi, csrc/stoi.hip; the definition is in include/wm_hip.h): the quality
 # column of the evaluation side.  Nothing is differentiated: a measure, not a loss.

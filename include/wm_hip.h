@@ -561,6 +561,46 @@ int wm_rir_synth(const float* params, float* h, long long rows, int K, float sam
 int wm_time_warp(const float* x, const float* params, const float* tab, float* y, long long rows, long long n, int zeros, int res,
                  int adjoint, wm_stream_t stream);
 
+/* ---- pitch-preserving time stretch: waveform-similarity overlap-add (WSOLA), and its adjoint at constant positions -------------------
+ * the other desynchronising channel (the reference ships no code for it): the time axis is stretched by `rate` while the spectrum stays,
+ * by copying frames of the input to evenly spaced places of the output, each frame taken near its nominal place where it continues the
+ * one before best, cross-faded over half a frame.  Verhelst and Roelands, "An overlap-add technique based on waveform similarity (WSOLA)
+ * for high quality time-scale modification of speech", ICASSP 1993.  A pitch shift at constant tempo is this followed by wm_time_warp.
+ * x (rows, n_in) fp32, y (rows, n_out) fp32, rows >= 1, 1 <= n_in, n_out <= 2^30, rows * max(n_in, n_out) <= 2^46, every row on its own;
+ * xe is x extended by zeros outside [0, n_in).  L (the frame) a power of two in 64..1024, Hs = L / 2 (the hop), 1 <= S <= Hs (the search
+ * range).  win: Hs fp32 values from the caller, the rising half window (the package's: float32(0.5 - 0.5 cos(pi j / Hs)) formed in fp64,
+ * entry 0 exactly 0).  rate (rows,) fp32 on the device: input samples consumed per output sample, above 1 plays faster.
+ * A ROW WHOSE RATE IS NOT FINITE OR LIES OUTSIDE [1/4, 4] GETS ALL ZEROS in y and (mode 0) in delta.  Whatever rate or delta hold, every
+ * access stays inside the buffers and a row costs a bounded number of steps.
+ *   Frames k = 0 .. K - 1, K = ceil(n_out / Hs) + 1; frame k covers the outputs [o_k, o_k + L), o_k = (k - 1) Hs.
+ *   a_k = floor(r o_k + 0.5)   the nominal position: r the fp32 rate as fp64, one fp64 product, one fp64 sum
+ *   p_k = a_k + D_k            the chosen position; delta (rows, K) int32 holds D_k; D_0 = 0 (entry 0 is written as 0 and never read)
+ *   Search (mode 0, k >= 1, sequential in k):  q = p_(k-1) + Hs is the natural continuation.  For D in [-S, S]
+ *       d(D) = sum_{j < L} (xe[q + j] - xe[a_k + D + j])^2
+ *     each term one fp32 subtraction and one fmaf.  The order: with P the largest power of two <= min(4096 / S, L / 8) (integer division),
+ *     the terms j in [i L / P, (i + 1) L / P) form one fmaf chain from +0 in rising j, and the P chains are added in fp32 in rising i.  It
+ *     depends on (L, S) and j alone -- never on the grid, the row count or the other rows.  D_k is the candidate with the smallest fp32
+ *     score; ties go to the first candidate in the order 0, -1, +1, -2, +2, ...; a NaN score never wins, and if every score is NaN D_k = 0.
+ *     A squared difference and not a cross-correlation: at rate 1 the continuation scores exactly 0, so the map is the identity without a
+ *     normalisation, and a sum without cancellation has a purely relative fp32 error.
+ *   Synthesis: output t = m Hs + j, 0 <= j < Hs:   u = xe[p_(m+1) + j],  v = xe[p_m + Hs + j],  y[t] = fmaf(win[j], u - v, v)
+ *     (u - v one fp32 subtraction).  Linear in x; where p_(m+1) = p_m + Hs it equals x bit for bit.
+ *   mode 0: search, write delta, synthesise.
+ *   mode 1: synthesise from the caller's delta, every entry clamped to [-S, S] on load.
+ *   mode 2: the adjoint of mode 1.  x is the gradient g (rows, n_out), y is dx (rows, n_in); ge is g extended by zeros;
+ *       dx[s] = sum over the frames k with 0 <= s - p_k < L  of  W[s - p_k] ge[o_k + s - p_k]
+ *       W[i] = win[i] for i < Hs and 1 - win[i - Hs] (one fp32 subtraction) for i >= Hs
+ *     ONE fp32 fmaf chain from +0 in rising k, a gather: a_k is monotone and |D| <= S, so the frames of a sample are one bracket of k found
+ *     by arithmetic, of at most (L + 2 S) / (Hs / 4) + 3 members.  A term whose output index lies outside [0, n_out) is left out.
+ *   A sample's bits depend on its row's data, its row's rate (and delta), win, the dimensions and its index only; two launches give
+ *   identical bits.
+ * One launch (csrc/wsola.hip: mode 0 one workgroup per row with the frame's template and candidates in LDS, modes 1 and 2 one lane per
+ * sample), stateless, enqueue-only.  No atomics, no scratch.  Every pointer may start at any multiple of 4 bytes.  IN PLACE IS REFUSED.
+ * hipErrorInvalidValue before any launch: rows, n_in, n_out, L or S out of range, mode outside 0..2, a null or misaligned pointer, y
+ * overlapping x, rate, win or delta, and in mode 0 delta overlapping x, rate or win. */
+int wm_wsola(const float* x, const float* rate, const float* win, float* y, int* delta, long long rows, long long n_in, long long n_out,
+             int L, int S, int mode, wm_stream_t stream);
+
 /* ---- STOI: short-time objective intelligibility (Taal, Hendriks, Heusdens, Jensen 2011) of a processed signal against its reference ----
  * replaces the per-segment pystoi.stoi(clean, wm, 16000, extended=False) loop of evaluate_unseen_file (py/main14.py:1099-1203,
  * py/main16.py:2012-2153) at the rate the measure is defined at.  x (the reference) and y (the processed signal) are (rows, n) fp32 AT
