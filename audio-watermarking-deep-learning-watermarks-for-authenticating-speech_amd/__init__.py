@@ -6,7 +6,7 @@ from .losses import (MultiScaleMelLoss, TFLoudnessLoss, clamp_peak, detection_lo
 from .step import LOSS_WEIGHTS, forward_losses, train_step, eval_forward
 from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
-from .attacks import (Convolved, Distortion, Lowpass, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
+from .attacks import (Convolved, Distortion, Lowpass, LpcCodec, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
                       evaluate_localization, evaluate_robustness, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
 from . import attacks
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
@@ -24,7 +24,7 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "fir_lowpass", "clamp_peak", "limit_rms", "postprocess", "high_freq_penalty", "detection_losses", "l1_to_zero",
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
-           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness",
+           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "LpcCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness",
            "Splice", "evaluate_localization", "row_splice_spans", "splice_rows_host", "pack_labels", "unpack_labels", "detection_losses_masked",
            "locate_watermark",
            "stoi", "quality",

@@ -12,6 +12,10 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
   TransformCodec   a STAND-IN for lossy compression: lapped MDCT, per-band quantiser at a per-row SNR, bandwidth cut, synthesis -- one
                wm_mdct_codec launch (ops.MdctCodecFn), its backward the same launch with the quantiser off.  The signal path MP3 / AAC
                share, not an encoder: parity with a real one is unmeasured
+  LpcCodec     a STAND-IN for a predictive speech codec (ADPCM / CELP / AMR-WB / SILK are all linear-predictive): per-frame LPC, an
+               open-loop quantiser on the prediction residual at a per-row SNR, all-pole synthesis that shapes the noise like the
+               speech envelope -- one wm_lpc_codec launch (ops.LpcCodecFn); its "dead_zone" backward is the adjoint launch.  No LSP
+               interpolation, no pitch predictor, no noise feedback, no entropy coder: parity with a real codec is unmeasured
   Convolved    a long convolutive channel: every row convolved with a given impulse response, or with one drawn per row from a bank of
                measured ones -- one wm_fir_rows launch (ops.FirRowsFn), its backward the same launch with reverse=True.  echo_ir
                makes the two-tap response of a plain echo
@@ -62,7 +66,7 @@ FAMILIES = {
     "sample": (None, 0),                        # Distortion's noise
     "rir_tap": (None, 0xFFFFFFFE),              # the taps of Reverb's synthetic responses
     "param": (0xFFFFFFFF, 0xFFFFFFFF),          # o0..o2: Distortion's gain, SNR and noise coin; o3: TransformCodec's SNR
-    "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry
+    "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry; o3: LpcCodec's SNR
     "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
     "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones
     **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
@@ -394,6 +398,113 @@ class TransformCodec(_RowDraws):
     def extra_repr(self):
         return (f"snr_db={self.snr_db}, bandwidth_hz={self.bandwidth_hz}, hop={self.hop}, band={self.band}, "
                 f"sample_rate={self.sample_rate}, seed={self.seed}, grad={self.grad!r}")
+
+
+def row_lpc_snr_db(seed, draw, rows, snr_db):
+    """LpcCodec's per-row quality for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the "param2"
+    counter -- Reverb and Convolved use its first three, so no two attacks share a number -- mapped onto the pair snr_db as
+    fmaf(high - low, u, low)"""
+    return _affine(snr_db, _unit(_words("param2", seed, draw, rows)[3]))
+
+
+def _lpc_rows_host(x2, snr, L, p, sample_rate, floor_step):
+    """wm_lpc_codec's forward on a (rows, n) float32 array in float32 numpy: (y, coefficients (rows, F, p), int16 codes (rows, n)).  The
+    definition of include/wm_hip.h with numpy's own summation order inside the autocorrelation and the frame energy."""
+    f32 = np.float32
+    rows, n = x2.shape
+    F = ops.lpc_frames(n, L)
+    lag, expand = (t.numpy() for t in ops.lpc_tables(p, sample_rate))
+    j = np.arange(2 * L, dtype=np.float64)
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * (j + 0.5) / (2 * L))).astype(f32)
+    xp = np.zeros((rows, L // 2 + F * L + L), dtype=f32)
+    xp[:, L // 2:L // 2 + n] = x2
+    s = np.stack([xp[:, f * L:f * L + 2 * L] for f in range(F)], axis=1) * w                       # (rows, F, 2L)
+    Rc = np.stack([(s[..., :2 * L - k] * s[..., k:]).sum(axis=-1, dtype=f32) for k in range(p + 1)], axis=-1) * lag
+    a = np.zeros((rows, F, p + 1), dtype=f32)                                                      # a[..., k] is tap k; entry 0 unused
+    E = Rc[..., 0].copy()
+    go = E > 0
+    E = np.where(go, E, f32(1))
+    for i in range(1, p + 1):
+        acc = Rc[..., i].copy()
+        for m in range(1, i):
+            acc = acc + a[..., m] * Rc[..., i - m]
+        k = -acc / E
+        go = go & (np.abs(k) < 1)
+        k = np.where(go, k, f32(0)).astype(f32)
+        a[..., 1:i] = a[..., 1:i] + k[..., None] * a[..., i - 1:0:-1]
+        a[..., i] = k
+        E = (E * (f32(1) - k * k)).astype(f32)
+    a = (a[..., 1:] * expand).astype(f32)
+    at = np.repeat(a, L, axis=1)[:, :n]                                                            # (rows, n, p): the set of sample t
+    hist = np.zeros((rows, n + p), dtype=f32)
+    hist[:, p:] = x2
+    e = x2.copy()
+    for k in range(1, p + 1):
+        e = e + at[:, :, k - 1] * hist[:, p - k:p - k + n]
+    ep = np.zeros((rows, F * L), dtype=f32)
+    ep[:, :n] = e
+    cnt = np.minimum(L, n - L * np.arange(F)).astype(f32)
+    P = (ep.reshape(rows, F, L) ** 2).sum(axis=2, dtype=f32) / cnt
+    snr = np.nan_to_num(np.asarray(snr, dtype=f32), nan=0.0).clip(0, 60)
+    g = (10.0 ** (-snr.astype(np.float64) / 20.0)).astype(f32).reshape(rows, 1)
+    step = np.repeat(np.maximum(np.sqrt(f32(12) * P) * g, f32(floor_step)), L, axis=1)[:, :n]
+    q = np.rint(e / step)
+    eq = (q * step).astype(f32)
+    y = np.zeros((rows, n + p), dtype=f32)                                                         # y[:, p + t]; the first p are the silence before
+    ar = at[:, :, ::-1]
+    for t in range(n):
+        y[:, p + t] = eq[:, t] - (ar[:, t] * y[:, t:t + p]).sum(axis=1, dtype=f32)
+    return np.ascontiguousarray(y[:, p:]), a, q.astype(np.int16)
+
+
+class LpcCodec(_RowDraws):
+    """A STAND-IN for a predictive speech codec on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the signal path ADPCM, CELP,
+    AMR-WB and SILK share -- per frame of `frame` samples an order-`order` linear predictor from the windowed autocorrelation, the
+    prediction residual quantised by a uniform quantiser whose step sits snr_db below the residual's own level (never finer than the
+    16-bit grid), all-pole synthesis, which shapes the white quantisation noise like the frame's spectral envelope (wm_lpc_codec in
+    include/wm_hip.h has the definition).  It is not a speech codec -- open-loop quantisation, no LSP interpolation, no pitch
+    predictor, no noise feedback, no entropy coder -- and PARITY WITH A REAL CODEC IS UNMEASURED, as is narrowband use behind
+    Resampled(8000).  The output stays time-aligned with the input, so STOI applies.
+    snr_db: a number fixes the quality, a pair draws one value per row, reproducible from (seed, draw, row0 + r) (row_lpc_snr_db); 0..60.
+    Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
+    pieces draws what the whole batch would.  `last_snr_db`: the per-row values of the last call (a CPU tensor).
+    grad "straight_through": the gradient is dy itself (with the quantiser passed through, synthesis inverts the residual filter) |
+    "dead_zone": residual samples coded 0 pass none -- the adjoint launch at the forward's coefficients (ops.LpcCodecFn; the dependence of
+    the coefficients and steps on x is not differentiated).  CUDA tensors run the kernel; CPU tensors a float32 numpy restatement of the
+    definition (forward only)."""
+
+    def __init__(self, snr_db=(10, 30), frame=320, order=16, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
+        if grad not in ops.LPC_GRAD_MODES:
+            raise ValueError(f"grad must be one of {ops.LPC_GRAD_MODES}, got {grad!r}")
+        super().__init__(seed)
+        self.snr_db = _pair(snr_db, "snr_db")
+        if not 0.0 <= self.snr_db[0] <= self.snr_db[1] <= 60.0:
+            raise ValueError(f"snr_db: expected values in [0, 60], got {snr_db!r}")
+        ops._lpc_dims(frame, order)
+        ops.lpc_tables(order, sample_rate)                                        # a bad sample rate fails here
+        self.frame, self.order, self.sample_rate = frame, order, sample_rate
+        self.floor_step = ops.LPC_FLOOR_STEP
+        self.grad = grad
+        self.last_snr_db = None
+
+    def forward(self, x, row0=0):
+        x, rows = self._rows(x, row0)
+        snr = torch.from_numpy(row_lpc_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
+        self._next_draw()
+        if x.is_cuda:
+            y = ops.LpcCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.frame, self.order, self.sample_rate, self.floor_step,
+                                     self.grad)
+        else:
+            x32 = x.detach().to(torch.float32)
+            y2 = _lpc_rows_host(x32.reshape(-1, x.shape[-1]).numpy(), snr.numpy(), self.frame, self.order, self.sample_rate,
+                                self.floor_step)[0]
+            y = torch.from_numpy(y2).reshape(x.shape)
+        self.last_snr_db = snr
+        return y
+
+    def extra_repr(self):
+        return (f"snr_db={self.snr_db}, frame={self.frame}, order={self.order}, sample_rate={self.sample_rate}, seed={self.seed}, "
+                f"grad={self.grad!r}")
 
 
 def row_reverb_params(seed, draw, rows, rt60, drr_db):

@@ -2070,6 +2070,139 @@ class WsolaFn(torch.autograd.Function):
         return dx.reshape(shape), None, None, None, None
 
 
+# ---------------------------------------------------------------------------------------------- predictive speech-codec stand-in
+# Per-frame linear prediction -> open-loop quantiser on the residual -> all-pole synthesis (wm_lpc_codec, csrc/lpc_codec.hip): the signal
+# path ADPCM / CELP / AMR-WB / SILK share, as a step of the graph.  A stand-in, not a speech codec: no LSP interpolation, no pitch
+# predictor, no noise feedback, no entropy coder; parity with a real one is unmeasured.
+LPC_FRAMES = (160, 320, 640)
+LPC_MAX_ORDER = 16
+LPC_GRAD_MODES = ("straight_through", "dead_zone")
+LPC_FLOOR_STEP = 2.0 ** -15
+
+_LPC_HOST = {}           # (order, sample_rate) -> (lag, expand), CPU tensors
+_LPC_DEV = {}            # (order, sample_rate, device) -> the same on the device
+
+
+def _lpc_dims(frame, order):
+    if isinstance(frame, bool) or not isinstance(frame, int) or frame not in LPC_FRAMES:
+        raise ValueError(f"frame must be one of {LPC_FRAMES}, got {frame!r}")
+    _chk_int(order, "order", 2, LPC_MAX_ORDER)
+
+
+def lpc_tables(order=16, sample_rate=16000):
+    """(lag, expand), fp32 CPU tensors (cached; do not write to them), evaluated in float64 and rounded once.  lag (order + 1,): the lag
+    window the autocorrelation is multiplied by, exp(-0.5 (2 pi 60 k / sample_rate)^2) -- a 60 Hz Gaussian -- with lag[0] = 1 + 1e-4, the
+    white-noise correction.  expand (order,): 0.994^k for k = 1 .. order, the bandwidth expansion of the coefficients."""
+    _chk_int(order, "order", 2, LPC_MAX_ORDER)
+    _chk_positive(sample_rate, "sample_rate")
+    key = (order, float(sample_rate))
+    if key not in _LPC_HOST:
+        import numpy as np
+        k = np.arange(order + 1, dtype=np.float64)
+        lag = np.exp(-0.5 * (2.0 * np.pi * 60.0 * k / float(sample_rate)) ** 2)
+        lag[0] = 1.0 + 1e-4
+        expand = 0.994 ** k[1:]
+        _LPC_HOST[key] = (torch.from_numpy(lag.astype(np.float32)), torch.from_numpy(expand.astype(np.float32)))
+    return _LPC_HOST[key]
+
+
+def _lpc_tables_on(order, sample_rate, device):
+    key = (order, float(sample_rate), str(device))
+    if key not in _LPC_DEV:
+        _LPC_DEV[key] = tuple(t.to(device) for t in lpc_tables(order, sample_rate))
+    return _LPC_DEV[key]
+
+
+def lpc_frames(n, frame=320):
+    """F = ceil(n / frame): the frames of a row of n samples"""
+    return -(-int(n) // int(frame))
+
+
+def lpc_codec(x, snr_db, *, frame=320, order=16, sample_rate=16000, floor_step=None, quantise=True, coeffs=None, coeffs_out=False,
+              codes_out=False, mask_in=None, adjoint=False):
+    """One launch of wm_lpc_codec along the last axis of a contiguous fp32 CUDA tensor (all leading axes are rows; include/wm_hip.h has the
+    definition): per frame of `frame` samples an order-`order` predictor from the windowed autocorrelation (lpc_tables(order,
+    sample_rate) are its lag window and bandwidth expansion), the residual quantised at the per-row SNR snr_db (a (rows,) fp32 CUDA
+    tensor, values in [0, 60]; ignored with quantise=False, where None is allowed) but never finer than floor_step (None: 2^-15), and
+    all-pole synthesis.  coeffs: a (rows, lpc_frames(n, frame), order) fp32 tensor that replaces the analysis.  mask_in: a (rows, n) int16
+    tensor; the residual is set to 0 where it holds 0.  coeffs_out / codes_out: also return the coefficients the launch used / the int16
+    codes (rows, n); the result is then the tuple (y[, coeffs][, codes]).  adjoint=True (needs coeffs, quantise=False): x is a gradient
+    and the transpose of the linear map synthesis . mask . residual filter at these coefficients comes back.  A stand-in for a speech
+    codec; parity with a real one is unmeasured."""
+    x = _chk(x, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x: needs at least one row of at least one sample, got shape {tuple(x.shape)}")
+    _lpc_dims(frame, order)
+    if floor_step is None:
+        floor_step = LPC_FLOOR_STEP
+    _chk_positive(floor_step, "floor_step")
+    if codes_out and not quantise:
+        raise ValueError("codes_out needs quantise=True: the linear map has no codes")
+    if adjoint and (coeffs is None or quantise or coeffs_out or codes_out):
+        raise ValueError("adjoint: needs coeffs and quantise=False, and has neither coeffs_out nor codes_out")
+    n = x.shape[-1]
+    rows = x.numel() // n
+    if n > 2 ** 34 or rows * n > 2 ** 46:
+        raise ValueError(f"rows = {rows}, n = {n}: a row may have 2^34 samples and a launch 2^46")
+    F = lpc_frames(n, frame)
+    if snr_db is None and not quantise:
+        snr_db = torch.zeros(rows, dtype=torch.float32, device=x.device)
+    snr_db = _chk(snr_db, "snr_db", 1)
+    if snr_db.shape[0] != rows:
+        raise ValueError(f"snr_db: expected ({rows},), one per row, got shape {tuple(snr_db.shape)}")
+    if coeffs is not None:
+        coeffs = _chk(coeffs, "coeffs")
+        if coeffs.numel() != rows * F * order or coeffs.shape[-1] != order:
+            raise ValueError(f"coeffs: expected {rows} x {F} x {order} fp32 values, got shape {tuple(coeffs.shape)}")
+    if mask_in is not None:
+        mask_in = _chk(mask_in, "mask_in", None, torch.int16)
+        if mask_in.numel() != rows * n:
+            raise ValueError(f"mask_in: expected {rows} x {n} int16 values, got shape {tuple(mask_in.shape)}")
+    for t, name in ((snr_db, "snr_db"), (coeffs, "coeffs"), (mask_in, "mask_in")):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{name}: expected a tensor on {x.device}, got one on {t.device}")
+    lag, expand = _lpc_tables_on(order, sample_rate, x.device)
+    y = torch.empty_like(x)
+    used = torch.empty(rows, F, order, dtype=torch.float32, device=x.device) if coeffs_out else None
+    codes = torch.empty(rows, n, dtype=torch.int16, device=x.device) if codes_out else None
+    lib.wm_lpc_codec(_p(x), _p(y), _p(coeffs), _p(used), _p(codes), _p(mask_in), _p(snr_db), _p(lag), _p(expand), rows, n, frame, order,
+                     float(floor_step), int(bool(quantise)), int(bool(adjoint)), _stream())
+    out = (y,) + ((used,) if coeffs_out else ()) + ((codes,) if codes_out else ())
+    return out if len(out) > 1 else y
+
+
+class LpcCodecFn(torch.autograd.Function):
+    """y = synthesis(Q(residual(x))) per row (lpc_codec) on the tape.  The coefficients and the steps follow x, and that dependence is
+    NOT differentiated: they are constants of the backward pass, as the MDCT codec's steps and WSOLA's positions are.
+      grad "straight_through": with the quantiser taken for the identity, synthesis inverts the residual filter exactly, so the map is the
+                               identity and the gradient IS dy: no launch, nothing saved;
+      grad "dead_zone":        residual samples whose forward code was 0 pass no gradient: the forward's coefficients and int16 codes
+                               are saved, and dx is the adjoint launch at those coefficients with the codes as mask_in."""
+
+    @staticmethod
+    def forward(ctx, x, snr_db, frame, order, sample_rate, floor_step, grad):
+        if grad not in LPC_GRAD_MODES:
+            raise ValueError(f"grad must be one of {LPC_GRAD_MODES}, got {grad!r}")
+        ctx.cfg = (frame, order, sample_rate, floor_step)
+        ctx.dead = grad == "dead_zone" and ctx.needs_input_grad[0]
+        if ctx.dead:
+            y, coeffs, codes = lpc_codec(x, snr_db, frame=frame, order=order, sample_rate=sample_rate, floor_step=floor_step,
+                                         coeffs_out=True, codes_out=True)
+            ctx.save_for_backward(coeffs, codes)
+            return y
+        return lpc_codec(x, snr_db, frame=frame, order=order, sample_rate=sample_rate, floor_step=floor_step)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.dead:
+            return g, None, None, None, None, None, None
+        frame, order, sample_rate, floor_step = ctx.cfg
+        coeffs, codes = ctx.saved_tensors
+        dx = lpc_codec(g.contiguous(), None, frame=frame, order=order, sample_rate=sample_rate, floor_step=floor_step, quantise=False,
+                       coeffs=coeffs, mask_in=codes, adjoint=True)
+        return dx.reshape(g.shape), None, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- STOI
 # Short-time objective intelligibility of rows at 10 kHz (wm_stoi, csrc/stoi.hip; the definition is in include/wm_hip.h): the quality
 # column of the evaluation side.  Nothing is differentiated: a measure, not a loss.

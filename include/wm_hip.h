@@ -601,6 +601,59 @@ int wm_time_warp(const float* x, const float* params, const float* tab, float* y
 int wm_wsola(const float* x, const float* rate, const float* win, float* y, int* delta, long long rows, long long n_in, long long n_out,
              int L, int S, int mode, wm_stream_t stream);
 
+/* ---- predictive speech-codec stand-in: per-frame LPC, open-loop residual quantiser, all-pole synthesis -- and the adjoint -------------
+ * the channel a speech recording most likely crosses (ADPCM, CELP, AMR-WB, SILK are all linear-predictive) as a step of the graph; the
+ * reference ships no code for it.  White quantisation noise goes on the prediction residual and the synthesis filter shapes it like the
+ * frame's spectral envelope.  It is a STAND-IN, not a speech codec: open-loop quantisation, no LSP interpolation, no pitch predictor, no
+ * noise feedback, no entropy coder; parity with any real codec is unmeasured.
+ * x, y (rows, n) fp32, rows >= 1, 1 <= n <= 2^34, rows * n <= 2^46, every row on its own; xe is the row extended by zeros.  Frame length
+ * L in {160, 320, 640}, order p in 2..16, F = ceil(n / L) frames, frame f owns the samples fL .. (f+1)L - 1, f(t) = floor(t / L).
+ *   Analysis (coeffs_in null).  w[j] = 0.5 - 0.5 cos(2 pi (j + 1/2) / (2L)), j < 2L, evaluated in fp64 and rounded once to fp32.
+ *       s[j]  = w[j] * xe[fL - L/2 + j]                      one fp32 product
+ *       R[k]  = sum_{j < 2L - k} s[j] s[j + k], k <= p        64 fmaf chains from +0, chain l over j = l, l + 64, ... rising; the chains are
+ *                                                            added by the xor butterfly 32, 16, .. 1 (v += partner: the same bits in every lane)
+ *       Rc[k] = R[k] * lag[k]                                lag (p + 1,) fp32 on the device, from the caller (the package's: lag[0] = 1 + 1e-4,
+ *                                                            the white-noise correction, lag[k] = exp(-0.5 (2 pi 60 k / sample_rate)^2), in fp64,
+ *                                                            rounded once)
+ *     Levinson-Durbin in fp32 on Rc, a all 0 at the start.  !(Rc[0] > 0): the frame's coefficients stay 0.  E = Rc[0]; at step i = 1 .. p:
+ *       acc = Rc[i], then acc = fmaf(a_j, Rc[i - j], acc) for j = 1 .. i - 1 rising;  k_i = -acc / E (one IEEE division).
+ *       !(|k_i| < 1): the recursion stops, a_j = 0 for j >= i.  Otherwise a_j <- fmaf(k_i, a_(i-j), a_j) for j < i (from the old values),
+ *       a_i = k_i,  E <- E * fmaf(-k_i, k_i, 1).
+ *     Then a[k] <- a[k] * expand[k - 1], expand (p,) fp32 on the device from the caller (the package's: 0.994^k, k = 1 .. p, in fp64).
+ *     coeffs_in ((rows, F, p) fp32, optional) replaces all of this; coeffs_out (optional, same shape) receives exactly the fp32
+ *     coefficients the launch used.  lag and expand are read only without coeffs_in.
+ *   Residual.   e[t] = x[t] + sum_{k = 1..p} a_f(t)[k] xe[t - k]     one fmaf chain from x[t] in rising k; the predictor runs on the INPUT
+ *   Quantiser (quantise != 0), per frame:
+ *       P = (sum of e^2 over the frame's samples inside the row) / their number; the sum: 64 fmaf chains from +0, chain l over the frame's
+ *           samples l, l + 64, ... rising, the same butterfly
+ *       step = max(sqrt(12 P) * g, floor_step),  g = 10^(-snr_db_r / 20) in fp64 rounded once;  snr_db (rows,) fp32 on the device, clamped to
+ *           0..60, NaN to 0;  floor_step > 0 (the package's: 2^-15)
+ *       q = rint(e / step), ties to even (one IEEE division)        eq = q * step
+ *       |q| <= sqrt(L / 12) * 10^3 < 32767: codes_out (optional, (rows, n) int16) receives q.   quantise == 0: eq = e (snr_db is not read).
+ *     Where mask_in (optional, (rows, n) int16) holds 0, eq[t] = 0.
+ *   Synthesis.  y[t] = eq[t] - sum_{k = 1..16} a_f(t)[k] y[t - k],  y[< 0] = 0, a[k] = 0 for k > p: one fmaf chain from eq[t] in FALLING k,
+ *       fmaf(-a[k], y[t - k], acc), so the newest output enters last.  (The zero terms change no bit of a finite result.)
+ *     With the quantiser off and no mask y = x up to rounding: synthesis inverts the residual filter.
+ *   adjoint != 0 (needs coeffs_in; quantise == 0, no coeffs_out, no codes_out): x is the gradient g, y is dx, the transpose of the linear
+ *     map y = S M A x at these coefficients (A the residual filter, M the mask, S synthesis), the coefficient taken at the ROW index of each
+ *     matrix -- the frame of the sample the term comes FROM.  For t falling from n - 1:
+ *       u[t]  = g[t] - sum_{k = 1..16} a_f(t+k)[k] u[t + k]          one fmaf chain from g[t] in FALLING k, as the synthesis
+ *       v[t]  = mask[t] * u[t]                                      (mask 1 or 0; all 1 without mask_in)
+ *       dx[t] = v[t] + sum_{k = 1..p} a_f(t+k)[k] v[t + k]           one fmaf chain from v[t] in rising k
+ *     terms with t + k >= n are left out (they are exact zeros).
+ *   The order of every sum depends on (L, p) and the index alone.  A sample's bits depend on its row's data, the tables and the scalars
+ *   only -- never on the grid or on the other rows of the launch; two launches give identical bits.
+ * One launch (csrc/lpc_codec.hip: one workgroup per row; producer waves analyse and quantise a chunk of frames ahead into an LDS ring,
+ * one wave runs the recursion, the producers write the chunk behind it out), stateless, enqueue-only.  No atomics, no scratch.  The fp32
+ * arrays may start at any multiple of 4 bytes, the int16 arrays of 2.  IN PLACE IS REFUSED: no output may overlap an input or another
+ * output.
+ * hipErrorInvalidValue before any launch: rows or n out of range, L or p outside the sets above, a null x or y, a misaligned pointer, no
+ * coeffs_in and a null lag or expand, quantise with a null snr_db or a non-finite or non-positive floor_step, codes_out without
+ * quantise, adjoint without coeffs_in or with quantise, coeffs_out or codes_out, overlapping buffers. */
+int wm_lpc_codec(const float* x, float* y, const float* coeffs_in, float* coeffs_out, void* codes_out, const void* mask_in,
+                 const float* snr_db, const float* lag, const float* expand, long long rows, long long n, int L, int p, float floor_step,
+                 int quantise, int adjoint, wm_stream_t stream);
+
 /* ---- STOI: short-time objective intelligibility (Taal, Hendriks, Heusdens, Jensen 2011) of a processed signal against its reference ----
  * replaces the per-segment pystoi.stoi(clean, wm, 16000, extended=False) loop of evaluate_unseen_file (py/main14.py:1099-1203,
  * py/main16.py:2012-2153) at the rate the measure is defined at.  x (the reference) and y (the processed signal) are (rows, n) fp32 AT
