@@ -17,6 +17,9 @@
 //                        pre-activation gradients da[b,t,256].
 //   4. wm_lstm_dx / wm_lstm_wgrad   everything that is NOT sequential leaves the recurrence:
 //                        dx = da W_ih, dW_ih = da^T x, dW_hh = da^T h_{t-1}, db = sum da are MFMA GEMMs.
+//   5. wm_lstm_bwd_wgrad / wm_lstm_bwd_wgrad_dx   ... and comes back beside it: four helper waves per workgroup form the
+//                        weight gradients, and two of them dx, on the matrix cores the recurrence leaves idle, from an
+//                        LDS image of da (lstm_bwd_ws_kernel); with dx inside, da never reaches memory.
 #include "wm_common.hpp"
 #include <type_traits>
 using namespace wm;
@@ -807,10 +810,27 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(float* __restrict__ gates
 // per step (s_barrier counts every wave of the workgroup) with a 1/32 slice of a chunk's work in between, so they can never run
 // behind; the recurrence keeps issue priority (s_setprio 3).  Per-clip slab: [256 n'][128 z] + [256] bias sums (the recurrence lanes
 // add their own da), reduced by lstm_wgrad_reduce_kernel.  T % 32 == 0.
+//
+// DX = true: the input gradient dx[c][t] = sum_n' W_ih[gate_row(n')][c] da[t][n'] is formed here as well, and da is NOT written to
+// `gates` (it keeps the saved activations): the [n'][step] image is the only copy of da there ever is.  Helper hw < 2 owns the
+// channel half mt = hw of a chunk = one 32 x 32 tile, lstm_dx_bf_kernel's product bit for bit -- the same A fragment (row = channel
+// mt*32 + l31, k = 16 ks + 8 half + j) and B fragment (column = step, the same k), the same split3_pair pieces, mfma_bf16x6's product
+// order, one accumulator chain from zero over ks = 0..15 ascending (an MFMA output column depends on its own B column only, so a 32-step
+// chunk in place of a 64-step tile changes nothing).  The B fragment is gathered from the image with eight ds_read_b32, one per n', and
+// split once per k-step; its six products issue one slot later (dx_slot).
+// W_ih's pieces (192 registers per tile if resident) live in memory, built by the helper's own lanes in the prologue and only ever read
+// back by the lane that wrote them: pieces 0 and 1 in LDS (64 KiB beside the 74 KiB the kernel has already), piece 2 -- one product in
+// six -- in the first 16 KiB of the helper's own quarter of the clip's `partial` slab, which is not written until the helper's
+// accumulators go out at the very end; it stays in L2 and is fetched three and four slots ahead.
+// LDS banks (64 x 4 B): a B-fragment read has lane l31 at float (n' * 36 + l31): 32 consecutive banks per half-wave, and the other half
+// is 8 columns = 288 floats = 32 banks further on -- conflict-free.  The W_ih image is [ks][piece][lane] x 16 B, read and written as
+// lane-consecutive b128: the canonical conflict-free pattern.
+template <bool DX>
 __global__ __launch_bounds__(512) void lstm_bwd_ws_kernel(float* __restrict__ gates, const float* __restrict__ cst,
                                                           const float* __restrict__ dh_out, const float* __restrict__ w_hh,
                                                           const float* __restrict__ x, const float* __restrict__ hseq,
-                                                          float* __restrict__ partial, int T) {
+                                                          float* __restrict__ partial, const float* __restrict__ w_ih,
+                                                          float* __restrict__ dx, int T) {
     constexpr int CT = 32, PT = 36;                 // chunk length, fp32 pitch of one gate column's chunk (16-byte multiple)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     float* daT = reinterpret_cast<float*>(smem_raw);                      // [2][256][PT]
@@ -865,7 +885,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_ws_kernel(float* __restrict__ ga
                 const float da = (is3 ? dht : dct) * M;
                 dc = dct * gf;
                 dav[j] = da;
-                buf_store(sgb, da, vgb, (unsigned)t * 1024u);
+                if constexpr (!DX) buf_store(sgb, da, vgb, (unsigned)t * 1024u);
                 float Dd[4];
                 rows_replicate(da, Dd);
                 const float psum = dot64_rowbcast(Dd, wt);
@@ -953,9 +973,90 @@ __global__ __launch_bounds__(512) void lstm_bwd_ws_kernel(float* __restrict__ ga
             acc[z][rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[rt][PA[j]], Bp[PB[j]], acc[z][rt][ct], 0, 0, 0);
         }
     };
+    // ---- DX: the chunk's dx tile on helpers 0 and 1 (hw is wave-uniform; no barrier inside, so the barrier count stays T + 1)
+    bf16x8* const wl = reinterpret_cast<bf16x8*>(smem_raw + (2 * 256 * PT + 2 * 64 * 4) * sizeof(float)) + hw * (16 * 2 * 64) + lane;
+    // piece 2: [ks][lane] x 16 B at the head of the helper's own quarter of the slab; dx rows of the tile: scalar row and chunk offsets
+    const wm_srd_t swg = make_srd(out + hw * (64 * 128), (size_t)16 * 64 * 16);
+    const wm_srd_t sdx = make_srd(DX ? dx + ((size_t)b * 64 + hw * 32) * T : nullptr, (size_t)32 * T * sizeof(float));
+    const unsigned vdx = (unsigned)(4 * half * T + l31) * 4u;
+    bf16x8 Bd[3], A2[2];
+    f32x16 dacc;
+    if constexpr (DX) {
+        if (hw < 2) {
+#pragma unroll 2
+            for (int ks = 0; ks < 16; ++ks) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = w_ih[gate_row(16 * ks + 8 * half + j) * 64 + hw * 32 + l31];
+                bf16x8 P[3];
+                split8(v, P);
+                wl[(2 * ks) * 64] = P[0];
+                wl[(2 * ks + 1) * 64] = P[1];
+                buf_store4(swg, __builtin_bit_cast(f32x4, P[2]), (unsigned)lane * 16u, (unsigned)ks * 1024u);
+            }
+        }
+    }
+    auto load_a2 = [&](int ks) { return __builtin_bit_cast(bf16x8, buf_load4(swg, (unsigned)lane * 16u, (unsigned)ks * 1024u)); };
+    auto dx_gather = [&](int chunk, int ks) {      // the B fragment of k-step ks: this lane's step, eight consecutive n', split once
+        const float* src = daT + ((chunk & 1) * 256 + 16 * ks + 8 * half) * PT + l31;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = src[j * PT];
+        split8(v, Bd);
+    };
+    auto dx_mul = [&](int ks, const bf16x8& a2) {   // pieces 0 and 1 read right before their products
+        const bf16x8 Ap[3] = {wl[(2 * ks) * 64], wl[(2 * ks + 1) * 64], a2};
+        dacc = mfma_bf16x6(Ap, Bd, dacc);
+    };
+    // Four slots = two k-steps (2g, 2g + 1), dealt around the weight gradients' own pattern (slot k = 0: their splits, no MFMA; k = 1..3:
+    // four MFMAs each, no VALU): k = 1 gather + split, k = 2 six products + gather + split, k = 3 six products.  The piece-2 fragments of
+    // the NEXT four slots are fetched at k = 3, i.e. before the weight gradients' raw loads of the following k = 0 slot: the memory counter
+    // retires in order, and a fetch issued behind those loads (x and h come from HBM) would make its consumer wait for them.
+    auto dx_slot = [&](int chunk, int sl) {
+        if (hw >= 2) return;
+        const int g = sl >> 2, k = sl & 3;
+        if (sl == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
+        }
+        if (k == 1) dx_gather(chunk, 2 * g);
+        if (k == 2) {
+            dx_mul(2 * g, A2[0]);
+            dx_gather(chunk, 2 * g + 1);
+        }
+        if (k == 3) {
+            dx_mul(2 * g + 1, A2[1]);
+            A2[0] = load_a2((2 * g + 2) & 15);     // (the last slot of a chunk fetches k-steps 0 and 1 for the next one)
+            A2[1] = load_a2((2 * g + 3) & 15);
+            if (sl == CT - 1) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) buf_store(sdx, dacc[r], vdx, (unsigned)(mfma_row(r, 0) * T + chunk * CT) * 4u);
+            }
+        }
+    };
+    if constexpr (DX) {
+        if (hw < 2) {
+            A2[0] = load_a2(0);
+            A2[1] = load_a2(1);
+        }
+    }
     const int nch = T / CT;
     load_raw(nch - 1, 0);
     __syncthreads();                                 // the recurrence's start-up barrier
+    if constexpr (DX) {
+        // the same T barriers as below with the idle first chunk peeled off: a per-slot `if (work)` leaves paths that skip one slot's
+        // loads and run the next slot's, and the wait counts the compiler derives for them are needlessly strict
+#pragma unroll 1
+        for (int sl = 0; sl < CT; ++sl) __syncthreads();
+        for (int c = nch - 2; c >= 0; --c) {
+#pragma unroll
+            for (int sl = 0; sl < CT; ++sl) {
+                slot(c + 1, sl);
+                dx_slot(c + 1, sl);
+                __syncthreads();
+            }
+        }
+    } else
     for (int c = nch - 1; c >= 0; --c) {             // the recurrence walks chunk c; chunk c + 1 is complete
         const bool work = c + 1 < nch;
 #pragma unroll
@@ -965,7 +1066,12 @@ __global__ __launch_bounds__(512) void lstm_bwd_ws_kernel(float* __restrict__ ga
         }
     }
 #pragma unroll
-    for (int sl = 0; sl < CT; ++sl) slot(0, sl);     // chunk 0, after the recurrence's last step
+    for (int sl = 0; sl < CT; ++sl) {                // chunk 0, after the recurrence's last step
+        slot(0, sl);
+        if constexpr (DX) dx_slot(0, sl);
+    }
+    // the accumulators below overwrite the piece-2 image: every read of it has returned first
+    if constexpr (DX) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int z = 0; z < 2; ++z)
 #pragma unroll
@@ -1665,8 +1771,9 @@ int wm_lstm_bwd_wgrad(float* gates, const float* cst, const float* dh_out, const
     if (B <= 0 || (T & 31) || T < 64) return (int)hipErrorInvalidValue;
     constexpr size_t lds = (size_t)(2 * 256 * 36 + 2 * 64 * 4) * sizeof(float);
     static wm::DevOnce done;
-    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_bwd_ws_kernel), lds, done)) return rc;
-    hipLaunchKernelGGL(lstm_bwd_ws_kernel, dim3(B), dim3(512), lds, stream, gates, cst, dh_out, w_hh, x, h, partial, T);
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_bwd_ws_kernel<false>), lds, done)) return rc;
+    hipLaunchKernelGGL(lstm_bwd_ws_kernel<false>, dim3(B), dim3(512), lds, stream, gates, cst, dh_out, w_hh, x, h, partial,
+                       (const float*)nullptr, (float*)nullptr, T);
     WM_CHECK_LAUNCH();
     hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3(kWgradSlab / 64), dim3(512), 0, stream, (const float*)partial, B,
                        dw_ih, dw_hh, db_ih, db_hh, accumulate);
@@ -1691,6 +1798,32 @@ int wm_lstm_dx(const float* da, const float* w_ih, float* dx, int B, int T, hipS
     static wm::DevOnce done;
     if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_dx_kernel), lds, done)) return rc;
     hipLaunchKernelGGL(lstm_dx_kernel, dim3(ntiles < kNumCU ? ntiles : kNumCU), dim3(256), lds, stream, da, w_ih, dx, B, T);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// wm_lstm_bwd_wgrad + wm_lstm_dx in one launch: helpers 0 and 1 also form dx from the LDS image of da (lstm_bwd_ws_kernel<true>), bit
+// for bit wm_lstm_dx's bf16x6 result; da is never written, gates keeps the saved activations.  partial must be 16-byte aligned (each
+// clip's slab holds W_ih's third piece, 2 x 16 KiB, until the slab's own values replace it).  Under wm_set_lstm_dx_bf16x6(0) there
+// is no such kernel: a const-cast of gates and the two launches (gates then holds da, as after wm_lstm_bwd_wgrad).
+int wm_lstm_bwd_wgrad_dx(const float* gates, const float* cst, const float* dh_out, const float* w_hh, const float* w_ih,
+                         const float* x, const float* h, float* partial, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh,
+                         float* dx, int B, int T, int accumulate, hipStream_t stream) {
+    if (B <= 0 || (T & 31) || T < 64 || !dx || !w_ih || (reinterpret_cast<uintptr_t>(partial) & 15)) return (int)hipErrorInvalidValue;
+    if (!g_lstm_dx_bf) {
+        if (int rc = wm_lstm_bwd_wgrad(const_cast<float*>(gates), cst, dh_out, w_hh, x, h, partial, dw_ih, dw_hh, db_ih, db_hh, B, T,
+                                       accumulate, stream))
+            return rc;
+        return wm_lstm_dx(gates, w_ih, dx, B, T, stream);
+    }
+    constexpr size_t lds = (size_t)(2 * 256 * 36 + 2 * 64 * 4) * sizeof(float) + (size_t)2 * 16 * 2 * 64 * 16;
+    static wm::DevOnce done;
+    if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(lstm_bwd_ws_kernel<true>), lds, done)) return rc;
+    hipLaunchKernelGGL(lstm_bwd_ws_kernel<true>, dim3(B), dim3(512), lds, stream, const_cast<float*>(gates), cst, dh_out, w_hh, x, h,
+                       partial, w_ih, dx, T);
+    WM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3(kWgradSlab / 64), dim3(512), 0, stream, (const float*)partial, B,
+                       dw_ih, dw_hh, db_ih, db_hh, accumulate);
     WM_CHECK_LAUNCH();
     return 0;
 }

@@ -370,6 +370,23 @@ def set_tail_in_consumer(on: bool):
     _TAILC["on"] = bool(on)
 
 
+# The train step's EncoderLSTMFn forms the LSTM input gradient inside the wave-specialised BPTT launch (wm_lstm_bwd_wgrad_dx): da is
+# neither written to memory nor read back by wm_lstm_dx.  WM_LSTM_DX_IN_BWD=0/1 sets the default ("1" = on, else off).  Kept outside
+# SWITCHES like _TAILC; plain LSTMFn always runs wm_lstm_bwd_wgrad + wm_lstm_dx.
+def read_lstm_dx_in_bwd(environ) -> bool:
+    """what the switch starts with under `environ` (pure, as read_switches)"""
+    return environ.get("WM_LSTM_DX_IN_BWD", "1") == "1"
+
+
+_LSTM_DX = {"in_bwd": read_lstm_dx_in_bwd(os.environ)}
+
+
+def set_lstm_dx_in_bwd(on: bool):
+    """1 (default): EncoderLSTMFn's backward is one wm_lstm_bwd_wgrad_dx launch where _lstm_bwd's conditions hold (wave-specialised
+    BPTT, T % 32 == 0, T >= 64, no side-stream weight gradients); 0: wm_lstm_bwd_wgrad + wm_lstm_dx.  Bit-identical either way."""
+    _LSTM_DX["in_bwd"] = bool(on)
+
+
 def _tail_in_consumer_launches(x, lstm: bool = False) -> bool:
     """the switch and what the two launches need: the f16 pipelined forward (the tail prologue exists in that build only, so
     T % 128 == 0); lstm=True adds the wave-specialised fused LSTM forward.  What a tape node asks inside its forward, where autograd
@@ -942,8 +959,10 @@ def _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, need_grad, tail=None):
     return h, ((x, h, gates, cst, w_ih, w_hh) if need_grad else None)
 
 
-def _lstm_bwd(saved, gdst, dh):
-    """LSTMFn's backward on _lstm_fwd's saved tensors: (dx, dw_ih, dw_hh, db_ih, db_hh); gdst = the four destinations of _gdst"""
+def _lstm_bwd(saved, gdst, dh, dx_inside=False):
+    """LSTMFn's backward on _lstm_fwd's saved tensors: (dx, dw_ih, dw_hh, db_ih, db_hh); gdst = the four destinations of _gdst.
+    dx_inside (EncoderLSTMFn, set_lstm_dx_in_bwd): dx comes out of the wave-specialised BPTT launch itself, unless the side-stream
+    option is on.  (The library's own fp32 choice, wm_set_lstm_dx_bf16x6(0), is not visible here: the entry point honours it.)"""
     x, h, gates, cst, w_ih, w_hh = saved
     dh = dh.contiguous()
     B, _, T = x.shape
@@ -953,6 +972,10 @@ def _lstm_bwd(saved, gdst, dh):
     dst, acc, launch = _wgrad_dst(gdst, dev, w_ih.shape, w_hh.shape, (256,), (256,))     # dwi, dwh, dbi, dbh
     if _LSTM["bwd_ws"] and not _LSTM["bwd_fused"] and T % 32 == 0 and T >= 64:
         part = _f32(B * (256 * 128 + 256), device=dev)       # (this launch accumulates into the flat store from the main stream)
+        if dx_inside and not _ASYNC["on"]:
+            lib.wm_lstm_bwd_wgrad_dx(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(w_ih), _p(x), _p(h), _p(part), *map(_p, dst), _p(dx),
+                                     B, T, int(acc), st)
+            return (dx,) + ((None,) * 4 if acc else dst)
         lib.wm_lstm_bwd_wgrad(_p(gates), _p(cst), _p(dh), _p(w_hh), _p(x), _p(h), _p(part), *map(_p, dst), B, T, int(acc), st)
         lib.wm_lstm_dx(_p(gates), _p(w_ih), _p(dx), B, T, st)
         return (dx,) + ((None,) * 4 if acc else dst)
@@ -993,7 +1016,7 @@ class EncoderLSTMFn(GradAwareFunction):
         sv = ctx.saved_tensors
         _single_backward(ctx, "EncoderLSTMFn")
         s1_, s2_ = sv[:9], sv[9:18]
-        lgrads = _lstm_bwd(sv[18:], ctx.gdst, dh)
+        lgrads = _lstm_bwd(sv[18:], ctx.gdst, dh, dx_inside=_LSTM_DX["in_bwd"])
         dmid, grads2, fout = _resblock_bwd_fused(s2_, True, lgrads[0], fold=(s1_[3], s1_[2]))
         dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout)
         return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + lgrads[1:]

@@ -251,6 +251,14 @@ int wm_lstm_wgrad(const float* da, const float* x, const float* h, float* partia
 int wm_lstm_bwd_wgrad(float* gates, const float* cst, const float* dh_out, const float* w_hh, const float* x, const float* h,
                       float* partial, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int B, int T, int accumulate,
                       wm_stream_t stream);
+/* wm_lstm_bwd_wgrad + wm_lstm_dx in one launch: two of the helper waves also form dx = W_ih^T da from the LDS image of the finished
+ * chunk, bit for bit wm_lstm_dx's bf16x6 result.  da is never written: gates is read only and keeps the saved activations.  Same
+ * conditions as wm_lstm_bwd_wgrad (B > 0, T % 32 == 0, T >= 64); a NULL dx or w_ih, or a partial that is not 16-byte aligned (each
+ * clip's slab carries a packed piece of W_ih until its own values replace it), is hipErrorInvalidValue as well, and nothing is
+ * written.  After wm_set_lstm_dx_bf16x6(0) the entry point runs the two launches instead, and gates then holds da. */
+int wm_lstm_bwd_wgrad_dx(const float* gates, const float* cst, const float* dh_out, const float* w_hh, const float* w_ih,
+                         const float* x, const float* h, float* partial, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh,
+                         float* dx, int B, int T, int accumulate, wm_stream_t stream);
 
 /* ---- nn.Embedding(2**bits,64) lookup :158 and its dense gradient ------------------------------------------- */
 int wm_embed_gather(const float* table, const long long* message, float* vec, int B, int nrows, int* err, wm_stream_t stream);
