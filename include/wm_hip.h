@@ -212,7 +212,10 @@ int wm_headN_bwd_bce(const float* logits, const long long* message, const float*
                      const float* w, float* dx, float* partial, float* dw, float* db, int B, int R, int T, int NO, int accumulate,
                      wm_stream_t stream);
 
-/* ---- nn.LSTM(64,64,batch_first=True) :138,:152-154 ---------------------------------------------------------- */
+/* ---- nn.LSTM(64,64,batch_first=True) :138,:152-154 ----------------------------------------------------------
+ * csrc/lstm_fwd.hip:  wm_lstm_xproj, wm_lstm_fwd, wm_lstm_fwd_fused, wm_lstm_fwd_tail, wm_set_lstm_fwd_wave_specialised
+ * csrc/lstm_bwd.hip:  wm_lstm_bwd, wm_lstm_bwd_fused, wm_lstm_bwd_wgrad, wm_lstm_bwd_wgrad_dx
+ * csrc/lstm_grad.hip: wm_lstm_dx, wm_lstm_wgrad, wm_set_lstm_dx_bf16x6 */
 int wm_lstm_xproj(const float* x, const float* w_ih, const float* b_ih, const float* b_hh, float* xp, int B, int T,
                   wm_stream_t stream);
 int wm_lstm_fwd(const float* xp, const float* w_hh, float* hout, float* gates, float* cst, int B, int T, wm_stream_t stream);

@@ -1,5 +1,7 @@
-"""diagnostic: cycle budget of ONE step of the 16 000-step recurrences (needs the -DWM_STAMP build of csrc/lstm.hip:
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWM_STAMP -shared csrc/lstm.hip -o libwm_lstm_stamp.so).  The stamps serialise
+"""diagnostic: cycle budget of ONE step of the 16 000-step recurrences (needs the -DWM_STAMP build of the two stamped LSTM units,
+csrc/lstm_fwd.hip and csrc/lstm_bwd.hip, and of csrc/lstm_grad.hip, which lstm_bwd.hip's two-launch fallback links against:
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWM_STAMP -shared csrc/lstm_fwd.hip csrc/lstm_bwd.hip csrc/lstm_grad.hip -o libwm_lstm_stamp.so).
+Each stamped unit has its own copy of the stamp pointer and its own setter; both are set below.  The stamps serialise
 LDS traffic at each point (s_waitcnt lgkmcnt(0)), so the stamped step is longer than the real one; the shares are what to read."""
 import ctypes, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,7 +17,8 @@ b_ih, b_hh = (torch.randn(256, generator=g) * 0.1).to(dev), (torch.randn(256, ge
 h = torch.empty(B, 64, T, device=dev); gates = torch.empty(B, T, 256, device=dev); cst = torch.empty(B, T, 64, device=dev)
 dh = (torch.randn(B, 64, T, generator=g) * 0.1).to(dev)
 buf = torch.zeros(B * 4 * 6, dtype=torch.int64, device=dev)
-S.wm_debug_set_lstm_stamp_buffer(vp(buf.data_ptr()))
+S.wm_debug_set_lstm_stamp_buffer(vp(buf.data_ptr()))          # lstm_fwd.hip
+S.wm_debug_set_lstm_stamp_buffer_bwd(vp(buf.data_ptr()))      # lstm_bwd.hip
 
 
 def timed(fn):
