@@ -27,7 +27,7 @@
 //   lstm_bwd.hip    steps 3 and 5: the three BPTT recurrences (plain, dx inside, wave-specialised with the weight gradients and dx)
 //   lstm_grad.hip   step 4: the dx and weight-gradient GEMMs, fp32 and bf16x6
 // An entry point lives with every kernel it can launch; lstm_wgrad_reduce_kernel (below) is compiled once per including unit, so
-// nothing needs relocatable device code.  The per-step-launch LSTM of the main14b_2 variant (lstm_seq_*, in gconv.hip) shares nothing with these.
+// nothing needs relocatable device code.  The per-step-launch LSTM of the main14b_2 variant (lstm_seq_*, in lstm_seq.hip) shares nothing with these.
 #pragma once
 #include "wm_common.hpp"
 #include <type_traits>

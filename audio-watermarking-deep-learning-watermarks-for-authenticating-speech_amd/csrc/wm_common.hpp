@@ -8,6 +8,9 @@
 #define WM_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 #define WM_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+// the one entry point called across units without a family header: bn.hip defines it against this declaration, wm_gconv_pack_h (gconv_fwd.hip) calls it
+extern "C" int wm_gscale_absmax(const float* x, long long n, float* scratch, float log2_target, float* gscale, hipStream_t stream);
+
 namespace wm {
 
 // hipFuncSetAttribute (the > 64 KB dynamic-LDS opt-in) is a PER-DEVICE setting: remember it per device ordinal, so one

@@ -1,6 +1,7 @@
 """Drop-in mirrors of the reference's deep-residual variant, py/main14b_2.py:83-224 (BASELINE config 5):
 ResidualBlock / Generator / Detector with the reference's constructor arguments, sub-module names and state_dict
-layout.  Forward AND backward run in csrc/gconv.hip:
+layout.  Forward AND backward run in csrc/gconv_fwd.hip, gconv_wgrad.hip,
+gconv_small.hip and lstm_seq.hip:
 
   * every Conv1d / Linear / ConvTranspose1d (and each of their data gradients) is one launch of the generic
     matrix-core convolution `wm_gconv` with a re-indexed weight image (re-indexing = pure data movement, done here

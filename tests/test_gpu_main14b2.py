@@ -79,8 +79,10 @@ def test_gconvT_matches_conv_transpose1d(M, cin, cout, st, L):
                                                      (128, 256, 1, 5, 0, 2001), (16, 8, 3, 1, 1, 4000)])
 @pytest.mark.parametrize("gscale", [1.0, 1e-8, 3e3])
 def test_gconv_f16_split_is_fp32_grade(M, cin, cout, k, stride, pad, L, gscale):
-    """the generic convolution on the f16 two-piece split (wm_gconv_h: three products per product; weight image scaled from max |w| by
-    wm_gconv_pack_h, a gradient input from max |g| by wm_gscale_absmax) beside the native fp32-MFMA build (wm_gconv) on the same inputs,
+    """the generic convolution on the f16 two-piece split (wm_gconv_h: three products per product; weight image at the fixed scale 2^8,
+    as the package packs every image (wm_gconv_pack_h_conv, wm_gconv_pack_h with scratch = NULL; the max-|w| scale of wm_gconv_pack_h is
+    test_gpu_main14b2_kernels.py::test_gconv_pack_h_scaled_route's), a gradient input scaled from max |g| by wm_gscale_absmax) beside
+    the native fp32-MFMA build (wm_gconv) on the same inputs,
     both against fp64: forward with ELU, and the data gradient for upstream gradient magnitudes 1e-8 ... 3e3 (strided layers take the
     transposed / pixel-shuffled route).  Error relative to the result's max below 1e-6 and within 3x of the fp32 build's + 2e-7."""
     dev = torch.device("cuda:0")

@@ -44,7 +44,7 @@ GW_RA, GW_RB = 16, 24
 
 
 def gw_plan(NB, Ca, Cb, La, K):
-    """mirror of gw_plan (csrc/gconv.hip) -- only to report / assert which paths the cases take; its split-K depth is checked
+    """mirror of gw_plan (csrc/gconv_wgrad.hip) -- only to report / assert which paths the cases take; its split-K depth is checked
     against the library's own workspace size (wm_gwgrad_plan), so a drifted mirror fails loudly instead of mis-reporting"""
     WA = 2 if Ca > 32 else 1
     TA, R, NJ = 32 * WA, 4 // WA, Cb * K
@@ -616,6 +616,45 @@ def test_activation_scale_is_per_clip(M):
         y_all = M._gconv(x.to(DEV), w.to(DEV), b.to(DEV), 1, 1, act=1)
         for i in (0, 2):
             assert torch.equal(y_all[i:i + 1], M._gconv(x[i:i + 1].to(DEV), w.to(DEV), b.to(DEV), 1, 1, act=1)), i
+
+
+# ------------------------------------------------------------------------------------------ weight image scaled from max |w|
+def _pack_h(M, w, Cin, K, Mtot, scaled, fill):
+    """wm_gconv_pack_h's image of w [Cin * K][Mtot] -> (the 2 * Cin * K * Mtot f16 words, the two trailing floats).  scaled: with a real
+    scratch (ws from max |w| by wm_gscale_absmax, a call across translation units), else scratch = NULL (the fixed ws = 2^8).  The
+    buffer starts as `fill`, so a word a route leaves unwritten differs between two routes given different fills."""
+    n = Cin * K * Mtot
+    wd, scratch = w.contiguous().to(DEV), torch.zeros(1024, device=DEV)
+    wph = torch.full((2 * n + 4,), fill, dtype=torch.int16, device=DEV)
+    M.lib.wm_gconv_pack_h(wd.data_ptr(), wph.data_ptr(), scratch.data_ptr() if scaled else None, Cin, K, Mtot,
+                          torch.cuda.current_stream().cuda_stream)
+    return wph[:2 * n].cpu(), wph[2 * n:].view(torch.float32).cpu()
+
+
+@pytest.mark.parametrize("Cin,K,Mtot", [(16, 3, 5), (32, 1, 4), (16, 7, 17)])
+@pytest.mark.parametrize("e", [-3, 0, 5])
+def test_gconv_pack_h_scaled_route(M, Cin, K, Mtot, e):
+    """the scratch != NULL branch of wm_gconv_pack_h, which no caller in the package takes (main14b_2 passes NULL): max |w| = 0.75 * 2^e
+    lies 0.415 binades under 2^e, so ws = exp2(floor(10 - log2(max))) = 2^(10 - e) whatever the last bit of log2f.  The image must be
+    bit for bit the fixed-scale route's (the one test_gconv_f16_split_is_fp32_grade holds to fp64) for w * (ws / 2^8): that rescale is
+    a power of two, so both routes split the same v = w * ws."""
+    g = torch.Generator().manual_seed(1000 * Cin + 10 * K + Mtot + (e + 3))
+    w = (torch.rand(Cin * K, Mtot, generator=g) * 2 - 1) * (0.7 * 2.0 ** e)
+    w[(Cin * K) // 2, Mtot // 2] = 0.75 * 2.0 ** e
+    ws = 2.0 ** (10 - e)
+    img, tail = _pack_h(M, w, Cin, K, Mtot, True, 0x5555)
+    assert tail.tolist() == [ws, 1.0 / ws], (tail.tolist(), ws)
+    ref, ref_tail = _pack_h(M, w * (ws / 256.0), Cin, K, Mtot, False, 0x2AAA)
+    assert ref_tail.tolist() == [256.0, 1.0 / 256.0]
+    assert torch.equal(img, ref), f"{int((img != ref).sum())} of {img.numel()} f16 words differ"
+
+
+def test_gconv_pack_h_scaled_route_all_zero(M):
+    """max |w| = 0: the scale is 1 and the image all zero"""
+    Cin, K, Mtot = 16, 3, 5
+    img, tail = _pack_h(M, torch.zeros(Cin * K, Mtot), Cin, K, Mtot, True, 0x5555)
+    assert tail.tolist() == [1.0, 1.0]
+    assert not img.any()
 
 
 # ------------------------------------------------------------------------------------------ gradient scale under in-place accumulation
