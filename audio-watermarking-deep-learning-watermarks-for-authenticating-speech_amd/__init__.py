@@ -15,6 +15,8 @@ from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_wa
                         save_audio_float)
 from .quality import stoi
 from . import quality
+from .detection import (auc, calibrate_threshold, detection_report, eer, evaluate_detection, operating_point, roc_curve, tpr_at_fpr)
+from . import detection
 from . import checkpoint
 from . import main14b_2
 from . import distributed
@@ -28,4 +30,5 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "Splice", "evaluate_localization", "row_splice_spans", "splice_rows_host", "pack_labels", "unpack_labels", "detection_losses_masked",
            "locate_watermark",
            "stoi", "quality",
+           "detection", "evaluate_detection", "detection_report", "roc_curve", "auc", "eer", "tpr_at_fpr", "calibrate_threshold", "operating_point",
            "lib", "LIB_PATH"]

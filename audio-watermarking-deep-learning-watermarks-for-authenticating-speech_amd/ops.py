@@ -6,6 +6,7 @@ block of the reference graph (py/main16.py:112-186, :53-81, :192-217).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import math
 import os
@@ -2416,3 +2417,69 @@ def loc_counts(logits, lab, threshold=0.5, want_pred=False):
     pred = torch.empty(R, label_words(T), dtype=torch.int32, device=logits.device) if want_pred else None
     lib.wm_loc_score(_p(logits), _p(lab), thr, _p(counts), _p(pred), R, T, NO, lab_rows, _stream())
     return (counts, pred) if want_pred else counts
+
+
+# ---------------------------------------------------------------------------------------------- per-clip detection scores
+# wm_clip_scores (csrc/clip_scores.hip; the definition is in include/wm_hip.h): everything an operating-point report needs of the
+# Detector's logits, in one pass.  Nothing is differentiated: a measure, not a loss.
+CLIP_SCORES_MAX_T = 2 ** 24
+ClipScores = collections.namedtuple("ClipScores", "prob llr votes words biterr")
+
+
+def clip_scores_plan(R, T, NO):
+    """bytes of scratch one wm_clip_scores launch on (R, T, NO) logits needs"""
+    import ctypes
+    for v, name in ((R, "R"), (T, "T"), (NO, "NO")):
+        _chk_int(v, name, 1, math.inf, "a positive int")
+    if T > CLIP_SCORES_MAX_T or NO > 64 or R * T * NO > 2 ** 46:
+        raise ValueError(f"R = {R}, T = {T}, NO = {NO}: a clip may have 2^24 samples and 64 channels, a launch 2^46 elements")
+    need = ctypes.c_longlong(0)
+    lib.wm_clip_scores_plan(R, T, NO, ctypes.addressof(need), None)
+    return need.value
+
+
+def clip_scores(logits, message=None, threshold=0.5):
+    """Per-clip scores of the Detector's logits (R, T, NO) float32, channel 0 the detection logit and channels 1.. the message bits:
+    ClipScores(prob, llr, votes, words, biterr) on the logits' device --
+      prob (R,) float32         the mean over t of sigmoid(logits[:, t, 0]): the reference's per-clip score
+      llr (R, NO) float32       the mean logit of every channel
+      votes (R, NO) int32       exact: the samples with sigmoid(channel 0) > threshold (taken as logit > log(p / (1 - p)), as
+                                loc_counts does), and for o >= 1 the samples with logit > 0; a NaN casts no vote
+      words (R, 2) int64        the decoded message: [:, 0] the majority of the hard decisions (a tie is 0), [:, 1] the sign of the summed logits
+      biterr (B, 2) int32       the wrong bits of words[:B] against `message` ((B,) int64, B <= R: the watermarked rows come first);
+                                (0, 2) without a message
+    CUDA tensors: one wm_clip_scores call, no host sync.  CPU tensors: the float64 restatement detection.clip_scores_host rounded to
+    float32, the integers exact -- so that what is built on top runs without a GPU."""
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError(f"logits: expected a tensor, got {type(logits).__name__}")
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise ValueError(f"logits: expected a float32 (R, T, NO) tensor, got {logits.dtype} with shape {tuple(logits.shape)}")
+    R, T, NO = logits.shape
+    if R < 1 or T < 1 or NO < 1 or NO > 64 or T > CLIP_SCORES_MAX_T or R * T * NO > 2 ** 46:
+        raise ValueError(f"logits: needs at least one row, 1 .. 2^24 samples, 1 .. 64 channels and at most 2^46 elements, got shape {tuple(logits.shape)}")
+    thr = loc_threshold_logit(threshold)
+    B = 0
+    if message is not None:
+        if not isinstance(message, torch.Tensor) or message.dtype != torch.int64 or message.dim() != 1:
+            raise ValueError("message: expected a (B,) int64 tensor")
+        if message.device != logits.device:
+            raise ValueError(f"logits and message: expected one device, got {logits.device} and {message.device}")
+        B = message.shape[0]
+        if B > R:
+            raise ValueError(f"message: at most one per row of logits ({R}), got {B}")
+    dev = logits.device
+    if not logits.is_cuda:
+        from .detection import clip_scores_host
+        prob, llr, votes, words, biterr = clip_scores_host(logits.detach().numpy(), None if message is None else message.numpy(), thr)
+        return ClipScores(torch.from_numpy(prob.astype("float32")), torch.from_numpy(llr.astype("float32")), torch.from_numpy(votes),
+                          torch.from_numpy(words), torch.from_numpy(biterr))
+    logits = logits.contiguous()
+    message = None if message is None else message.contiguous()
+    prob, llr = _f32(R, device=dev), _f32(R, NO, device=dev)
+    votes = torch.empty(R, NO, dtype=torch.int32, device=dev)
+    words = torch.empty(R, 2, dtype=torch.int64, device=dev)
+    biterr = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(clip_scores_plan(R, T, NO) // 4, dtype=torch.int32, device=dev)
+    lib.wm_clip_scores(_p(logits), _p(message) if B else None, thr, _p(prob), _p(llr), _p(votes), _p(words), _p(biterr) if B else None,
+                       _p(scratch), B, R, T, NO, _stream())
+    return ClipScores(prob, llr, votes, words, biterr)

@@ -750,6 +750,47 @@ int wm_bce_masked_bwd(const float* logits, const long long* message, const int* 
 int wm_loc_score(const float* logits, const int* lab, float thr_logit, int* counts, int* pred, int R, int T, int NO,
                  int lab_rows, wm_stream_t stream);
 
+/* ---- per-clip detection scores: what an operating-point report (ROC, AUC, TPR at a set FPR, message accuracy) needs of the logits ------
+ * replaces the per-clip reductions of evaluate_model (py/main16.py:386-403: sigmoid, mean, compare, mean, compare) and feeds what the
+ * reference hands to roc_curve / auc / confusion_matrix (py/main16.py:2372-2386) with one pass over the Detector's output.
+ * logits [R][T][NO] fp32 contiguous, channel 0 the detection logit, channels 1 .. NO - 1 the message bits; message [B] int64 (optional),
+ * bit o - 1 the target of channel o, for the rows r < B; 1 <= T <= 2^24, 1 <= NO <= 64, 0 <= B <= R, R * T * NO <= 2^46.
+ * Per row r, with x[t][o] = logits[r][t][o]:
+ *   prob[r]        fp32   (1 / T) sum_t sigmoid(x[t][0])                   the reference's per-clip score              (optional)
+ *   llr[r][o]      fp32   (1 / T) sum_t x[t][o], o in [0, NO)              the mean log-likelihood ratio               (optional)
+ *   votes[r][o]    int32  o = 0: #{t : x[t][0] > thr_logit};  o >= 1: #{t : x[t][o] > 0}                  exact; a NaN is no vote
+ *   words[r][0]    int64  bit o - 1 set iff 2 * votes[r][o] > T            the majority of hard decisions; a tie is 0  (optional)
+ *   words[r][1]    int64  bit o - 1 set iff sum_t x[t][o] > 0              the soft decision: the sum of log-likelihood ratios, the
+ *                                                                          combination the reference does not have; a NaN sum is 0
+ *   biterr[r][k]   int32  r < B: popcount((words[r][k] ^ message[r]) & (2^(NO-1) - 1)), k = 0, 1                       (optional)
+ *                         B = 0 or message == NULL leaves biterr untouched; NO = 1 writes zeros to words and biterr.
+ * The vote is taken on the LOGIT: x > thr_logit with thr_logit = log(p / (1 - p)) from the caller (+-inf allowed: no vote / every
+ * non-NaN sample above -inf votes), x > 0 for the bits -- as wm_loc_score does -- not on sigmoid(x) > p in fp32.  The two differ only
+ * for 0 < x <~ 2^-23, where the fp32 sigmoid rounds to 0.5 exactly and the reference's comparison says no.  For logits that are 0 or
+ * at least 1e-3 in magnitude the integer rule gives the decoded bits of evaluate_model's (mean_t (sigmoid > 0.5)) > 0.5 exactly.
+ * Sums.  A row is cut into chunks of 8192 ELEMENTS (of its T * NO; a constant).  Per chunk and channel one fp32 partial: the elements of
+ *   the channel are dealt to floor(256 / NO) threads (thread j takes every floor(256 / NO)-th, in rising t, one fp32 chain from +0), and
+ *   the threads' sums are added in four chains (j mod 4) in rising j, ((c0 + c1) + (c2 + c3)).  The sigmoids (1 / (1 + expf(-x)), IEEE
+ *   division) of a chunk: 256 chains, the wave butterfly 32 .. 1, the four waves in rising order.  The finish adds a row's partials in
+ *   fp64: chunks in four contiguous groups of ceil(chunks / 4), inside a group four chains (position mod 4) in rising order, the groups
+ *   in rising order; prob's 256 chains (chunk mod 256) by the same butterfly.  prob = (float)(sum / T), llr likewise; the soft bit
+ *   tests the finished fp64 sum.  The order depends on (T, NO) alone: a row's bits depend on its own samples, T, NO, thr_logit and its
+ *   message -- never on R, the row's place in the batch, the grid or the pointer's alignment.  Rows [0, R) in one call equal R one-row
+ *   calls bit for bit; two launches give identical bits.
+ * Non-finite samples: a NaN makes prob[r] (channel 0) or llr[r][o] of ITS row and channel NaN and casts no vote; +-inf vote by the
+ *   comparison, give sigmoid 1 / 0 and an infinite (or, with both signs, NaN) llr.  No other row or channel changes a bit.
+ * Two launches (csrc/clip_scores.hip: one workgroup per (row, chunk) stages the chunk through LDS with 16-byte loads wherever a whole
+ * aligned group lies inside it; then one workgroup per row), stateless, enqueue-only, no atomics.  logits may start at any multiple of
+ * 4 bytes; message and words at multiples of 8, the rest of 4.
+ * scratch: wm_clip_scores_plan(R, T, NO) BYTES (host-only query, scratch_bytes is a HOST pointer, stream unused) =
+ *   R * ceil(T * NO / 8192) * (2 NO + 1) * 4; caller-allocated, contents unspecified before and after.
+ * hipErrorInvalidValue before any launch: R or T < 1, NO outside [1, 64], B outside [0, R], R * T * NO > 2^46, T > 2^24 (int32 counts,
+ * fp32 partials), a NaN thr_logit, a null logits, votes or scratch, a misaligned pointer, an output (scratch included) overlapping an
+ * input or another output. */
+int wm_clip_scores_plan(long long R, int T, int NO, long long* scratch_bytes, wm_stream_t stream);
+int wm_clip_scores(const float* logits, const long long* message, float thr_logit, float* prob, float* llr, int* votes, long long* words,
+                   int* biterr, void* scratch, long long B, long long R, int T, int NO, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
