@@ -7,7 +7,7 @@ from .step import LOSS_WEIGHTS, forward_losses, train_step, eval_forward
 from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
 from .attacks import (Convolved, Distortion, Lowpass, LpcCodec, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
-                      evaluate_localization, evaluate_robustness, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
+                      evaluate_localization, evaluate_robustness, evaluate_robustness_by_class, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
 from . import attacks
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
                         evaluate_unseen_file, generate_watermarked_audio, load_audio, locate_watermark, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
@@ -17,6 +17,8 @@ from .quality import stoi
 from . import quality
 from .detection import (auc, calibrate_threshold, detection_report, eer, evaluate_detection, operating_point, roc_curve, tpr_at_fpr)
 from . import detection
+from .curate import (butter_bandpass_sos, classify_speech_noise, clip_features, curate_files, dct_ortho, is_silent, prepare_recording, slaney_mel)
+from . import curate
 from . import checkpoint
 from . import main14b_2
 from . import distributed
@@ -26,9 +28,10 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "fir_lowpass", "clamp_peak", "limit_rms", "postprocess", "high_freq_penalty", "detection_losses", "l1_to_zero",
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
-           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "LpcCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness",
+           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "LpcCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness", "evaluate_robustness_by_class",
            "Splice", "evaluate_localization", "row_splice_spans", "splice_rows_host", "pack_labels", "unpack_labels", "detection_losses_masked",
            "locate_watermark",
            "stoi", "quality",
            "detection", "evaluate_detection", "detection_report", "roc_curve", "auc", "eer", "tpr_at_fpr", "calibrate_threshold", "operating_point",
+           "curate", "clip_features", "classify_speech_noise", "is_silent", "prepare_recording", "curate_files", "butter_bandpass_sos", "slaney_mel", "dct_ortho",
            "lib", "LIB_PATH"]

@@ -1163,6 +1163,21 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
     clips with fewer than 30 spectral frames have no score and are left out, not averaged in as the sentinel 1e-5 (NaN when none is
     left).  STOI assumes time-aligned signals: under TimeWarp it is low by construction and says nothing.  The default, quality=(), is
     the call as it was."""
+    return _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, False)
+
+
+@torch.no_grad()
+def evaluate_robustness_by_class(generator, detector, batches, attacks, device="cuda", message_bits=16, messages=None, quality=()):
+    """evaluate_robustness with every number given again per class of clean clip: each row gains "by_class", {"speech" | "noise" |
+    "silent": {"clips": count, and the row's keys over that class's clips (NaN for an empty class)}}.  The classes are
+    curate.clip_classes of the clean batch -- one wm_clip_features launch per batch, before the attacks -- and a clip with a non-finite
+    sample is in none.  With quality=("stoi",) a class's "stoi_rows" counts its scored clips.  (evaluate_robustness keeps its parameter
+    list, so the per-class report is a call of its own rather than a by_class argument.)"""
+    return _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, True)
+
+
+def _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, by_class):
+    """the loop of evaluate_robustness and evaluate_robustness_by_class"""
     from .step import _eval_reductions
     from .quality import check_metrics
     quality = check_metrics(quality)
@@ -1174,10 +1189,15 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
     named = [("none", None)] + list(attacks.items())
     acc = OrderedDict((name, {k: [] for k in keys}) for name, _ in named)
     stoi_acc = OrderedDict((name, ([], [])) for name, _ in named)
+    stoi_all = OrderedDict((name, ([], [], [])) for name, _ in named)               # by_class: both halves unmasked, and the mask
+    classes = []
     for bi, s in enumerate(batches):
         s = s.to(device)
         message = (messages[bi].to(device) if messages is not None else
                    torch.randint(0, 2 ** message_bits, (s.shape[0],), device=device))
+        if by_class:
+            from .curate import clip_classes
+            classes.append(clip_classes(s, SAMPLE_RATE))
         delta = postprocess(generator(s, message))
         both = torch.cat([s + delta, s], dim=0)
         for name, attack in named:
@@ -1191,6 +1211,9 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
                 scored = (kept[:B] > 30) | torch.isnan(d[:B])                      # the mask is decided on s: one for both halves
                 stoi_acc[name][0].append(d[:B][scored])
                 stoi_acc[name][1].append(d[B:][scored])
+                if by_class:
+                    for dst, v in zip(stoi_all[name], (d[:B], d[B:], scored)):
+                        dst.append(v)
     res = OrderedDict((name, {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in a.items()})
                       for name, a in acc.items())
     if "stoi" in quality:
@@ -1199,4 +1222,20 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
             res[name]["stoi"] = float(pooled.double().mean()) if pooled.numel() else math.nan
             res[name]["stoi_attack_only"] = float(torch.cat(clean_half).double().mean()) if pooled.numel() else math.nan
             res[name]["stoi_rows"] = int(pooled.numel())
+    if by_class:
+        from .curate import CLASSES, class_report
+        cls = torch.cat(classes) if classes else torch.empty(0, dtype=torch.int64)
+        for name, a in acc.items():
+            per = class_report({k: (torch.cat(v) if v else torch.empty(0)) for k, v in a.items()}, cls)
+            if "stoi" in quality and stoi_all[name][0]:
+                wm_half, clean_half, scored = (torch.cat(v).cpu() for v in stoi_all[name])
+                for i, c in enumerate(CLASSES):
+                    pick = (cls.cpu() == i) & scored
+                    per[c]["stoi"] = float(wm_half[pick].double().mean()) if pick.any() else math.nan
+                    per[c]["stoi_attack_only"] = float(clean_half[pick].double().mean()) if pick.any() else math.nan
+                    per[c]["stoi_rows"] = int(pick.sum())
+            elif "stoi" in quality:
+                for c in CLASSES:
+                    per[c].update(stoi=math.nan, stoi_attack_only=math.nan, stoi_rows=0)
+            res[name]["by_class"] = per
     return res

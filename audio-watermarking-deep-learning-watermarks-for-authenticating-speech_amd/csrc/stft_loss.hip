@@ -9,7 +9,7 @@
 // workgroup then evaluates the loss term AND its gradient w.r.t. the time-domain frame (inverse transform of
 // the Hermitian-completed spectral gradient, again two-for-one), so forward + backward of a loss is one
 // kernel plus a deterministic overlap-add gather -- no spectrogram ever reaches HBM.
-#include "wm_common.hpp"
+#include "fft_lds.hpp"
 using namespace wm;
 
 namespace {
@@ -29,26 +29,6 @@ struct StftArgs {
     int kcut;            // HF: first penalised bin
     int T, F, hop;
 };
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-template <int LOGN>
-__device__ __forceinline__ void fft_dif(float2* z, const float2* tw, int tid) {
-    constexpr int N = 1 << LOGN;
-#pragma unroll 1
-    for (int st = 0; st < LOGN; ++st) {
-        const int lm = LOGN - 1 - st, m = 1 << lm;           // half size of this stage's butterflies
-        for (int j = tid; j < N / 2; j += 256) {
-            const int pos = j & (m - 1), i0 = ((j >> lm) << (lm + 1)) + pos, i1 = i0 + m;
-            const float2 a = z[i0], b = z[i1], w = tw[pos << st];
-            z[i0] = make_float2(a.x + b.x, a.y + b.y);
-            z[i1] = cmul(make_float2(a.x - b.x, a.y - b.y), w);
-        }
-        __syncthreads();
-    }
-}
-template <int LOGN>
-__device__ __forceinline__ int brev(int k) { return (int)(__brev((unsigned)k) >> (32 - LOGN)); }
 
 __device__ __forceinline__ int reflect_idx(int m, int T) {
     if (m < 0) m = -m;

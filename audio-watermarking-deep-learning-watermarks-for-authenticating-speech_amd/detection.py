@@ -200,7 +200,7 @@ def clip_scores_host(logits, message=None, thr_logit=0.0):
 
 @torch.no_grad()
 def evaluate_detection(generator, detector, batches, attacks=None, device="cuda", message_bits=16, messages=None, fpr_targets=(0.01,),
-                       threshold=0.5, score="prob", decode="vote"):
+                       threshold=0.5, score="prob", decode="vote", by_class=False):
     """Detection operating points under attacks: {"none": row, name: row, ...}, every row a detection_report.
     The loop is attacks.evaluate_robustness's -- eval mode, no_grad, the Generator once per batch, every attack applied to the
     concatenation of s + delta and s, the Detector once per attack -- with ONE ops.clip_scores call per Detector call in place of the
@@ -212,7 +212,10 @@ def evaluate_detection(generator, detector, batches, attacks=None, device="cuda"
     `threshold` is the probability both the per-sample vote and the row's "operating_point" use.  "tpr_at_fpr" is read off the row's own
     curve, i.e. calibrated on this attack's clean half; "deployed" applies the thresholds calibrated on the "none" row's clean scores
     under the attack.  message_bits = 0 gives NaN for "ber" and "message_accuracy".  `messages` (optional list, one tensor per batch)
-    replaces the random draw."""
+    replaces the random draw.
+    `by_class=True` adds "by_class" to every row: {"speech" | "noise" | "silent": a detection_report over that class's clips alone} (its
+    "clips" is the class's count; "deployed" uses the thresholds calibrated on ALL clean clips of the "none" row), the classes being
+    curate.clip_classes of the clean batch (one wm_clip_features launch per batch; a clip with a non-finite sample is in none)."""
     from . import ops
     from .losses import postprocess
     if score not in SCORES:
@@ -227,9 +230,13 @@ def evaluate_detection(generator, detector, batches, attacks=None, device="cuda"
     generator.eval(); detector.eval()
     named = [("none", None)] + list(attacks.items())
     acc = OrderedDict((name, ([], [], [])) for name, _ in named)                            # marked scores, clean scores, bit errors
+    classes = []
     for bi, s in enumerate(batches):
         s = s.to(device)
         B = s.shape[0]
+        if by_class:
+            from .curate import clip_classes
+            classes.append(clip_classes(s, 16000))
         message = (messages[bi].to(device) if messages is not None else
                    torch.randint(0, 2 ** message_bits, (B,), device=device))
         delta = postprocess(generator(s, message))
@@ -244,4 +251,11 @@ def evaluate_detection(generator, detector, batches, attacks=None, device="cuda"
     pooled = OrderedDict((name, [torch.cat(v).cpu().numpy() if v else np.zeros(0) for v in a]) for name, a in acc.items())
     clean0 = pooled["none"][1]
     deployed = {t: calibrate_threshold(clean0, t).threshold for t in targets} if clean0.size else {}
-    return OrderedDict((name, detection_report(m, c, be, message_bits, targets, threshold, deployed)) for name, (m, c, be) in pooled.items())
+    res = OrderedDict((name, detection_report(m, c, be, message_bits, targets, threshold, deployed)) for name, (m, c, be) in pooled.items())
+    if by_class:
+        from .curate import CLASSES
+        cls = torch.cat(classes).cpu().numpy() if classes else np.zeros(0, dtype=np.int64)
+        for name, (m, c, be) in pooled.items():
+            res[name]["by_class"] = OrderedDict((cname, detection_report(m[cls == i], c[cls == i], be[cls == i], message_bits, targets, threshold,
+                                                                         deployed)) for i, cname in enumerate(CLASSES))
+    return res

@@ -565,24 +565,37 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
 
 
 @torch.no_grad()
-def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None, codec=None, tamper=None):
+def evaluate_batches(generator, detector, batches, device="cuda", message_bits=16, threshold=0.5, messages=None, codec=None, tamper=None,
+                     by_class=False):
     """evaluate_model (:369-423): the per-batch reductions run on the device (step.eval_forward); the per-clip values of
     all batches are pooled and averaged once, as the reference's np.mean over its extended lists does (so a ragged last
     batch weighs by its clips).  `messages` (optional list, one tensor per batch) replaces the randint draw of :381.
     `codec` (a codec.PcmCodec): the Detector is evaluated on codec(s + delta), as in main15c's validate_one_epoch.
     `tamper` (an attacks.Splice): the watermarked half is spliced behind the codec (step.eval_forward); the averages are the same ones, so
-    the watermarked probability falls with the share that was cut out -- attacks.evaluate_localization scores the per-sample track."""
+    the watermarked probability falls with the share that was cut out -- attacks.evaluate_localization scores the per-sample track.
+    `by_class=True` adds "by_class": {"speech" | "noise" | "silent": {"clips": count, and the four keys over that class's clips (NaN for
+    an empty class)}}, the classes being curate.clip_classes of the clean batch (one wm_clip_features launch per batch; a clip with a
+    non-finite sample is in none).  The default returns the dict as it was."""
     from .step import eval_forward
     generator.eval(); detector.eval()
     keys = {"watermarked_prob": "prob_watermarked", "clean_prob": "prob_clean", "bit_accuracy": "bit_accuracy",
             "delta_rms": "delta_rms"}
     acc = {k: [] for k in keys}
+    classes = []
     for bi, s in enumerate(batches):
         s = s.to(device)
         message = (messages[bi].to(device) if messages is not None else
                    torch.randint(0, 2 ** message_bits, (s.shape[0],), device=device))
+        if by_class:
+            from .curate import clip_classes
+            classes.append(clip_classes(s, SAMPLE_RATE))
         extra = {} if tamper is None else {"tamper": tamper}
         out = eval_forward(generator, detector, s, message, codec=codec, **extra)
         for k, src in keys.items():
             acc[k].append(out[src])
-    return {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in acc.items()}
+    res = {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in acc.items()}
+    if by_class:
+        from .curate import class_report
+        res["by_class"] = class_report({k: (torch.cat(v) if v else torch.empty(0)) for k, v in acc.items()},
+                                       torch.cat(classes) if classes else torch.empty(0, dtype=torch.int64))
+    return res

@@ -2483,3 +2483,49 @@ def clip_scores(logits, message=None, threshold=0.5):
     lib.wm_clip_scores(_p(logits), _p(message) if B else None, thr, _p(prob), _p(llr), _p(votes), _p(words), _p(biterr) if B else None,
                        _p(scratch), B, R, T, NO, _stream())
     return ClipScores(prob, llr, votes, words, biterr)
+
+
+# ---------------------------------------------------------------------------------------------- clip curation features
+# wm_clip_features (csrc/clip_features.hip; the definition is in include/wm_hip.h): the speech / noise feature table and the silence
+# measure of the reference's dataset scripts, one launch for all rows.  Nothing is differentiated: a measure, not a loss.
+ClipFeaturesPlan = collections.namedtuple("ClipFeaturesPlan", "frames energy_frames lds_bytes")
+
+
+def clip_features_plan(rows, n, sample_rate=16000):
+    """ClipFeaturesPlan(frames, energy_frames, lds_bytes) of one wm_clip_features launch on (rows, n) at sample_rate: F = 1 + n // 512
+    spectral frames per row, the 25-ms frames of energy_std, the LDS one workgroup takes.  ValueError where the launch would be refused."""
+    import ctypes
+    from .curate import check_shape
+    _chk_int(rows, "rows", 1, 2 ** 40)
+    _chk_int(n, "n", 1, math.inf, "a positive int")
+    sr = check_shape(n, sample_rate)
+    out = (ctypes.c_int * 3)()
+    base = ctypes.addressof(out)
+    lib.wm_clip_features_plan(rows, n, sr, base, base + 4, base + 8, None)
+    return ClipFeaturesPlan(out[0], out[1], out[2])
+
+
+def clip_features(x, sample_rate=16000, frames=False):
+    """The curation features of every row of x: a float32 tensor (B, 1, T), (C, N) or (N,) at `sample_rate`, 400 .. 32768 samples a row.
+    Returns (feat (rows, 16) float32, counts (rows, 4) int32) on x's device, and with frames=True also frames (rows, F, 4) float32 -- per
+    spectral frame the centroid, the bandwidth, the roll-off bin and the zero-crossing count.  The columns of feat are curate.FEATURES
+    (then three reserved zeros); counts holds the zero-crossing total, the speech score, the non-finite flag and the label (1 speech,
+    0 noise, -1 non-finite).  CUDA tensors: ONE wm_clip_features launch, no host sync.  CPU tensors: the float64 restatement
+    curate.clip_features_host rounded to float32, the integers exact."""
+    from . import curate
+    rows_t = _stoi_rows(x, "x")
+    rows, n = rows_t.shape
+    sr = curate.check_shape(n, sample_rate)
+    if not rows_t.is_cuda:
+        out = curate.clip_features_host(rows_t.detach().numpy(), sr, frames)
+        res = (torch.from_numpy(out[0].astype("float32")), torch.from_numpy(out[1]))
+        return res + (torch.from_numpy(out[2].astype("float32")),) if frames else res
+    dev = rows_t.device
+    F = clip_features_plan(rows, n, sr).frames
+    tab = curate.tables_on(sr, dev)
+    feat = _f32(rows, 16, device=dev)
+    counts = torch.empty(rows, 4, dtype=torch.int32, device=dev)
+    per = _f32(rows, F, 4, device=dev) if frames else None
+    lib.wm_clip_features(_p(rows_t), _p(tab["sos"]), _p(tab["fb"]), _p(tab["klo"]), _p(tab["khi"]), _p(tab["dct"]), _p(feat), _p(counts),
+                         _p(per), rows, n, sr, tab["warm"], _stream())
+    return (feat, counts, per) if frames else (feat, counts)

@@ -791,6 +791,58 @@ int wm_clip_scores_plan(long long R, int T, int NO, long long* scratch_bytes, wm
 int wm_clip_scores(const float* logits, const long long* message, float thr_logit, float* prob, float* llr, int* votes, long long* words,
                    int* biterr, void* scratch, long long B, long long R, int T, int NO, wm_stream_t stream);
 
+/* ---- clip curation: the speech / noise feature table and the silence measure of the dataset scripts, one launch ----------------------
+ * replaces analyze_audio_file + classify_speech_noise of dataset_creation/noise.py (librosa 0.10 defaults, scipy) and the rms of
+ * dataset_creation/silent.py, which the reference runs per file in a process pool.  x (rows, n) fp32 at sample_rate sr, every row on its
+ * own; 400 <= n <= 32768, 6000 < sr <= 2^20, int(0.025 sr) <= n, rows >= 1.  With y = the row and F = 1 + n / 512 (integer division):
+ *   feat (rows, 16) fp32, the columns in this order (0..11 are the reference's CSV columns):
+ *    0 duration               n / sr
+ *    1 energy                 mean(y^2)
+ *    2 speech_band_energy     mean(z^2), z = y through the order-5 Butterworth band-pass 300..3000 Hz from zero initial state
+ *                             (scipy.signal.butter(5, [300, 3000] / (sr / 2), 'band') + lfilter), run as the five second-order sections
+ *                             sos (5, 6) = rows of b0 b1 b2 1 a1 a2, cascaded in the order given, transposed direct form II
+ *    3 zero_crossing_rate     y padded by 1024 samples at each end with the EDGE value, F frames of 2048 at hop 512, samples with
+ *                             |v| <= 1e-10 set to 0; a position i >= 1 of a frame counts iff signbit differs from position i - 1 (the
+ *                             first sample of a frame never counts); rate = total count / (2048 F)
+ *    4 spectral_centroid      S = |rfft(frame * periodic Hann 2048)| on y padded by 1024 ZEROS at each end, hop 512, f_k = k sr / 2048;
+ *    5 spectral_bandwidth     per frame c = sum f_k S_k / sum S_k, bandwidth = sqrt(sum (S_k / sum S)(f_k - c)^2), roll-off bin = the
+ *    6 rolloff                smallest k with cumsum(S)_k >= 0.85 sum S (the feature is its frequency k sr / 2048); a frame whose sum S
+ *                             is below fp32 tiny (1.17549435e-38) gives 0 for all three; each feature is the mean over the F frames
+ *    7 mfcc_mean              M = S^2 mel^T with fb (1025, 128) fp32 (fb[k][m], 128 Slaney-scale, Slaney-normalised triangles from 0 to
+ *    8 mfcc_var               sr / 2, built in fp64 and rounded) of which mel m uses the bins klo[m] .. khi[m] (inclusive; the banded form
+ *                             of wm_mel_loss); dB = 10 log10(max(1e-10, M)), clamped from below at (maximum dB of the clip) - 80; the
+ *                             first 13 coefficients of the orthonormal DCT-II along the mel axis, dct (13, 128) fp32; mfcc_mean = the
+ *                             mean over coefficients of the mean over frames, mfcc_var = the mean over coefficients of the variance
+ *                             over frames (ddof 0)
+ *    9 kurtosis               m4 / m2^2 - 3 on central moments (the mean first, then the moments); NaN when m2 = 0
+ *   10 energy_std             population standard deviation of the mean square of the frames of int(0.025 sr) samples at hop
+ *                             int(0.010 sr), unpadded: 1 + (n - length) / hop of them
+ *   11 speech_to_noise_ratio  speech_band_energy / (energy + 1e-10)
+ *   12 rms                    sqrt(energy): the quantity silent.py compares with its threshold (the caller applies the threshold)
+ *   13..15                    reserved, written as +0
+ *   counts (rows, 4) int32:   [0] the total zero-crossing count, exact;  [1] speech_score = classify_speech_noise: +1 for each of
+ *                             speech_band_energy > 0.001, zero_crossing_rate < 0.1, spectral_centroid < 3000, kurtosis > 5,
+ *                             energy_std > 0.01, +2 for speech_to_noise_ratio > 0.6, compared in fp32, a comparison with NaN false;
+ *                             [2] 1 iff the row holds a non-finite sample;  [3] the label: 1 speech (score >= 4), 0 noise, -1 non-finite
+ *   frames_out (rows, F, 4) fp32, optional: per frame the centroid (Hz), the bandwidth (Hz), the roll-off BIN and the zero-crossing count.
+ *   A row with a non-finite sample has columns 0..12 NaN, counts {0, 0, 1, -1} and NaN frames; no other row changes a bit.
+ * Computed in fp32 (csrc/clip_features.hip): ONE launch, one workgroup per row, stateless, enqueue-only, no scratch, no atomics.  A row of
+ * n <= 16384 samples is read from memory once (it is held in LDS beside the transform's workspace and the F x 128 dB table); a longer
+ * row is re-read through L2.  Two neighbouring frames share one complex 2048-point transform (2^-23 of the louder one is left in the
+ * other's spectrum; a frame whose windowed samples are all zero has a spectrum of exactly zero).  The band-pass runs in 256 chunks,
+ * each started `warm` samples early from zero state (at sample 0 where the chunk begins before `warm`): the caller passes a warm-up
+ * after which the cascade's impulse response is below 1e-7 (curate.bandpass_warmup: 512 at 16 kHz).  A row's bits depend on its samples,
+ * n, sr, warm and the tables -- never on rows, the row's place in the batch or the grid; two launches give identical bits.
+ * wm_clip_features_plan (host-only query, the outputs are HOST pointers, stream unused): frames = F, energy_frames = the number of
+ * 25-ms frames, lds_bytes = the LDS one workgroup of the launch takes.
+ * Pointers may start at any multiple of 4 bytes; inputs are borrowed.  hipErrorInvalidValue before any launch: rows, n, sample_rate or
+ * warm (outside [0, 32768]) out of range, int(0.025 sr) > n, a null (frames_out excepted) or misaligned pointer, an output overlapping
+ * an input or another output. */
+int wm_clip_features_plan(long long rows, long long n, int sample_rate, int* frames, int* energy_frames, int* lds_bytes,
+                          wm_stream_t stream);
+int wm_clip_features(const float* x, const float* sos, const float* fb, const int* klo, const int* khi, const float* dct, float* feat,
+                     int* counts, float* frames_out, long long rows, long long n, int sample_rate, int warm, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
