@@ -19,6 +19,7 @@ from .detection import (auc, calibrate_threshold, detection_report, eer, evaluat
 from . import detection
 from .curate import (butter_bandpass_sos, classify_speech_noise, clip_features, curate_files, dct_ortho, is_silent, prepare_recording, slaney_mel)
 from . import curate
+from . import dsp, ops
 from . import checkpoint
 from . import main14b_2
 from . import distributed

@@ -53,7 +53,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import dsp
+from ._host import _chk_int, _chk_positive
 from .codec import SAMPLE_RATE, _time_rows
 from .losses import postprocess
 
@@ -69,8 +70,8 @@ FAMILIES = {
     "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry; o3: LpcCodec's SNR
     "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
     "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones
-    **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
-    **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(ops.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
+    **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
+    **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
 }
 
 
@@ -153,18 +154,18 @@ class _RowDraws(torch.nn.Module):
 
     def __init__(self, seed):
         super().__init__()
-        self.seed = ops._chk_int(seed, "seed", what="an int")
+        self.seed = _chk_int(seed, "seed", what="an int")
         self.reset()
 
     def reset(self, draw=0):
-        self.draw = ops._chk_int(draw, "draw", 0, 2 ** 32 - 1, "an int in [0, 2^32)")
+        self.draw = _chk_int(draw, "draw", 0, 2 ** 32 - 1, "an int in [0, 2^32)")
         return self
 
     def _rows(self, x, row0):
         """x as time rows and their number; row0 + rows must stay a row counter"""
         x = _time_rows(x, "x")
         rows = x.numel() // x.shape[-1]
-        ops._chk_int(row0, "row0", 0, 2 ** 32 - rows, "an int with 0 <= row0 and row0 + rows <= 2^32")
+        _chk_int(row0, "row0", 0, 2 ** 32 - rows, "an int with 0 <= row0 and row0 + rows <= 2^32")
         return x, rows
 
     def _next_draw(self):
@@ -202,7 +203,7 @@ class Distortion(_RowDraws):
         x, _ = self._rows(x, row0)
         draw = self._next_draw()
         if x.is_cuda:
-            y, stat = ops.DistortFn.apply(x.to(torch.float32), self.bounds, self.seed, draw, row0, self.noise_grad == "through")
+            y, stat = dsp.DistortFn.apply(x.to(torch.float32), self.bounds, self.seed, draw, row0, self.noise_grad == "through")
         else:
             y, stat = self._host(x.detach().to(torch.float32), draw, row0)
         self.last_stat = stat
@@ -234,11 +235,11 @@ class _LowpassFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, coeffs):
         ctx.coeffs = coeffs
-        return ops.biquad(x, coeffs, clamp=False, mode="float")
+        return dsp.biquad(x, coeffs, clamp=False, mode="float")
 
     @staticmethod
     def backward(ctx, g):
-        return ops.biquad(g.contiguous(), ctx.coeffs, clamp=False, mode="float", reverse=True), None
+        return dsp.biquad(g.contiguous(), ctx.coeffs, clamp=False, mode="float", reverse=True), None
 
 
 class Lowpass(torch.nn.Module):
@@ -248,7 +249,7 @@ class Lowpass(torch.nn.Module):
 
     def __init__(self, cutoff, sample_rate=SAMPLE_RATE):
         super().__init__()
-        self.coeffs = ops.biquad_lowpass_coeffs(sample_rate, cutoff)              # bad rates fail here
+        self.coeffs = dsp.biquad_lowpass_coeffs(sample_rate, cutoff)              # bad rates fail here
         self.cutoff, self.sample_rate = cutoff, sample_rate
 
     def forward(self, x):
@@ -273,8 +274,8 @@ class Resampled(torch.nn.Module):
 
     def __init__(self, rate, sample_rate=SAMPLE_RATE):
         super().__init__()
-        ops.resample_table(sample_rate, rate)                                     # bad rates fail here
-        ops.resample_table(rate, sample_rate)
+        dsp.resample_table(sample_rate, rate)                                     # bad rates fail here
+        dsp.resample_table(rate, sample_rate)
         self.rate, self.sample_rate = int(rate), int(sample_rate)
 
     def forward(self, x):
@@ -284,7 +285,7 @@ class Resampled(torch.nn.Module):
         T = x.shape[-1]
         rows = x.to(torch.float32).reshape(-1, T)
         if x.is_cuda:
-            y = ops.ResampleRowsFn.apply(ops.ResampleRowsFn.apply(rows, self.sample_rate, self.rate), self.rate, self.sample_rate, T)
+            y = dsp.ResampleRowsFn.apply(dsp.ResampleRowsFn.apply(rows, self.sample_rate, self.rate), self.rate, self.sample_rate, T)
         else:
             from .inference import _resample_rows_host
             y = _resample_rows_host(_resample_rows_host(rows, self.sample_rate, self.rate), self.rate, self.sample_rate, T)
@@ -333,15 +334,15 @@ class TransformCodec(_RowDraws):
     float32 numpy restatement of the definition (forward only)."""
 
     def __init__(self, snr_db=(10, 30), bandwidth_hz=None, hop=256, band=8, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
-        if grad not in ops.MDCT_GRAD_MODES:
-            raise ValueError(f"grad must be one of {ops.MDCT_GRAD_MODES}, got {grad!r}")
+        if grad not in dsp.MDCT_GRAD_MODES:
+            raise ValueError(f"grad must be one of {dsp.MDCT_GRAD_MODES}, got {grad!r}")
         super().__init__(seed)
         self.snr_db = _pair(snr_db, "snr_db")
         if not 0.0 <= self.snr_db[0] <= self.snr_db[1] <= 60.0:
             raise ValueError(f"snr_db: expected values in [0, 60], got {snr_db!r}")
-        self.kcut = ops.mdct_kcut(hop, band, bandwidth_hz, sample_rate)           # bad hops, bands and bandwidths fail here
+        self.kcut = dsp.mdct_kcut(hop, band, bandwidth_hz, sample_rate)           # bad hops, bands and bandwidths fail here
         self.hop, self.band, self.bandwidth_hz, self.sample_rate = hop, band, bandwidth_hz, sample_rate
-        self.floor_step = ops.mdct_default_floor_step(hop)
+        self.floor_step = dsp.mdct_default_floor_step(hop)
         self.grad = grad
         self.last_snr_db = None
 
@@ -354,7 +355,7 @@ class TransformCodec(_RowDraws):
         x, snr = self._snr(x, row0)
         self._next_draw()
         if x.is_cuda:
-            y = ops.MdctCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.hop, self.band, self.kcut, self.floor_step, self.grad)
+            y = dsp.MdctCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.hop, self.band, self.kcut, self.floor_step, self.grad)
         else:
             y = self._host(x.detach().to(torch.float32), snr)[0]
         self.last_snr_db = snr
@@ -364,7 +365,7 @@ class TransformCodec(_RowDraws):
         """(y, int16 codes (rows, F, hop)) of a CPU tensor: the definition in float32 numpy, dense matrices"""
         M, band, n, f32 = self.hop, self.band, x.shape[-1], np.float32
         x2 = x.reshape(-1, n).numpy()
-        rows, F = x2.shape[0], ops.mdct_frames(n, M)
+        rows, F = x2.shape[0], dsp.mdct_frames(n, M)
         j, k = np.arange(2 * M, dtype=np.float64), np.arange(M, dtype=np.float64)
         w = np.sin(np.pi * (j + 0.5) / (2 * M)).astype(f32)
         C = np.cos(np.pi / M * np.outer(k + 0.5, j + 0.5 + M / 2)).astype(f32)
@@ -389,7 +390,7 @@ class TransformCodec(_RowDraws):
         coder is run.  It relates snr_db to a bitrate and says nothing about what an MP3 / AAC encoder would spend."""
         x, snr = self._snr(x, row0)
         if x.is_cuda:
-            codes = ops.mdct_codec(x.detach().to(torch.float32), snr.to(x.device), hop=self.hop, band=self.band, kcut=self.kcut,
+            codes = dsp.mdct_codec(x.detach().to(torch.float32), snr.to(x.device), hop=self.hop, band=self.band, kcut=self.kcut,
                                    floor_step=self.floor_step, codes_out=True)[1]
         else:
             codes = self._host(x.detach().to(torch.float32), snr)[1]
@@ -412,8 +413,8 @@ def _lpc_rows_host(x2, snr, L, p, sample_rate, floor_step):
     definition of include/wm_hip.h with numpy's own summation order inside the autocorrelation and the frame energy."""
     f32 = np.float32
     rows, n = x2.shape
-    F = ops.lpc_frames(n, L)
-    lag, expand = (t.numpy() for t in ops.lpc_tables(p, sample_rate))
+    F = dsp.lpc_frames(n, L)
+    lag, expand = (t.numpy() for t in dsp.lpc_tables(p, sample_rate))
     j = np.arange(2 * L, dtype=np.float64)
     w = (0.5 - 0.5 * np.cos(2.0 * np.pi * (j + 0.5) / (2 * L))).astype(f32)
     xp = np.zeros((rows, L // 2 + F * L + L), dtype=f32)
@@ -474,16 +475,16 @@ class LpcCodec(_RowDraws):
     definition (forward only)."""
 
     def __init__(self, snr_db=(10, 30), frame=320, order=16, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
-        if grad not in ops.LPC_GRAD_MODES:
-            raise ValueError(f"grad must be one of {ops.LPC_GRAD_MODES}, got {grad!r}")
+        if grad not in dsp.LPC_GRAD_MODES:
+            raise ValueError(f"grad must be one of {dsp.LPC_GRAD_MODES}, got {grad!r}")
         super().__init__(seed)
         self.snr_db = _pair(snr_db, "snr_db")
         if not 0.0 <= self.snr_db[0] <= self.snr_db[1] <= 60.0:
             raise ValueError(f"snr_db: expected values in [0, 60], got {snr_db!r}")
-        ops._lpc_dims(frame, order)
-        ops.lpc_tables(order, sample_rate)                                        # a bad sample rate fails here
+        dsp._lpc_dims(frame, order)
+        dsp.lpc_tables(order, sample_rate)                                        # a bad sample rate fails here
         self.frame, self.order, self.sample_rate = frame, order, sample_rate
-        self.floor_step = ops.LPC_FLOOR_STEP
+        self.floor_step = dsp.LPC_FLOOR_STEP
         self.grad = grad
         self.last_snr_db = None
 
@@ -492,7 +493,7 @@ class LpcCodec(_RowDraws):
         snr = torch.from_numpy(row_lpc_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
         self._next_draw()
         if x.is_cuda:
-            y = ops.LpcCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.frame, self.order, self.sample_rate, self.floor_step,
+            y = dsp.LpcCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.frame, self.order, self.sample_rate, self.floor_step,
                                      self.grad)
         else:
             x32 = x.detach().to(torch.float32)
@@ -552,8 +553,8 @@ def echo_ir(delay_s, gain_db, sample_rate=SAMPLE_RATE):
     if sample_rate <= 0:
         raise ValueError(f"sample_rate must be positive, got {sample_rate!r}")
     d = int(round(delay_s * sample_rate))
-    if not 1 <= d < ops.FIR_MAX_TAPS:
-        raise ValueError(f"delay_s: the echo must fall on a tap in [1, {ops.FIR_MAX_TAPS - 1}], got tap {d} ({delay_s!r} s at {sample_rate} Hz)")
+    if not 1 <= d < dsp.FIR_MAX_TAPS:
+        raise ValueError(f"delay_s: the echo must fall on a tap in [1, {dsp.FIR_MAX_TAPS - 1}], got tap {d} ({delay_s!r} s at {sample_rate} Hz)")
     g = 10.0 ** (gain_db / 20.0)
     h = torch.zeros(d + 1, dtype=torch.float64)
     h[0], h[d] = 1.0 / math.sqrt(1.0 + g * g), g / math.sqrt(1.0 + g * g)
@@ -577,8 +578,8 @@ class Convolved(_RowDraws):
     CUDA tensors run wm_fir_rows, one launch each way (ops.FirRowsFn); CPU tensors F.conv1d in float32, differentiable by autograd."""
 
     def __init__(self, h, normalize=False, seed=0):
-        if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2) or h.numel() == 0 or not 1 <= h.shape[-1] <= ops.FIR_MAX_TAPS:
-            raise ValueError(f"h: expected a (K,) or (R, K) tensor with 1 <= K <= {ops.FIR_MAX_TAPS}, got "
+        if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2) or h.numel() == 0 or not 1 <= h.shape[-1] <= dsp.FIR_MAX_TAPS:
+            raise ValueError(f"h: expected a (K,) or (R, K) tensor with 1 <= K <= {dsp.FIR_MAX_TAPS}, got "
                              f"{tuple(h.shape) if isinstance(h, torch.Tensor) else type(h).__name__}")
         if not isinstance(normalize, bool):
             raise ValueError(f"normalize: expected a bool, got {normalize!r}")
@@ -605,7 +606,7 @@ class Convolved(_RowDraws):
             h = h[self.last_index.to(x.device)]                                   # gathered on the device: per-row taps
         x32 = x.to(torch.float32)
         if x.is_cuda:
-            return ops.FirRowsFn.apply(x32.reshape(rows, -1), h).reshape(x.shape)
+            return dsp.FirRowsFn.apply(x32.reshape(rows, -1), h).reshape(x.shape)
         return _conv_rows_host(x32.reshape(rows, -1), h).reshape(x.shape)
 
     def extra_repr(self):
@@ -630,8 +631,8 @@ class Reverb(_RowDraws):
         self.rt60, self.drr_db = _pair(rt60, "rt60"), _pair(drr_db, "drr_db")
         if not self.rt60[0] > 0.0:
             raise ValueError(f"rt60: expected positive values, got {rt60!r}")
-        self.taps = ops._chk_int(taps, "taps", 1, ops.FIR_MAX_TAPS)
-        self.sample_rate = ops._chk_positive(sample_rate, "sample_rate")
+        self.taps = _chk_int(taps, "taps", 1, dsp.FIR_MAX_TAPS)
+        self.sample_rate = _chk_positive(sample_rate, "sample_rate")
         self.last_params = self.last_ir = None
 
     def forward(self, x, row0=0):
@@ -641,8 +642,8 @@ class Reverb(_RowDraws):
         self.last_params = torch.from_numpy(np.stack([rt60, drr], axis=1))
         x32 = x.to(torch.float32)
         if x.is_cuda:
-            h = ops.rir_synth(self.last_params.to(x.device), self.taps, self.sample_rate, self.seed, draw, row0)
-            y = ops.FirRowsFn.apply(x32.reshape(rows, -1), h)
+            h = dsp.rir_synth(self.last_params.to(x.device), self.taps, self.sample_rate, self.seed, draw, row0)
+            y = dsp.FirRowsFn.apply(x32.reshape(rows, -1), h)
         else:
             h = torch.from_numpy(np.stack([rir_taps(self.seed, draw, row0 + r, rt60[r], drr[r], self.taps, self.sample_rate)
                                            for r in range(rows)]).astype(np.float32))
@@ -731,7 +732,7 @@ class TimeWarp(_RowDraws):
 
     def __init__(self, speed=(0.9, 1.1), shift_s=0.0, flutter_hz=None, flutter_depth=None, zeros=16, sample_rate=SAMPLE_RATE, seed=0):
         super().__init__(seed)
-        self.sample_rate = ops._chk_positive(sample_rate, "sample_rate")
+        self.sample_rate = _chk_positive(sample_rate, "sample_rate")
         self.speed, self.shift_s = _pair(speed, "speed"), _pair(shift_s, "shift_s")
         if not 0.5 <= self.speed[0] <= self.speed[1] <= 2.0:
             raise ValueError(f"speed: expected values in [0.5, 2], got {speed!r}")
@@ -744,7 +745,7 @@ class TimeWarp(_RowDraws):
                 raise ValueError(f"flutter_hz: expected values in (0, sample_rate / 4 = {sample_rate / 4}], got {flutter_hz!r}")
             if not 0.0 <= self.flutter_depth[0] <= self.flutter_depth[1] <= 0.25:
                 raise ValueError(f"flutter_depth: expected values in [0, 0.25], got {flutter_depth!r}")
-        ops.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
+        dsp.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
         self.zeros = zeros
         self.last_params = None
 
@@ -755,10 +756,10 @@ class TimeWarp(_RowDraws):
                                                             self.flutter_hz, self.flutter_depth, self.sample_rate))
         x2 = x.to(torch.float32).reshape(rows, -1)
         if x.is_cuda:
-            y = ops.TimeWarpFn.apply(x2, self.last_params.to(x.device), ops._time_warp_table_on(self.zeros, self.RES, x.device),
+            y = dsp.TimeWarpFn.apply(x2, self.last_params.to(x.device), dsp._time_warp_table_on(self.zeros, self.RES, x.device),
                                      self.zeros, self.RES)
         else:
-            y = _warp_rows_host(x2, self.last_params, ops.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
+            y = _warp_rows_host(x2, self.last_params, dsp.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
         return y.reshape(x.shape)
 
     def extra_repr(self):
@@ -788,8 +789,8 @@ def _wsola_rows_host(x2, rates, n_out, L, S):
     with the weights w and 1 - w of the adjoint's definition.  Row by row."""
     rows, n = x2.shape
     hs = L // 2
-    K = ops.wsola_frames(n_out, L)
-    win = ops.wsola_window(L)
+    K = dsp.wsola_frames(n_out, L)
+    win = dsp.wsola_window(L)
     cand = torch.arange(-S, S + 1)
     order = torch.argsort(torch.where(cand == 0, 0, torch.where(cand < 0, -2 * cand - 1, 2 * cand)))     # 0, -1, +1, -2, +2, ...
     j = torch.arange(hs)
@@ -832,14 +833,14 @@ class _Wsola(_RowDraws):
 
     def __init__(self, frame, search, seed):
         super().__init__(seed)
-        ops._wsola_dims(frame, search)
+        dsp._wsola_dims(frame, search)
         self.frame, self.search = frame, search
         self.last_params = self.last_delta = None
 
     def _stretch(self, x2, rates, n_out):
         """(rows, n) -> (rows, n_out) at the float32 rates; keeps the offsets in last_delta (on x2's device)"""
         if x2.is_cuda:
-            y, delta = ops.WsolaFn.apply(x2, torch.from_numpy(rates).to(x2.device), n_out, self.frame, self.search)
+            y, delta = dsp.WsolaFn.apply(x2, torch.from_numpy(rates).to(x2.device), n_out, self.frame, self.search)
         else:
             y, delta = _wsola_rows_host(x2, rates, n_out, self.frame, self.search)
         self.last_delta = delta
@@ -899,7 +900,7 @@ class PitchShift(_Wsola):
         self.semitones = _pair(semitones, "semitones")
         if not -12.0 <= self.semitones[0] <= self.semitones[1] <= 12.0:
             raise ValueError(f"semitones: expected values in [-12, 12], got {semitones!r}")
-        ops.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
+        dsp.time_warp_table(zeros, self.RES)                                      # a bad `zeros` fails here
         self.zeros = zeros
 
     def forward(self, x, row0=0):
@@ -917,9 +918,9 @@ class PitchShift(_Wsola):
         b64 = beta.astype(np.float64)
         params = torch.from_numpy(np.stack([b64, 0 * b64, 0 * b64, 0 * b64, 0 * b64, np.minimum(1.0, 1.0 / b64)], axis=1).astype(np.float32))
         if x.is_cuda:
-            y = ops.TimeWarpFn.apply(z, params.to(x.device), ops._time_warp_table_on(self.zeros, self.RES, x.device), self.zeros, self.RES)
+            y = dsp.TimeWarpFn.apply(z, params.to(x.device), dsp._time_warp_table_on(self.zeros, self.RES, x.device), self.zeros, self.RES)
         else:
-            y = _warp_rows_host(z, params, ops.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
+            y = _warp_rows_host(z, params, dsp.time_warp_table(self.zeros, self.RES), self.zeros, self.RES)
         return y[:, :n].reshape(x.shape)
 
     def extra_repr(self):
@@ -931,10 +932,10 @@ SPLICE_KINDS = ("original", "silence", "moved")           # the `kind` of a span
 
 def _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence):
     n = int(n)
-    if not 1 <= n <= ops.SPLICE_MAX_N:
+    if not 1 <= n <= dsp.SPLICE_MAX_N:
         raise ValueError(f"n: expected 1 <= n <= 2^24 samples, got {n}")
-    if isinstance(max_spans, bool) or not isinstance(max_spans, (int, np.integer)) or not 1 <= max_spans <= ops.SPLICE_MAX_SPANS:
-        raise ValueError(f"max_spans: expected an int in [1, {ops.SPLICE_MAX_SPANS}], got {max_spans!r}")
+    if isinstance(max_spans, bool) or not isinstance(max_spans, (int, np.integer)) or not 1 <= max_spans <= dsp.SPLICE_MAX_SPANS:
+        raise ValueError(f"max_spans: expected an int in [1, {dsp.SPLICE_MAX_SPANS}], got {max_spans!r}")
     if not 1 <= int(len_lo) <= int(len_hi) <= n:
         raise ValueError(f"span lengths: expected 1 <= len_lo <= len_hi <= n = {n} samples, got {len_lo!r} and {len_hi!r}")
     p = [np.float32(v) for v in (p_span, p_original, p_silence)]
@@ -995,7 +996,7 @@ def pack_labels(labels):
     if labels.ndim != 2:
         raise ValueError(f"labels: expected a (rows, n) array, got shape {labels.shape}")
     rows, n = labels.shape
-    W = ops.label_words(n)
+    W = dsp.label_words(n)
     padded = np.zeros((rows, W * 32), dtype=np.uint64)
     padded[:, :n] = labels
     return (padded.reshape(rows, W, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
@@ -1006,8 +1007,8 @@ def unpack_labels(lab, n):
     if isinstance(lab, torch.Tensor):
         lab = lab.detach().cpu().numpy()
     lab = np.ascontiguousarray(lab)
-    if lab.ndim != 2 or lab.dtype not in (np.uint32, np.int32) or lab.shape[1] != ops.label_words(n):
-        raise ValueError(f"lab: expected a (rows, {ops.label_words(n)}) uint32 or int32 mask for n = {n}, got {lab.dtype} {lab.shape}")
+    if lab.ndim != 2 or lab.dtype not in (np.uint32, np.int32) or lab.shape[1] != dsp.label_words(n):
+        raise ValueError(f"lab: expected a (rows, {dsp.label_words(n)}) uint32 or int32 mask for n = {n}, got {lab.dtype} {lab.shape}")
     words = lab.view(np.uint32)
     return (((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)) != 0).reshape(lab.shape[0], -1)[:, :int(n)]
 
@@ -1031,10 +1032,10 @@ class Splice(_RowDraws):
 
     def __init__(self, max_spans=2, p_span=0.5, length_s=(0.05, 0.4), kinds=(1 / 3, 1 / 3, 1 / 3), seed=0, sample_rate=SAMPLE_RATE):
         super().__init__(seed)
-        ops._chk_int(max_spans, "max_spans", 1, ops.SPLICE_MAX_SPANS)
+        _chk_int(max_spans, "max_spans", 1, dsp.SPLICE_MAX_SPANS)
         if isinstance(p_span, bool) or not isinstance(p_span, (int, float)) or not 0.0 <= p_span <= 1.0:
             raise ValueError(f"p_span: expected a probability in [0, 1], got {p_span!r}")
-        ops._chk_positive(sample_rate, "sample_rate")
+        _chk_positive(sample_rate, "sample_rate")
         self.length_s = _pair(length_s, "length_s")
         if not self.length_s[0] > 0.0:
             raise ValueError(f"length_s: expected positive lengths, got {length_s!r}")
@@ -1045,7 +1046,7 @@ class Splice(_RowDraws):
         self.max_spans, self.p_span, self.kinds, self.sample_rate = max_spans, float(p_span), tuple(map(float, kinds)), sample_rate
         self.len_lo = max(1, int(round(self.length_s[0] * sample_rate)))
         self.len_hi = max(self.len_lo, int(round(self.length_s[1] * sample_rate)))
-        if self.len_hi > ops.SPLICE_MAX_N:
+        if self.len_hi > dsp.SPLICE_MAX_N:
             raise ValueError(f"length_s: {self.length_s[1]} s is more than the 2^24 samples a row may have")
         # the kernel takes float32 probabilities and wants p_original + p_silence <= 1 of THOSE: step p_silence down where rounding broke it
         po, ps = np.float32(self.kinds[0]), np.float32(self.kinds[1])
@@ -1067,12 +1068,12 @@ class Splice(_RowDraws):
             raise ValueError(f"watermarked and clean: expected equal shapes on one device, got {tuple(a.shape)} on {a.device} and "
                              f"{tuple(b.shape)} on {b.device}")
         n = a.shape[-1]
-        if n > ops.SPLICE_MAX_N:
+        if n > dsp.SPLICE_MAX_N:
             raise ValueError(f"a row may have 2^24 samples, got {n}")
         draw = self._next_draw()
         cut = self.cut(n)
         if a.is_cuda:
-            y, lab = ops.SpliceFn.apply(a.to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous(),
+            y, lab = dsp.SpliceFn.apply(a.to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous(),
                                         tuple(cut[k] for k in ("max_spans", "p_span", "len_lo", "len_hi", "p_original", "p_silence")),
                                         self.seed, draw, row0)
         else:
@@ -1130,7 +1131,7 @@ def evaluate_localization(generator, detector, batches, tamper, device="cuda", m
             s_w = codec(s_w)
         s_t, labels = tamper(s_w, s)
         logits = detector(torch.cat([s_t, s], dim=0))
-        counts = ops.loc_counts(logits, labels, threshold).to(torch.int64)
+        counts = dsp.loc_counts(logits, labels, threshold).to(torch.int64)
         pooled += torch.stack([counts[:B].sum(dim=0), counts[B:].sum(dim=0)])
         rows += B
         nbits = logits.shape[-1] - 1
@@ -1207,7 +1208,7 @@ def _evaluate_robustness(generator, detector, batches, attacks, device, message_
                 acc[name][k].append(out[src])
             if "stoi" in quality:
                 B = s.shape[0]
-                d, kept = ops.stoi(torch.cat([s, s], dim=0), attacked, SAMPLE_RATE)
+                d, kept = dsp.stoi(torch.cat([s, s], dim=0), attacked, SAMPLE_RATE)
                 scored = (kept[:B] > 30) | torch.isnan(d[:B])                      # the mask is decided on s: one for both halves
                 stoi_acc[name][0].append(d[:B][scored])
                 stoi_acc[name][1].append(d[B:][scored])

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import dsp
 
 SAMPLE_RATE = 16000
 GRAD_MODES = ("reference", "straight_through")
@@ -30,10 +30,10 @@ def perceptual_postprocess(x, cutoff=7000, sample_rate=SAMPLE_RATE, grad="refere
     (ops.PcmCodecFn).  CPU: the stated expression over inference.lowpass_biquad (grad="reference" only)."""
     if grad not in GRAD_MODES:
         raise ValueError(f"grad must be one of {GRAD_MODES}, got {grad!r}")
-    coeffs = ops.biquad_lowpass_coeffs(sample_rate, cutoff)
+    coeffs = dsp.biquad_lowpass_coeffs(sample_rate, cutoff)
     x = _time_rows(x, "x")
     if x.is_cuda:
-        return ops.PcmCodecFn.apply(x.to(torch.float32), coeffs, grad)
+        return dsp.PcmCodecFn.apply(x.to(torch.float32), coeffs, grad)
     if grad != "reference":
         raise ValueError('grad="straight_through" needs a CUDA tensor: the CPU path has no adjoint filter')
     from .inference import lowpass_biquad
@@ -47,7 +47,7 @@ class PcmCodec(torch.nn.Module):
         super().__init__()
         if grad not in GRAD_MODES:
             raise ValueError(f"grad must be one of {GRAD_MODES}, got {grad!r}")
-        ops.biquad_lowpass_coeffs(sample_rate, cutoff)              # bad rates fail here
+        dsp.biquad_lowpass_coeffs(sample_rate, cutoff)              # bad rates fail here
         self.cutoff, self.sample_rate, self.grad = cutoff, sample_rate, grad
 
     def forward(self, x):
@@ -66,8 +66,8 @@ def encode_pcm16(waveform, sample_rate=SAMPLE_RATE, lowpass_hz=7000):
         x = x.unsqueeze(0)
     if x.dim() != 2:
         raise ValueError(f"waveform: expected (channels, samples) or (samples,), got shape {tuple(waveform.shape)}")
-    coeffs = ops.BIQUAD_IDENTITY if lowpass_hz is None else ops.biquad_lowpass_coeffs(sample_rate, lowpass_hz)
+    coeffs = dsp.BIQUAD_IDENTITY if lowpass_hz is None else dsp.biquad_lowpass_coeffs(sample_rate, lowpass_hz)
     if x.is_cuda:
-        return ops.biquad(x.to(torch.float32), coeffs, mode="pcm16")
+        return dsp.biquad(x.to(torch.float32), coeffs, mode="pcm16")
     from .inference import lowpass_biquad, pcm16
     return pcm16(x if lowpass_hz is None else lowpass_biquad(x, sample_rate, cutoff_freq=lowpass_hz))

@@ -273,8 +273,8 @@ def clip_features(clips, sample_rate=16000):
     """The feature table of clips (B, 1, T), (C, N) or (N,) float32 at `sample_rate`: an OrderedDict of name -> (rows,) tensor on the clips'
     device for every name of FEATURES (float32), then "speech_score" (int32) and "finite" (bool).  CUDA tensors: one wm_clip_features
     launch; CPU tensors: clip_features_host rounded to float32."""
-    from . import ops
-    feat, counts = ops.clip_features(clips, sample_rate)
+    from . import dsp
+    feat, counts = dsp.clip_features(clips, sample_rate)
     out = OrderedDict((name, feat[:, i]) for i, name in enumerate(FEATURES))
     out["speech_score"] = counts[:, 1]
     out["finite"] = counts[:, 2] == 0
@@ -308,8 +308,8 @@ def is_silent(waveform, threshold=SILENCE_RMS):
 def clip_classes(clips, sample_rate=16000, threshold=SILENCE_RMS):
     """the class of every clip as an index into CLASSES, (rows,) int64 on the clips' device, -1 for a clip with a non-finite sample:
     "silent" where rms < threshold, else noise.py's label.  One wm_clip_features launch on CUDA tensors."""
-    from . import ops
-    feat, counts = ops.clip_features(clips, sample_rate)
+    from . import dsp
+    feat, counts = dsp.clip_features(clips, sample_rate)
     label = counts[:, 3].to(torch.int64)
     cls = torch.where(label == SPEECH, 0, 1)
     cls = torch.where(feat[:, FEATURES.index("rms")] < threshold, 2, cls)
@@ -366,14 +366,15 @@ def segment_recording(waveform, orig_freq=None, device="cuda", segment_s=1.0):
     resampled to 16 kHz by the package's resampler (ops.resample on the device, its host restatement on the CPU), scaled by 0.99 / max|x|
     over the whole recording (wm_absmax_rows on the device; an all-zero recording stays zero, where the reference divides by zero), cut
     into whole segments; the remainder is dropped."""
-    from . import inference, ops
+    from . import dsp, inference
+    from ._lib import lib
     from .inference import SAMPLE_RATE
     if isinstance(waveform, (str, os.PathLike)):
         waveform, rate = inference.read_audio(os.fspath(waveform))
         orig_freq = rate if orig_freq is None else orig_freq
     if orig_freq is None:
         raise ValueError("orig_freq: the rate of a tensor has to be given")
-    rate = ops._rate(orig_freq, "orig_freq")
+    rate = dsp._rate(orig_freq, "orig_freq")
     seg = int(round(float(segment_s) * SAMPLE_RATE))
     if seg < 1:
         raise ValueError(f"segment_s: expected a positive duration, got {segment_s!r}")
@@ -383,13 +384,13 @@ def segment_recording(waveform, orig_freq=None, device="cuda", segment_s=1.0):
         return torch.empty(0, 1, seg, device=dev)
     if dev.type == "cuda":
         if rate != SAMPLE_RATE:
-            mono = ops.resample(x, rate, SAMPLE_RATE)                                        # the channel mean and the filter, one launch
+            mono = dsp.resample(x, rate, SAMPLE_RATE)                                        # the channel mean and the filter, one launch
         else:
             mono = x.mean(dim=0, keepdim=True) if x.shape[0] > 1 else x
         head = mono.shape[1] & ~3                                                            # wm_absmax_rows takes rows of whole quads
         peak = torch.zeros(1, device=dev)
         if head:
-            ops.lib.wm_absmax_rows(mono.data_ptr(), 1, head, peak.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            lib.wm_absmax_rows(mono.data_ptr(), 1, head, peak.data_ptr(), torch.cuda.current_stream().cuda_stream)
         if head < mono.shape[1]:
             peak = torch.maximum(peak, mono[0, head:].abs().max())
     else:

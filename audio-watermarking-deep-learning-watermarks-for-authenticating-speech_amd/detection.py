@@ -216,14 +216,14 @@ def evaluate_detection(generator, detector, batches, attacks=None, device="cuda"
     `by_class=True` adds "by_class" to every row: {"speech" | "noise" | "silent": a detection_report over that class's clips alone} (its
     "clips" is the class's count; "deployed" uses the thresholds calibrated on ALL clean clips of the "none" row), the classes being
     curate.clip_classes of the clean batch (one wm_clip_features launch per batch; a clip with a non-finite sample is in none)."""
-    from . import ops
+    from . import dsp
     from .losses import postprocess
     if score not in SCORES:
         raise ValueError(f"score: expected one of {SCORES}, got {score!r}")
     if decode not in DECODES:
         raise ValueError(f"decode: expected one of {DECODES}, got {decode!r}")
     targets = [_rate(t, "fpr_targets") for t in fpr_targets]
-    ops.loc_threshold_logit(threshold)
+    dsp.loc_threshold_logit(threshold)
     attacks = {} if attacks is None else attacks
     if "none" in attacks:
         raise ValueError('attacks: the name "none" is taken by the undistorted row')
@@ -243,7 +243,7 @@ def evaluate_detection(generator, detector, batches, attacks=None, device="cuda"
         both = torch.cat([s + delta, s], dim=0)
         for name, attack in named:
             logits = detector(both if attack is None else attack(both))
-            cs = ops.clip_scores(logits, message, threshold)
+            cs = dsp.clip_scores(logits, message, threshold)
             sc = cs.prob if score == "prob" else cs.votes[:, 0].double() / logits.shape[1]
             acc[name][0].append(sc[:B])
             acc[name][1].append(sc[B:])

@@ -31,10 +31,10 @@ def _resample_rows_host(x, orig_freq, new_freq, length=None):
     """CPU twin of ops.resample_rows: every row of the float32 (rows, N) tensor by itself through the float32 `dense` table as one strided
     F.conv1d per row (a row's samples do not depend on its neighbours or on their number); the first `length` samples of each, all
     ceil(new * N / orig) by default.  Plain torch operations: autograd differentiates it."""
-    from . import ops
-    tab = ops.resample_table(orig_freq, new_freq)
+    from . import dsp
+    tab = dsp.resample_table(orig_freq, new_freq)
     P, width = tab["P"], tab["width"]
-    n = ops.resample_length(x.shape[1], orig_freq, new_freq) if length is None else length
+    n = dsp.resample_length(x.shape[1], orig_freq, new_freq) if length is None else length
     padded = F.pad(x, (width, width + P))
     weight = tab["dense"][:, None, :]
     # (1, Q, N // P + 1): [phase][period] per row
@@ -52,22 +52,22 @@ def resample(waveform, orig_freq, new_freq, mixdown=True):
     (ops.resample_rows on CUDA, the same conv1d per channel on the CPU).
     PARITY WITH TORCHAUDIO UNPINNED: torchaudio is absent from this image; tests/test_resample_cpu.py pins it on the first
     machine that has it."""
-    from . import ops
-    tab = ops.resample_table(orig_freq, new_freq)
+    from . import dsp
+    tab = dsp.resample_table(orig_freq, new_freq)
     if tab["K"] == 1:
         return waveform
     x = _as_channels(waveform)
     if not mixdown:
-        return ops.resample_rows(x, orig_freq, new_freq) if x.is_cuda else _resample_rows_host(x, orig_freq, new_freq)
+        return dsp.resample_rows(x, orig_freq, new_freq) if x.is_cuda else _resample_rows_host(x, orig_freq, new_freq)
     if x.is_cuda:
-        return ops.resample(x, orig_freq, new_freq)
+        return dsp.resample(x, orig_freq, new_freq)
     # channels added in float64, one rounding to float32 (as the kernel does): the mean's error is an ulp of the mean, also where channels cancel
     mono = x.double().mean(dim=0, keepdim=True).float() if x.shape[0] > 1 else x
     P, Q, width = tab["P"], tab["Q"], tab["width"]
     n = mono.shape[1]
     padded = F.pad(mono, (width, width + P))
     y = F.conv1d(padded[None], tab["dense"][:, None, :], stride=P)                 # (1, Q, n // P + 1): [phase][period]
-    return y.transpose(1, 2).reshape(1, -1)[:, :ops.resample_length(n, orig_freq, new_freq)].contiguous()
+    return y.transpose(1, 2).reshape(1, -1)[:, :dsp.resample_length(n, orig_freq, new_freq)].contiguous()
 
 
 class Resample(torch.nn.Module):
@@ -75,8 +75,8 @@ class Resample(torch.nn.Module):
 
     def __init__(self, orig_freq=SAMPLE_RATE, new_freq=SAMPLE_RATE):
         super().__init__()
-        from . import ops
-        ops.resample_table(orig_freq, new_freq)          # bad rates fail here, as torchaudio's constructor does
+        from . import dsp
+        dsp.resample_table(orig_freq, new_freq)          # bad rates fail here, as torchaudio's constructor does
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
 
     def forward(self, waveform):
@@ -89,17 +89,17 @@ def resample_add(x, delta, orig_freq, delta_freq=SAMPLE_RATE):
     lies behind them is ignored.  Returns (out (C, N), up (1, N)): up is resample(delta[:n_d], delta_freq, orig_freq)[:, :N] and
     out[c] = x[c] + up[0].  CUDA tensors go to the HIP kernel (ops.resample_add, one launch); CPU tensors through the CPU twin of
     `resample` and one add."""
-    from . import ops
-    ops.resample_table(delta_freq, orig_freq)                        # bad rates fail here
+    from . import dsp
+    dsp.resample_table(delta_freq, orig_freq)                        # bad rates fail here
     x = _as_channels(x)
     if not isinstance(delta, torch.Tensor):
         raise TypeError(f"delta: expected a tensor, got {type(delta).__name__}")
     n = x.shape[1]
-    n_d = ops.resample_length(n, orig_freq, delta_freq)
+    n_d = dsp.resample_length(n, orig_freq, delta_freq)
     if delta.numel() < n_d:
         raise ValueError(f"delta: {n} samples at {orig_freq} Hz need {n_d} at {delta_freq} Hz, got {delta.numel()}")
     if x.is_cuda:
-        return ops.resample_add(x.contiguous(), delta.to(torch.float32).contiguous(), orig_freq, delta_freq)
+        return dsp.resample_add(x.contiguous(), delta.to(torch.float32).contiguous(), orig_freq, delta_freq)
     d = delta.to(torch.float32).reshape(1, -1)[:, :n_d]
     up = resample(d, delta_freq, orig_freq)[:, :n]
     up = up.clone() if up.data_ptr() == delta.data_ptr() else up.contiguous()     # equal rates hand delta itself back: never a view of it
@@ -270,10 +270,10 @@ def _ingest(waveform, orig_freq, device, seg_len=SAMPLE_RATE):
     if orig_freq is None or int(orig_freq) == seg_len:
         segs, remainder = _segments(waveform.float(), seg_len)
         return segs, remainder, waveform
-    from . import ops
+    from . import dsp
     x = _as_channels(waveform).to(device)
-    segs = ops.resample(x, orig_freq, seg_len, seg_len=seg_len)
-    n = ops.resample_length(x.shape[1], orig_freq, seg_len)
+    segs = dsp.resample(x, orig_freq, seg_len, seg_len=seg_len)
+    n = dsp.resample_length(x.shape[1], orig_freq, seg_len)
     return segs, n % seg_len, segs.reshape(1, -1)[:, :n]
 
 
@@ -329,11 +329,11 @@ def _embed_native(waveform, generator, message_bits, device, messages, max_batch
     The segments come from the launch _ingest uses for a recording that is not at 16 kHz, called here directly: _ingest cuts a 16 kHz
     waveform on the host without a mixdown (the old call, which must not change) and does not hand back the uploaded (C, N) channels that
     wm_resample_add adds delta to."""
-    from . import ops
-    rate = seg_len if orig_freq is None else ops._rate(orig_freq, "orig_freq")
+    from . import dsp
+    rate = seg_len if orig_freq is None else dsp._rate(orig_freq, "orig_freq")
     original = _as_channels(waveform)
     x = original.to(device).contiguous()
-    segs = ops.resample(x, rate, seg_len, seg_len=seg_len)           # (S, 1, seg_len): mixdown (+ resampling) + tail padding, one launch
+    segs = dsp.resample(x, rate, seg_len, seg_len=seg_len)           # (S, 1, seg_len): mixdown (+ resampling) + tail padding, one launch
     S = segs.shape[0]
     if S == 0:
         original = original.cpu()
@@ -343,7 +343,7 @@ def _embed_native(waveform, generator, message_bits, device, messages, max_batch
     delta = torch.empty_like(segs)
     for i in range(0, S, max_batch):
         delta[i:i + max_batch] = generator(segs[i:i + max_batch], messages[i:i + max_batch].to(device))
-    wm, up = ops.resample_add(x, delta, rate, seg_len)               # Nd = n16: the generator's output for the zero tail is not read
+    wm, up = dsp.resample_add(x, delta, rate, seg_len)               # Nd = n16: the generator's output for the zero tail is not read
     return wm.cpu(), up.cpu(), original.cpu()
 
 
@@ -385,8 +385,8 @@ def generate_watermarked_audio(input_file, generator, output_file=None, message_
 
 def _stoi_whole(original, processed, rate, device):
     """STOI of a whole (C, N) recording against its original, every channel as one row (the long-row path of wm_stoi), mean over channels"""
-    from . import ops
-    d, _ = ops.stoi(_as_channels(original).to(device), _as_channels(processed).to(device), rate)
+    from . import dsp
+    d, _ = dsp.stoi(_as_channels(original).to(device), _as_channels(processed).to(device), rate)
     return float(d.double().mean())
 
 
@@ -462,11 +462,11 @@ def locate_watermark(waveform_or_path, detector, threshold=0.5, min_len_s=0.02, 
     (merge_short_runs).  A path is read by load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz
     (see _ingest; the intervals are then in seconds all the same).  The shipped checkpoints were never trained to localise: what
     this returns for a spliced recording is whatever attacks.evaluate_localization measures, not a promise."""
-    from . import ops
+    from . import dsp
     from .attacks import unpack_labels
     if isinstance(min_len_s, bool) or not isinstance(min_len_s, (int, float)) or not math.isfinite(min_len_s) or min_len_s < 0:
         raise ValueError(f"min_len_s: expected a non-negative number of seconds, got {min_len_s!r}")
-    ops.loc_threshold_logit(threshold)                                  # a bad threshold fails here
+    dsp.loc_threshold_logit(threshold)                                  # a bad threshold fails here
     if isinstance(waveform_or_path, (str, os.PathLike)):
         waveform, orig_freq = load_audio(waveform_or_path), None
     else:
@@ -479,7 +479,7 @@ def locate_watermark(waveform_or_path, detector, threshold=0.5, min_len_s=0.02, 
     masks = []
     for i in range(0, S, max_batch):
         logits = detector(segs[i:i + max_batch].to(device))            # [s,T,1+bits]: stays on the device
-        masks.append(ops.loc_counts(logits, None, threshold, want_pred=True)[1])
+        masks.append(dsp.loc_counts(logits, None, threshold, want_pred=True)[1])
     pred = unpack_labels(torch.cat(masks, dim=0), T).reshape(-1)[:n]
     out = {"watermarked": [], "unmarked": [], "fraction_watermarked": float(pred.mean())}
     for a, b, v in merge_short_runs(pred, min_len_s * SAMPLE_RATE):
@@ -557,9 +557,9 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
     out = torch.stack([torch.cat(v).double().mean() for v in (clean, wm, si, rms)]).cpu()
     res = tuple(float(v) for v in out)
     if stoi:
-        from . import ops
+        from . import dsp
         n = (S - 1) * segs.shape[2] + (remainder if remainder else segs.shape[2])     # the recording without the last segment's padding
-        d, _ = ops.stoi(segs.to(device).reshape(1, -1)[:, :n], whole.reshape(1, -1)[:, :n], SAMPLE_RATE)
+        d, _ = dsp.stoi(segs.to(device).reshape(1, -1)[:, :n], whole.reshape(1, -1)[:, :n], SAMPLE_RATE)
         res += (float(d[0]),)
     return res
 

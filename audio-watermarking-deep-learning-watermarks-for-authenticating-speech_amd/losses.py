@@ -6,7 +6,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import dsp, ops
 
 SAMPLE_RATE = 16000      # py/main16.py:30
 MAX_RMS = 0.005          # py/main16.py:29
@@ -110,7 +110,7 @@ def detection_losses_masked(logits, message, labels):
     """(loc_loss, bce) against per-sample labels: `labels` is the (B, ceil(T / 32)) int32 bit mask "still watermarked" of the watermarked
     half (attacks.Splice's second output), the clean half has target 0.  loc averages over all 2B * T samples; bce over the samples whose
     label is 1, since the message can only be decoded where the watermark still is (ops.MaskedBCEFn)."""
-    return ops.MaskedBCEFn.apply(logits, message, labels)
+    return dsp.MaskedBCEFn.apply(logits, message, labels)
 
 
 def detect_with_losses(detector, x, message, input_grad_rows=None):

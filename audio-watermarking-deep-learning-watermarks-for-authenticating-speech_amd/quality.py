@@ -73,8 +73,8 @@ def stoi(reference, processed, sample_rate=16000):
     leading shape ((B,), (C,) or a 0-d tensor), float32 on the inputs' device.  CUDA tensors run wm_stoi (one resampling launch first unless
     the rate is 10 kHz); CPU tensors run the float64 host restatement.  A row with fewer than 30 spectral frames (under 4097 samples at
     10 kHz, or mostly silence) scores the published sentinel 1e-5; a row with a non-finite sample scores NaN."""
-    from . import ops
-    d, _ = ops.stoi(reference, processed, sample_rate)
+    from . import dsp
+    d, _ = dsp.stoi(reference, processed, sample_rate)
     lead = tuple(reference.shape[:-2]) if reference.dim() == 3 else tuple(reference.shape[:-1])
     return d.reshape(lead)
 

@@ -1,4 +1,4 @@
-"""Host side of the biquad / 16-bit PCM codec path (no GPU): the coefficient and warm-up helpers of ops.py, the CPU twins of
+"""Host side of the biquad / 16-bit PCM codec path (no GPU): the coefficient and warm-up helpers of dsp.py, the CPU twins of
 perceptual_postprocess and encode_pcm16, save_audio's unchanged host path, and the adjoint formula the straight-through backward uses."""
 import math
 import wave

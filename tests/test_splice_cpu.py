@@ -225,7 +225,7 @@ def test_argument_validation():
 # ------------------------------------------------------------------------------------------ 7. tamper=None is the call as it was
 def test_forward_losses_without_tamper_does_not_touch_the_new_code(monkeypatch):
     import awm_amd
-    from awm_amd import losses as L, ops, step
+    from awm_amd import dsp, losses as L, ops, step
     calls = []
 
     def forbidden(name):
@@ -256,6 +256,7 @@ def test_forward_losses_without_tamper_does_not_touch_the_new_code(monkeypatch):
     monkeypatch.setattr(ops.SpliceFn, "apply", forbidden("ops.SpliceFn"))
     monkeypatch.setattr(ops.MaskedBCEFn, "apply", forbidden("ops.MaskedBCEFn"))
     monkeypatch.setattr(ops, "loc_counts", forbidden("ops.loc_counts"))
+    monkeypatch.setattr(dsp, "loc_counts", forbidden("dsp.loc_counts"))      # the module the package reads it from
     monkeypatch.setattr(L, "detection_losses_masked", forbidden("detection_losses_masked"))
     s, msg = torch.randn(2, 1, 64), torch.tensor([1, 2])
     gen = lambda s, m: 0.01 * s
