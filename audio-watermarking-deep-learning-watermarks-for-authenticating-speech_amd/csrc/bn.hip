@@ -117,14 +117,19 @@ __global__ __launch_bounds__(256) void bn_add_relu_kernel(const float* __restric
 // dz = g * (out > 0);  partial[b][0][c] = sum dz, partial[b][1][c] = sum dz*y   (row = b*64+c).  MASK: the sign bits written by
 // bn_add_relu_kernel<true> stand in for `out` (a 16.4 MB frame pass per clip less).  WRITE = false: the sums only -- the fused
 // convolution-backward kernels re-apply the mask to g while loading it, so dz is never materialised (another frame pass less).
-template <bool MASK, bool WRITE>
+// R1: the gradient is the rank-one frame g[b][c][t] = w[c] g1[b][t] of the Conv1d(64, 1, 1) head (head1_bwd_kernel's dx), formed
+// here from the clip's row g1 [B][T] (g points at it) and the 64 weights with the one multiply that kernel performs: same thread <->
+// element map, same sums -- the frame itself is never read.
+template <bool MASK, bool WRITE, bool R1 = false>
 __global__ __launch_bounds__(256) void relu_bwd_reduce_kernel(const float* __restrict__ g, const float* __restrict__ out,
                                                               const unsigned* __restrict__ mask,
                                                               const float* __restrict__ y, float* __restrict__ dz,
-                                                              float* __restrict__ partial, float* __restrict__ dzmax, int T4) {
+                                                              float* __restrict__ partial, float* __restrict__ dzmax, int T4,
+                                                              const float* __restrict__ w = nullptr) {
     __shared__ float scratch[8];
     const int row = blockIdx.x, b = row >> 6, c = row & 63;
-    const float4* gr = reinterpret_cast<const float4*>(g) + (size_t)row * T4;
+    const float4* gr = reinterpret_cast<const float4*>(g) + (size_t)(R1 ? b : row) * T4;
+    const float wc = R1 ? w[c] : 1.f;
     const float4* orow = MASK ? nullptr : reinterpret_cast<const float4*>(out) + (size_t)row * T4;
     const float4* yr = reinterpret_cast<const float4*>(y) + (size_t)row * T4;
     float4* dr = WRITE ? reinterpret_cast<float4*>(dz) + (size_t)row * T4 : nullptr;
@@ -146,7 +151,9 @@ __global__ __launch_bounds__(256) void relu_bwd_reduce_kernel(const float* __res
         for (int k = 0; k < U; ++k) {
             const int i = base + k * 256 + (int)threadIdx.x;
             if (i >= T4) continue;
-            const float4 gg = gq[k], yy = yq[k];
+            float4 gg = gq[k];
+            const float4 yy = yq[k];
+            if (R1) { gg.x = __fmul_rn(wc, gg.x); gg.y = __fmul_rn(wc, gg.y); gg.z = __fmul_rn(wc, gg.z); gg.w = __fmul_rn(wc, gg.w); }
             bool p0, p1, p2, p3;
             if (MASK) {
                 const unsigned m = mq[k] >> (4 * (i & 7));
@@ -381,6 +388,17 @@ int wm_relu_bwd_reduce_mask(const float* g, const void* mask, const float* y2, f
     else
         hipLaunchKernelGGL((relu_bwd_reduce_kernel<true, false>), dim3(B * 64), dim3(256), 0, stream, g, (const float*)nullptr,
                            reinterpret_cast<const unsigned*>(mask), y2, (float*)nullptr, partial, dzmax, T / 4);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// wm_relu_bwd_reduce_mask(dz = NULL) for the gradient behind the Conv1d(64, 1, 1) head: g[b][c][t] = w[c] g1[b][t] is formed on load
+// from g1 [B][T] and w [64] (wm_head1_bwd's dx, which then need not exist); partial and dzmax bit for bit the frame route's.
+int wm_relu_bwd_reduce_mask_r1(const float* g1, const float* w, const void* mask, const float* y2, float* partial, float* dzmax, int B,
+                               int T, hipStream_t stream) {
+    if ((T & 3) || B <= 0 || !g1 || !w || !mask || !y2 || !partial) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((relu_bwd_reduce_kernel<true, false, true>), dim3(B * 64), dim3(256), 0, stream, g1, (const float*)nullptr,
+                       reinterpret_cast<const unsigned*>(mask), y2, (float*)nullptr, partial, dzmax, T / 4, w);
     WM_CHECK_LAUNCH();
     return 0;
 }

@@ -36,6 +36,7 @@ struct DWArgs {
     const float* gscale;                                // H (f16 two-piece split): {gs, 1 / gs}, the power-of-two scale of the rebuilt
                                                         // gradient (wm_bn_bwd_finalize); the weight image carries its own scale
     float* dzmax;                                       // H, epi 1 / 2 / 8: max |y| per workgroup [grid] (sizes the NEXT launch's scale)
+    const float* g1; const float* hw;                   // R1: the rank-one frame w[c] g1[b][t] that stands in for g (conv2 pair) / e1 (conv1 pair)
 };
 
 // H = false: bf16 three-piece split, six piece products per product (bf16x6).  H = true: f16 TWO-piece split (hi = RNE_f16(x s),
@@ -44,9 +45,16 @@ struct DWArgs {
 // max |w|, stored behind the image), the gradient's (gs from wm_bn_bwd_finalize: max |A| max |dz| -> 2^9, applied through the
 // BatchNorm-backward constants, i.e. for free; the rebuilt value is clamped to +-6e4 so that a pathological element saturates
 // instead of becoming an infinity); activations need none.  Results are unscaled in the epilogue / at the slab write.
-template <int EPI, int XPRO, bool GM, bool H>
+// R1 (GM, H; the block in front of the Conv1d(64, 1, 1) head): the gradient that reaches the block output is the rank-one frame
+// hw[c] g1[b][t] (head1_bwd_kernel's dx).  It is not read from memory but formed from the clip's row g1 [B][T] and the 64 weights with
+// that kernel's one multiply, in front of the mask AND: as the gradient operand g (conv2 pair: one dwordx4 of g1 per unit instead of
+// one per channel and unit) / as the epilogue addend e1 (conv1 pair: one dwordx4 of g1 per lane instead of four row fetches).
+template <int EPI, int XPRO, bool GM, bool H, bool R1 = false>
 __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     static_assert((EPI == EPI_RELUMASK && XPRO == PRO_BNRELU) || ((EPI == EPI_ADD || EPI == EPI_ADDSTATS) && XPRO == PRO_NONE), "conv2 pair or conv1 pair");
+    static_assert(!R1 || (GM && H && (EPI == EPI_RELUMASK || EPI == EPI_ADD)), "rank-one gradient: masked on load, f16 build");
+    constexpr bool R1G = R1 && EPI == EPI_RELUMASK, R1E = R1 && EPI == EPI_ADD;     // ... as g / as e1
+    constexpr int NCS = R1 ? 9 : 8;                        // rows of Cs: R1 adds the head's weights
     constexpr int KW = 3, NT = 64, NP = H ? 2 : 3, ROWS = NT + 2, PITCH = 72, PG = 72, PX = 88, XO = 8;
     constexpr int NPR = H ? 3 : 6, SPM = 6 / NPR;          // piece products per product; side-work slices per MFMA
     constexpr bool STATS = (EPI == EPI_RELUMASK || EPI == EPI_ADDSTATS);
@@ -56,14 +64,14 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     unsigned short* Db = reinterpret_cast<unsigned short*>(smem_raw);          // [NP][ROWS][PITCH]   row r = time t0 - 1 + r
     unsigned short* Gb0 = Db + DIMG;                                           // [2][NP][64][PG]
     unsigned short* Xb0 = Gb0 + 2 * GIMG;                                      // [2][NP][64][PX]     element XO + (t - t0)
-    float* Cs = reinterpret_cast<float*>(Xb0 + 2 * XIMG);                      // [8][64]
+    float* Cs = reinterpret_cast<float*>(Xb0 + 2 * XIMG);                      // [NCS][64]
     // H: a wave-private [32 channels][32 steps (+4)] exchange tile.  In the accumulator layout a lane owns one channel, so a dwordx4
     // access touches 32 rows with 16 bytes each; such a store (load) holds the wave at issue for ~300 cycles (measured: the four
     // epilogue stores were 1 200 of a tile's 7 000 cycles).  Epilogue operands and results therefore cross HBM in ROW layout (a lane
     // = 4 steps, 8 lanes = one 128-byte row segment, 8 rows per instruction) and change layout through this tile.
     constexpr bool XL = H;
     constexpr int EXP = 36;
-    float* Ex = Cs + 8 * 64 + (threadIdx.x >> 6) * (32 * EXP);
+    float* Ex = Cs + NCS * 64 + (threadIdx.x >> 6) * (32 * EXP);
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mt = wave & 1, nh = wave >> 1;           // data gradient: 32 output rows x 32 columns; weight gradient: block (mt, nt = nh)
@@ -99,6 +107,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     float hg = 0.f, hy = 0.f, hxv = 0.f;
     wm_srd_t dsg = make_srd(a.g, 0), dsy = dsg, dsx = dsg, dsm = dsg;
     unsigned voff = 0, hoff = 0;
+    unsigned voffr = 0, hoffr = 0;                       // R1G: the same places in the clip's row of g1
     bool okh = true;
     constexpr bool GMG = GM && EPI == EPI_RELUMASK;      // the mask belongs to the gradient operand g (else, with GM, to e1)
     unsigned mk_[2][2] = {{0u, 0u}, {0u, 0u}}, hmk = 0u; // mask dwords of (unit, channel) / of the halo step, as loaded
@@ -107,13 +116,17 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     auto set_tile = [&](int tile) {
         const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
         const size_t clip = (size_t)b * 64 * T, bytes = (size_t)64 * T * sizeof(float);
-        dsg = make_srd(a.g + clip, bytes);
+        dsg = R1G ? make_srd(a.g1 + (size_t)b * T, (size_t)T * sizeof(float)) : make_srd(a.g + clip, bytes);
         dsy = make_srd(a.g2 + clip, bytes);
         dsx = make_srd(a.x + clip, bytes);
         voff = (unsigned)(c0 * T + t0 + 4 * q0) * 4u;
         const int th = hh ? t0 + NT : t0 - 1;
         hoff = (unsigned)(hc * T + min(max(th, 0), T - 1)) * 4u;
         okh = th >= 0 && th < T;
+        if (R1G) {
+            voffr = (unsigned)(t0 + 4 * q0) * 4u;
+            hoffr = (unsigned)min(max(th, 0), T - 1) * 4u;
+        }
         if (GMG) {
             dsm = make_srd(reinterpret_cast<const float*>(a.gmask) + (size_t)b * 64 * nwm, (size_t)64 * nwm * sizeof(unsigned));
             voffm = ((unsigned)c0 * nwm + ((unsigned)t0 >> 5)) * 4u;
@@ -124,8 +137,11 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     };
     const unsigned rowT = (unsigned)T * 4u;
     auto load_g = [&](int u) {
-        ra_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, 0u));
-        rb_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, rowT));
+        if (R1G) ra_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voffr + 128u * u, 0u));     // both channels' g1 quad; rb_ unused
+        else {
+            ra_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, 0u));
+            rb_[u] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u * u, rowT));
+        }
         ya_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, 0u));
         yb_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, rowT));
     };
@@ -138,12 +154,13 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     // whenever the CU's miss queue is full, a different wave every tile -- measured as 430 of 8 250 cycles per tile spent at the
     // phase-A barrier waiting for whichever wave was hit.
     auto refillA = [&](int m) {                     // phase-A slice m
-        if (m == 14) ra_[0] = __builtin_bit_cast(float4, buf_load4(dsg, voff, 0u));
-        if (m == 20) rb_[0] = __builtin_bit_cast(float4, buf_load4(dsg, voff, rowT));
+        // (R1G: ra_[u] serves both channels of unit u -- last read by slice 12 / 30 -- and the rb_ slots stay empty)
+        if (m == 14) ra_[0] = __builtin_bit_cast(float4, R1G ? buf_load4(dsg, voffr, 0u) : buf_load4(dsg, voff, 0u));
+        if (m == 20 && !R1G) rb_[0] = __builtin_bit_cast(float4, buf_load4(dsg, voff, rowT));
         if (m == 26) ya_[0] = __builtin_bit_cast(float4, buf_load4(dsy, voff, 0u));
         if (m == 32) yb_[0] = __builtin_bit_cast(float4, buf_load4(dsy, voff, rowT));
-        if (m == 38) ra_[1] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u, 0u));
-        if (m == 44) rb_[1] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u, rowT));
+        if (m == 38) ra_[1] = __builtin_bit_cast(float4, R1G ? buf_load4(dsg, voffr + 128u, 0u) : buf_load4(dsg, voff + 128u, 0u));
+        if (m == 44 && !R1G) rb_[1] = __builtin_bit_cast(float4, buf_load4(dsg, voff + 128u, rowT));
         if (m == 50) ya_[1] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u, 0u));
         if (m == 56) yb_[1] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u, rowT));
         if (GMG) {
@@ -160,7 +177,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         if (v == 19) xb_[1] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u, rowT));
     };
     auto load_ghalo = [&]() {
-        hg = buf_load(dsg, hoff, 0u); hy = buf_load(dsy, hoff, 0u);
+        hg = buf_load(dsg, R1G ? hoffr : hoff, 0u); hy = buf_load(dsy, hoff, 0u);
         if (GMG) hmk = __builtin_bit_cast(unsigned, buf_load(dsm, hoffm, 0u));
     };
     auto load_gmask = [&](int u) {
@@ -185,6 +202,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         Cs[320 + tid] = (XPRO == PRO_BNRELU) ? a.xb[tid] : 0.f;
         Cs[384 + tid] = (EPI == EPI_RELUMASK) ? a.ea[tid] : 0.f;
         Cs[448 + tid] = (EPI == EPI_RELUMASK) ? a.eb[tid] : 0.f;
+        if (R1) Cs[512 + tid] = a.hw[tid];
     }
     // the element right of the right halo only feeds bits that the funnel shift drops: keep it defined in both images
     for (int i = tid; i < 2 * NP * 64; i += 256) Xb0[(i / (NP * 64)) * XIMG + (i % (NP * 64)) * PX + XO + NT + 1] = 0;
@@ -196,6 +214,8 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         kga[j] = Cs[c0 + j] * gs; kgb[j] = Cs[64 + c0 + j] * gs; kgc[j] = Cs[128 + c0 + j] * gs; kgl[j] = Cs[192 + c0 + j] * gs;   // gs = 1 | 2^k: exact
         kxa[j] = Cs[256 + c0 + j]; kxb[j] = Cs[320 + c0 + j];
     }
+    // R1G: the head's weights of the staging channels / of the halo channel
+    const float kw[2] = {R1G ? Cs[512 + c0] : 0.f, R1G ? Cs[512 + c0 + 1] : 0.f}, khw = R1G ? Cs[512 + hc] : 0.f;
     const float hga = Cs[hc] * gs, hgb = Cs[64 + hc] * gs, hgc = Cs[128 + hc] * gs, hgl = Cs[192 + hc] * gs, hxa = Cs[256 + hc], hxb = Cs[320 + hc];
 
     // ---- split stages on a value pair (va, vb) -> pieces (p0, p1, [lo]) and a second pair (vc, vd) -> (q0_, q1_, [lo])
@@ -256,10 +276,11 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     // gradient rebuild of channel j of unit u from the raw staging registers (free for the refill afterwards): one value per slice
     // (a slice must stay within the shadow of one MFMA, about seven instructions: a twelve-instruction slice costs its excess in full)
     auto g_build = [&](int u, int j, int e) {
-        const float4 dz = j ? rb_[u] : ra_[u], yy = j ? yb_[u] : ya_[u];
+        const float4 dz = (j && !R1G) ? rb_[u] : ra_[u], yy = j ? yb_[u] : ya_[u];
         float4& gz = gz_;
         float d = (e == 0) ? dz.x : (e == 1) ? dz.y : (e == 2) ? dz.z : dz.w;
         const float yv = (e == 0) ? yy.x : (e == 1) ? yy.y : (e == 2) ? yy.z : yy.w;
+        if (R1G) d = __fmul_rn(kw[j], d);   // the frame element, rounded once as head1_bwd_kernel rounds it
         if (GMG) {                          // dz = g_out where the block output was positive: its bit, sign-extended, ANDed in
             if (e == 0) mk_[u][j] >>= 4 * q0;
             d = __uint_as_float(__float_as_uint(d) & (unsigned)__builtin_amdgcn_sbfe((int)mk_[u][j], e, 1));
@@ -315,8 +336,8 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         }
     };
     auto hg_pick = [&]() {
-        float hgm = hg;
-        if (GMG) hgm = __uint_as_float(__float_as_uint(hg) & (unsigned)__builtin_amdgcn_sbfe((int)(hmk >> hsh_cur), 0, 1));
+        float hgm = R1G ? __fmul_rn(khw, hg) : hg;
+        if (GMG) hgm = __uint_as_float(__float_as_uint(hgm) & (unsigned)__builtin_amdgcn_sbfe((int)(hmk >> hsh_cur), 0, 1));
         float v = pro_apply<PRO_BNBWD>(hgm, hy, hga, hgb, hgc, hgl);
         if (H) v = __builtin_amdgcn_fmed3f(v, -6.0e4f, 6.0e4f);
         va = okh_cur ? v : 0.f; vb = 0.f;
@@ -412,12 +433,13 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     f32x4 e1n[4];
     unsigned emk = 0u, pmk = 0u, emkn = 0u, pmkn = 0u;
     f32x4 pyq[FOLD ? 4 : 1], pyn[FOLD ? 4 : 1];
-    f32x4 ec[XL ? 4 : 1], pyc[(XL && FOLD) ? 4 : 1];     // row-layout staging of the next tile's epilogue operands
+    f32x4 ec[(XL && !R1E) ? 4 : 1], pyc[(XL && FOLD) ? 4 : 1];     // row-layout staging of the next tile's epilogue operands (R1E: g1)
     const int xrow = lane >> 3, xcol = 4 * (lane & 7);       // row layout: lane -> (row xrow + 8 r, steps xcol .. xcol + 3)
     const unsigned xlane = (unsigned)(xrow * T + xcol) * 4u;
     unsigned row8T[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) row8T[r] = (unsigned)(8 * r * T) * 4u;
+    const float kwa = R1E ? Cs[512 + 32 * mt + l31] : 0.f;     // the head's weight of the lane's accumulator channel
     const float kea = (EPI == EPI_RELUMASK) ? Cs[384 + 32 * mt + l31] : 0.f, keb = (EPI == EPI_RELUMASK) ? Cs[448 + 32 * mt + l31] : 0.f;
     int buf = 0;
 #ifdef WM_STAMP
@@ -427,9 +449,18 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         const int b0 = tile / tilesPerClip, t00 = (tile - b0 * tilesPerClip) * NT;
         const size_t slab0 = ((size_t)b0 * 64 + 32 * mt) * T;
         const unsigned eo0 = (unsigned)(l31 * T + t00 + 32 * nh + 4 * half) * 4u, mo0 = ((unsigned)l31 * nwm + ((unsigned)t00 >> 5) + (unsigned)nh) * 4u;
-        const wm_srd_t s0 = make_srd(a.e1 + slab0, (size_t)32 * T * sizeof(float));
+        const wm_srd_t s0 = R1E ? make_srd(a.g1 + (size_t)b0 * T, (size_t)T * sizeof(float)) : make_srd(a.e1 + slab0, (size_t)32 * T * sizeof(float));
+        if (R1E) {                                       // the lane's channel times the clip's row, in the accumulator layout
+            const unsigned go0 = (unsigned)(t00 + 32 * nh + 4 * half) * 4u;
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) e1q[q4] = buf_load4(s0, eo0 + 32u * q4, 0u);
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const f32x4 gq = buf_load4(s0, go0 + 32u * q4, 0u);
+                e1q[q4] = f32x4{__fmul_rn(kwa, gq[0]), __fmul_rn(kwa, gq[1]), __fmul_rn(kwa, gq[2]), __fmul_rn(kwa, gq[3])};
+            }
+        } else {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) e1q[q4] = buf_load4(s0, eo0 + 32u * q4, 0u);
+        }
         if (GM && (EPI == EPI_ADD || EPI == EPI_ADDSTATS))
             emk = __builtin_bit_cast(unsigned, buf_load(make_srd(reinterpret_cast<const float*>(a.gmask) + ((size_t)b0 * 64 + 32 * mt) * nwm,
                                                                  (size_t)32 * nwm * sizeof(unsigned)), mo0, 0u));
@@ -465,10 +496,11 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         // data-gradient output / epilogue operand of this lane: channel 32 mt + l31, steps t0 + 32 nh + 8 q + 4 half + (0..3) for quad q
         const size_t slab = ((size_t)b * 64 + 32 * mt) * T;
         const wm_srd_t sye = make_srd(a.y + slab, (size_t)32 * T * sizeof(float));
-        const wm_srd_t se1 = make_srd(a.e1 + slab, (size_t)32 * T * sizeof(float));
+        const wm_srd_t se1 = R1E ? make_srd(a.g1 + (size_t)b * T, (size_t)T * sizeof(float)) : make_srd(a.e1 + slab, (size_t)32 * T * sizeof(float));
         const unsigned eoff = (unsigned)(l31 * T + t0 + 32 * nh + 4 * half) * 4u;
         const int tnx = min(tile + tstep, ntiles - 1), bnx = tnx / tilesPerClip, t0nx = (tnx - bnx * tilesPerClip) * NT;
-        const wm_srd_t se1n = EAHEAD ? make_srd(a.e1 + ((size_t)bnx * 64 + 32 * mt) * T, (size_t)32 * T * sizeof(float)) : se1;
+        const wm_srd_t se1n = R1E ? make_srd(a.g1 + (size_t)bnx * T, (size_t)T * sizeof(float))
+                                  : EAHEAD ? make_srd(a.e1 + ((size_t)bnx * 64 + 32 * mt) * T, (size_t)32 * T * sizeof(float)) : se1;
         const unsigned eoffn = (unsigned)(l31 * T + t0nx + 32 * nh + 4 * half) * 4u;
         // GM, conv1 pair: e1 is the gradient that reaches the block output; its ReLU bits: dword t0 / 32 + nh of the lane's row
         constexpr bool GME = GM && (EPI == EPI_ADD || EPI == EPI_ADDSTATS);
@@ -484,6 +516,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         const wm_srd_t smen = GME ? make_srd(reinterpret_cast<const float*>(a.gmask) + ((size_t)bnx * 64 + 32 * mt) * nwm,
                                              (size_t)32 * nwm * sizeof(unsigned)) : se1;
         const unsigned emoffn = ((unsigned)l31 * nwm + ((unsigned)t0nx >> 5) + (unsigned)nh) * 4u;
+        const unsigned goffn = (unsigned)(t0nx + 32 * nh + xcol) * 4u;        // R1E: the lane's four steps in the next tile's row of g1
         const unsigned xoffn = xlane + (unsigned)(t0nx + 32 * nh) * 4u, xoff = xlane + (unsigned)(t0 + 32 * nh) * 4u;
 
         STAMP(ts0);
@@ -516,7 +549,8 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
 #pragma unroll
                     for (int i_ = 0; i_ < SPM; ++i_) {
                         const int m = (s * NPR + j) * SPM + i_;          // 0..71
-                        if (XL && m < 8 && (m & 1)) ec[m >> 1] = buf_load4(se1n, xoffn, row8T[m >> 1]);
+                        if (R1E) { if (m == 1) ec[0] = buf_load4(se1n, goffn, 0u); }
+                        else if (XL && m < 8 && (m & 1)) ec[m >> 1] = buf_load4(se1n, xoffn, row8T[m >> 1]);
                         if (XL && FOLD && m >= 8 && m < 16 && (m & 1)) pyc[(m - 8) >> 1] = buf_load4(spyn, xoffn, row8T[(m - 8) >> 1]);
                         if (m < NSA) {
                             sideA(m, Gn, Xn); refillA(m);
@@ -624,11 +658,26 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
                     if (v < 2 * NSB) {
                         if ((v & 1) == 0) sideB(v >> 1); else refillB(v);
                         if (XL) {       // the next tile's epilogue operands: row layout -> exchange tile -> accumulator layout
-                            if (v == 3) {
+                            if (R1E) {
+                                // every channel's row of the frame is the clip's row of g1 times that channel's weight: the 32 steps go
+                                // through the exchange tile once (eight copies, rows 0..7: lanes 8 apart fetched the same quad), a lane reads
+                                // its four quads from row l31 % 8 and multiplies by its own channel's weight, two quads per slice
+                                if (v == 3) *reinterpret_cast<f32x4*>(Ex + xrow * EXP + xcol) = ec[0];
+                                if (v == 5) {
+#pragma unroll
+                                    for (int q4 = 0; q4 < 4; ++q4) e1n[q4] = *reinterpret_cast<const f32x4*>(Ex + (l31 & 7) * EXP + 8 * q4 + 4 * half);
+                                }
+                                if (v == 9 || v == 11) {
+#pragma unroll
+                                    for (int q4 = v - 9; q4 < v - 7; ++q4)
+                                        e1n[q4] = f32x4{__fmul_rn(kwa, e1n[q4][0]), __fmul_rn(kwa, e1n[q4][1]), __fmul_rn(kwa, e1n[q4][2]), __fmul_rn(kwa, e1n[q4][3])};
+                                }
+                            }
+                            if (!R1E && v == 3) {
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x4*>(Ex + (xrow + 8 * r) * EXP + xcol) = ec[r];
                             }
-                            if (v == 5) {
+                            if (!R1E && v == 5) {
 #pragma unroll
                                 for (int q4 = 0; q4 < 4; ++q4) e1n[q4] = *reinterpret_cast<const f32x4*>(Ex + l31 * EXP + 8 * q4 + 4 * half);
                             }
@@ -730,13 +779,13 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     }
 }
 
-template <int EPI, int XPRO, bool GM, bool H>
+template <int EPI, int XPRO, bool GM, bool H, bool R1 = false>
 int launch_dwgrad64bf(const DWArgs& a, int* grid_out, hipStream_t stream) {
     constexpr int NP = H ? 2 : 3;
-    constexpr size_t lds = (size_t)(NP * 66 * 72 + 2 * NP * 64 * 72 + 2 * NP * 64 * 88) * 2 + 8 * 64 * sizeof(float) +
+    constexpr size_t lds = (size_t)(NP * 66 * 72 + 2 * NP * 64 * 72 + 2 * NP * 64 * 88) * 2 + (R1 ? 9 : 8) * 64 * sizeof(float) +
                            (H ? (size_t)4 * 32 * 36 * sizeof(float) : 0);
     static wm::DevOnce attr_done;
-    auto kern = dwgrad64bf_kernel<EPI, XPRO, GM, H>;
+    auto kern = dwgrad64bf_kernel<EPI, XPRO, GM, H, R1>;
     if (int rc = wm::lds_opt_in(reinterpret_cast<const void*>(kern), lds, attr_done)) return rc;
     const int ntiles = a.B * (a.T / 64);
     const int grid = ntiles < kNumCU ? ntiles : kNumCU;
@@ -744,6 +793,14 @@ int launch_dwgrad64bf(const DWArgs& a, int* grid_out, hipStream_t stream) {
     if (a.stats && grid < kNumCU) WM_TRY(hipMemsetAsync(a.stats, 0, sizeof(float) * 128 * kNumCU, stream));
     if (H && a.dzmax && grid < kNumCU) WM_TRY(hipMemsetAsync(a.dzmax, 0, sizeof(float) * kNumCU, stream));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
+    WM_CHECK_LAUNCH();
+    return 0;
+}
+
+// the slabs of the launch above -> dw [64][64][3], dbias [64]
+int reduce_dwgrad_slabs(const float* partial, int grid, float* dw, float* dbias, int accumulate, hipStream_t stream) {
+    const int n = 3 * 4096 + 64;
+    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, partial, grid, 3, 0, dw, dbias, accumulate & 1);
     WM_CHECK_LAUNCH();
     return 0;
 }
@@ -760,7 +817,8 @@ int wm_dwgrad64_bf(const float* g, const float* g2, const float* ga, const float
     if (!g || !g2 || !ga || !gb || !gc || !wpb || !x || !e1 || !y || !partial || !dw) return (int)hipErrorInvalidValue;
     if (arith != 0 && (arith != 1 || !gscale)) return (int)hipErrorInvalidValue;
     DWArgs a{g, g2, ga, gb, gc, wpb, x, xa, xb, e1, ea, eb, y, stats, partial, B, T, reinterpret_cast<const unsigned*>(gmask),
-             epi == EPI_ADDSTATS ? reinterpret_cast<const unsigned*>(eb) : nullptr, epi == EPI_ADDSTATS ? ea : nullptr, gscale, dzmax};
+             epi == EPI_ADDSTATS ? reinterpret_cast<const unsigned*>(eb) : nullptr, epi == EPI_ADDSTATS ? ea : nullptr, gscale, dzmax,
+             nullptr, nullptr};
     int grid = 0, rc = (int)hipErrorInvalidValue;
 #define WM_DW(E, X, G) (arith ? launch_dwgrad64bf<E, X, G, true>(a, &grid, stream) : launch_dwgrad64bf<E, X, G, false>(a, &grid, stream))
     if (epi == EPI_RELUMASK && xpro == PRO_BNRELU && stats && xa && xb && ea && eb)
@@ -771,10 +829,29 @@ int wm_dwgrad64_bf(const float* g, const float* g2, const float* ga, const float
         rc = WM_DW(EPI_ADDSTATS, PRO_NONE, true);
 #undef WM_DW
     if (rc) return rc;
-    const int n = 3 * 4096 + 64;
-    hipLaunchKernelGGL(wgrad64_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, (const float*)partial, grid, 3, 0, dw,
-                       dbias, accumulate & 1);
-    WM_CHECK_LAUNCH();
-    return 0;
+    return reduce_dwgrad_slabs(partial, grid, dw, dbias, accumulate, stream);
+}
+
+// wm_dwgrad64_bf for the block in front of the Conv1d(64, 1, 1) head, whose output gradient is the rank-one frame hw[c] g1[b][t]
+// (wm_head1_bwd's dx): the frame is formed on load from g1 [B][T] and hw [64] instead of being read.  Two forms, both with gmask and
+// arith 1: (xpro 1, epi 1) with g == NULL, the frame is the gradient operand; (xpro 0, epi 2) with e1 == NULL, it is the addend.
+// Everything else, and every result bit for bit, as wm_dwgrad64_bf on the materialised frame.
+int wm_dwgrad64_bf_r1(const float* g, const float* g2, const float* ga, const float* gb, const float* gc, const void* wpb,
+                      const float* x, const float* xa, const float* xb, const float* e1, const float* ea, const float* eb,
+                      float* y, float* stats, float* partial, float* dw, float* dbias, int B, int T, int xpro, int epi, int accumulate,
+                      const void* gmask, int arith, const float* gscale, float* dzmax, const float* g1, const float* hw,
+                      hipStream_t stream) {
+    if (B <= 0 || T <= 0 || (T & 63)) return (int)hipErrorInvalidValue;
+    if (!g1 || !hw || !gmask || !g2 || !ga || !gb || !gc || !wpb || !x || !y || !partial || !dw) return (int)hipErrorInvalidValue;
+    if (arith != 1 || !gscale) return (int)hipErrorInvalidValue;
+    DWArgs a{g, g2, ga, gb, gc, wpb, x, xa, xb, e1, ea, eb, y, stats, partial, B, T, reinterpret_cast<const unsigned*>(gmask),
+             nullptr, nullptr, gscale, dzmax, g1, hw};
+    int grid = 0, rc = (int)hipErrorInvalidValue;
+    if (epi == EPI_RELUMASK && xpro == PRO_BNRELU && !g && e1 && stats && xa && xb && ea && eb)
+        rc = launch_dwgrad64bf<EPI_RELUMASK, PRO_BNRELU, true, true, true>(a, &grid, stream);
+    else if (epi == EPI_ADD && xpro == PRO_NONE && g && !e1 && !stats)
+        rc = launch_dwgrad64bf<EPI_ADD, PRO_NONE, true, true, true>(a, &grid, stream);
+    if (rc) return rc;
+    return reduce_dwgrad_slabs(partial, grid, dw, dbias, accumulate, stream);
 }
 }  // extern "C"

@@ -281,6 +281,9 @@ __global__ __launch_bounds__(256) void head1_tail_fwd_kernel(const float* __rest
 }
 
 // dx[c,t] = w[c] g[t];  dw[c] = sum g[t] x[c,t];  db = sum g   -> partial[block][65]
+// DX = false: dx is not written (its readers rebuild w[c] g[t] on load: wm_relu_bwd_reduce_mask_r1, wm_dwgrad64_bf_r1); the loop, the
+// grid and the order of acc[] are the same, so dw and db keep their bits.
+template <bool DX>
 __global__ __launch_bounds__(256) void head1_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                         const float* __restrict__ w, float* __restrict__ dx,
                                                         float* __restrict__ partial, int T4, int total4) {
@@ -297,8 +300,10 @@ __global__ __launch_bounds__(256) void head1_bwd_kernel(const float* __restrict_
         for (int c = 0; c < 64; ++c) {
             const float4 v = reinterpret_cast<const float4*>(x)[base + (size_t)c * T4];
             acc[c] += fmaf(gv.x, v.x, gv.y * v.y) + fmaf(gv.z, v.z, gv.w * v.w);
-            const float wc = w[c];
-            reinterpret_cast<float4*>(dx)[base + (size_t)c * T4] = make_float4(wc * gv.x, wc * gv.y, wc * gv.z, wc * gv.w);
+            if (DX) {
+                const float wc = w[c];
+                reinterpret_cast<float4*>(dx)[base + (size_t)c * T4] = make_float4(wc * gv.x, wc * gv.y, wc * gv.z, wc * gv.w);
+            }
         }
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -665,14 +670,15 @@ int wm_head1_tail_fwd(const float* x, const float* y2, const float* scale, const
     return 0;
 }
 
-// partial: >= 1024*65 floats.  dwb: [65] = dw[64] followed by db[1] (two separate tensors on the host side).
+// partial: >= 1024*65 floats.  dwb: [65] = dw[64] followed by db[1] (two separate tensors on the host side).  dx == NULL: dw and db only.
 int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
                  int T, int accumulate, hipStream_t stream) {
     if (T & 3) return (int)hipErrorInvalidValue;
     const int total4 = B * (T / 4);
     int grid = (total4 + 255) / 256;
     if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(head1_bwd_kernel, dim3(grid), dim3(256), 0, stream, g, x, w, dx, partial, T / 4, total4);
+    if (dx) hipLaunchKernelGGL(head1_bwd_kernel<true>, dim3(grid), dim3(256), 0, stream, g, x, w, dx, partial, T / 4, total4);
+    else hipLaunchKernelGGL(head1_bwd_kernel<false>, dim3(grid), dim3(256), 0, stream, g, x, w, dx, partial, T / 4, total4);
     WM_CHECK_LAUNCH();
     // partial [grid][65]: first 64 -> dw, last -> db
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, stream, (const float*)partial, grid, 65, 64, dw, accumulate);

@@ -342,6 +342,30 @@ def set_lstm_dx_in_bwd(on: bool):
     _LSTM_DX["in_bwd"] = bool(on)
 
 
+# decoder.1's backward never sees the gradient frame behind the Conv1d(64, 1, 1) head: dout[b,c,t] = hw[c] g[b,t] is formed on load by its
+# three readers (wm_relu_bwd_reduce_mask_r1, wm_dwgrad64_bf_r1 twice) and wm_head1_bwd writes dw and db only.  WM_HEAD1_RANK1=0/1 sets
+# the default ("1" = on, else off).  Kept outside SWITCHES like _TAILC.
+def read_head1_rank1(environ) -> bool:
+    """what the switch starts with under `environ` (pure, as read_switches)"""
+    return environ.get("WM_HEAD1_RANK1", "1") == "1"
+
+
+_HEAD1_R1 = {"on": read_head1_rank1(os.environ)}
+
+
+def set_head1_rank1(on: bool):
+    """1 (default): ResBlockHead1Fn's backward passes (g, hw) down instead of the frame where head1_rank1_applies(); 0: wm_head1_bwd
+    writes the frame and the block's backward reads it.  Bit-identical either way: the same single multiply, no sum is regrouped."""
+    _HEAD1_R1["on"] = bool(on)
+
+
+def head1_rank1_applies(x) -> bool:
+    """the switch and what the three rank-one launches need: the fused backward in its f16 build with the mask applied on load,
+    T % 64 == 0, no side-stream weight gradients"""
+    return bool(_HEAD1_R1["on"] and x.is_cuda and x.dim() == 3 and x.shape[-1] % 64 == 0 and _CONV["bf16x6"] and _CONV["fused_bwd"]
+                and _CONV["bwd_f16x3"] and _CONV["mask_on_load"] and not _ASYNC["on"])
+
+
 def _tail_in_consumer_launches(x, lstm: bool = False) -> bool:
     """the switch and what the two launches need: the f16 pipelined forward (the tail prologue exists in that build only, so
     T % 128 == 0); lstm=True adds the wave-specialised fused LSTM forward.  What a tape node asks inside its forward, where autograd
@@ -583,12 +607,14 @@ def _resblock_bwd(saved, training, gdst, g_out):
     return (dx,) + g1_ + (dg1, dbe1) + g2_ + (dg2, dbe2)
 
 
-def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
+def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None):
     """Backward of one ResBlock on the fused path (data + weight gradient of each convolution in one launch, T % 64 == 0).
     g_out: gradient w.r.t. the block output.  `pre` = (stats partials [NCU,2,64], max |dz| per workgroup [NCU]) when g_out ALREADY is
     dz2 = g (out > 0) and its two BatchNorm sums exist (made by the next block's folded conv1 launch): no reduction pass, no mask.
     `fold` = (mask, y2) of the block BEFORE this one: the conv1 launch then writes that block's dz2 instead of the plain input
     gradient and returns (its BatchNorm-sum partials, its max |dz| per workgroup) as the third value.
+    `rank1` = (g1 [B,1,T], hw [1,64,1]) with g_out None: the gradient w.r.t. the block output is hw[c] g1[b,t] and is formed on load
+    (head1_rank1_applies; neither `pre` nor `fold`).
     Returns (dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fold outputs | None)."""
     x, y1, y2, mask, cst, w1, w2, g1, g2 = saved
     sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
@@ -601,7 +627,14 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
     k2 = _f32(4, 64, device=dev)          # A, B (hi), B (lo), C  -- B is handed over as hi + lo words
     dg2, dbe2 = _f32(64, device=dev), _f32(64, device=dev)
     gs2 = _f32(2, device=dev) if h else None
-    if pre is not None:
+    if rank1 is not None:
+        r1g, r1w = rank1
+        part, dzm = _f32(max(B, 1) * 128, device=dev), _f32(B * 64, device=dev)
+        lib.wm_relu_bwd_reduce_mask_r1(_p(r1g), _p(r1w), _p(mask), _p(y2), _p(part), _p(dzm), B, T, st)
+        lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
+                               _p(dzm), B * 64, _p(gs2), st)
+        gsrc, gm = None, mask
+    elif pre is not None:
         ppart, pmax = pre
         gsrc, gm = g_out, None
         lib.wm_bn_bwd_finalize(_p(ppart), NCU, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
@@ -622,8 +655,13 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
     dzm1 = _f32(NCU, device=dev) if h else None          # max |dz1| per workgroup, written by the conv2-pair launch
     dw2, db2, dw1, db1 = torch.empty_like(w2), _f32(64, device=dev), torch.empty_like(w1), _f32(64, device=dev)
     wpart = _f32(NCU * (3 * 4096 + 64), device=dev)
-    lib.wm_dwgrad64_bf(_p(gsrc), _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(pack(w2, 1)), _p(y1), _p(sc1), _p(sh1),
-                       _p(y1), _p(sc1), _p(sh1), _p(dz1), _p(stats), _p(wpart), _p(dw2), _p(db2), B, T, 1, 1, 0, _p(gm), h, _p(gs2), _p(dzm1), st)
+    if rank1 is not None:
+        lib.wm_dwgrad64_bf_r1(None, _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(pack(w2, 1)), _p(y1), _p(sc1), _p(sh1),
+                              _p(y1), _p(sc1), _p(sh1), _p(dz1), _p(stats), _p(wpart), _p(dw2), _p(db2), B, T, 1, 1, 0, _p(gm), h, _p(gs2), _p(dzm1),
+                              _p(r1g), _p(r1w), st)
+    else:
+        lib.wm_dwgrad64_bf(_p(gsrc), _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(pack(w2, 1)), _p(y1), _p(sc1), _p(sh1),
+                           _p(y1), _p(sc1), _p(sh1), _p(dz1), _p(stats), _p(wpart), _p(dw2), _p(db2), B, T, 1, 1, 0, _p(gm), h, _p(gs2), _p(dzm1), st)
     k1 = _f32(4, 64, device=dev)
     dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
     gs1 = _f32(2, device=dev) if h else None
@@ -641,8 +679,13 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None):
         fout = (fpart, fmax)
     else:
         xmax = _f32(NCU, device=dev) if h else None          # max |dx| per workgroup: a consumer that splits dx into f16 pieces
-        lib.wm_dwgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
-                           _p(gsrc), None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax), st)
+        if rank1 is not None:
+            lib.wm_dwgrad64_bf_r1(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
+                                  None, None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax),
+                                  _p(r1g), _p(r1w), st)
+        else:
+            lib.wm_dwgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
+                               _p(gsrc), None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax), st)
         if h:
             _note_gmax(dx, xmax)                             # (ConvT7Fn.backward) then needs no pass over it for its scale
     return dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fout
@@ -808,10 +851,16 @@ class ResBlockHead1Fn(GradAwareFunction):
         sv = ctx.saved_tensors
         out, hw = sv[9], sv[10]
         B, _, T = out.shape
-        dout = torch.empty_like(out)
+        g = g.contiguous()
         part = _f32(1024 * 65, device=out.device)
         dhw, dhb = torch.empty_like(hw), _f32(1, device=out.device)
-        lib.wm_head1_bwd(_p(g.contiguous()), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
+        if head1_rank1_applies(out):
+            # dout[b,c,t] = hw[c] g[b,t] stays out of memory: the block's three readers of it form it on load
+            lib.wm_head1_bwd(_p(g), _p(out), _p(hw), None, _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
+            dx, grads, _ = _resblock_bwd_fused(sv[:9], True, None, rank1=(g, hw))
+            return (dx,) + grads + (None,) * 6 + (dhw, dhb)
+        dout = torch.empty_like(out)
+        lib.wm_head1_bwd(_p(g), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
         return _resblock_bwd(sv[:9], True, (None,) * 4, dout) + (None,) * 6 + (dhw, dhb)
 
 

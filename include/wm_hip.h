@@ -114,6 +114,16 @@ int wm_dwgrad64_bf(const float* g, const float* g2, const float* ga, const float
  *          power of two chosen from max |w|, stored behind the image); gscale = wm_bn_bwd_finalize's {gs, 1 / gs} for THIS launch's
  *          g; dzmax (optional, epi 1 / 2 / 8): 256 floats, max |y| per workgroup = the dzmax input of the next launch's finalize. */
 int wm_pack_w64_h(const float* w, void* wph, int mode, wm_stream_t stream);      /* 2 * 3 * 4096 f16 + 2 floats */
+/* wm_dwgrad64_bf for the ResBlock in front of the Conv1d(64,1,1) head.  The gradient that reaches its output is the rank-one frame
+ * hw[c] g1[b][t] (wm_head1_bwd's dx); it is formed on load from g1 [B][T] and hw [64] -- the same single multiply -- and never read
+ * from memory.  Two forms only, both with gmask and arith 1: (xpro 1, epi 1) with g == NULL: the frame is the gradient operand;
+ * (xpro 0, epi 2) with e1 == NULL: the frame is the epilogue addend.  Anything else: hipErrorInvalidValue.  Every output bit for bit
+ * what wm_dwgrad64_bf gives on the materialised frame. */
+int wm_dwgrad64_bf_r1(const float* g, const float* g2, const float* ga, const float* gb, const float* gc, const void* wpb,
+                      const float* x, const float* xa, const float* xb, const float* e1, const float* ea, const float* eb,
+                      float* y, float* stats, float* partial, float* dw, float* dbias, int B, int T, int xpro, int epi, int accumulate,
+                      const void* gmask, int arith, const float* gscale, float* dzmax, const float* g1, const float* hw,
+                      wm_stream_t stream);
 
 /* bf16x6 build of the 7-tap ConvTranspose1d(64,64,7,padding=3) (py/main16.py:144): wpb [3][7][64][64] uint16 from
  * wm_pack_w64_bf7 (mode 2 forward | 3 data gradient).  pro 0 x | 2 x + vec[b*64+c]; epi 0 + bias[c] | 3 none. */
@@ -171,6 +181,10 @@ int wm_bn_add_relu_mask(const float* x, const float* y2, const float* scale, con
                         wm_stream_t stream);
 int wm_relu_bwd_reduce_mask(const float* g, const void* mask, const float* y2, float* dz, float* partial, float* dzmax, int B, int T,
                             wm_stream_t stream);      /* dzmax (optional): B * 64 floats, max |dz| per row (wm_bn_bwd_finalize's gscale) */
+/* wm_relu_bwd_reduce_mask(dz = NULL) on the rank-one frame g[b][c][t] = w[c] g1[b][t] (wm_head1_bwd's dx), formed on load from
+ * g1 [B][T] and w [64]: partial and dzmax bit for bit the same. */
+int wm_relu_bwd_reduce_mask_r1(const float* g1, const float* w, const void* mask, const float* y2, float* partial, float* dzmax, int B,
+                               int T, wm_stream_t stream);
 /* A, Cc: [64]; Bc: [2][64] (hi, lo words of the offset, see wm_conv64 pro 3) */
 int wm_bn_bwd_finalize(const float* partials, int nparts, double count, const float* gamma, const float* save_mean,
                        const float* save_invstd, float* A, float* Bc, float* Cc, float* dgamma, float* dbeta,
@@ -184,7 +198,7 @@ int wm_stem_bwd(const float* g, const float* s, const float* w, float* ds, float
                 int T, int nds, int accumulate, wm_stream_t stream);   /* ds rows only for clips [0, nds); partial >= 512*512 floats */
 int wm_head1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, wm_stream_t stream);
 int wm_head1_bwd(const float* g, const float* x, const float* w, float* dx, float* partial, float* dw, float* db, int B,
-                 int T, int accumulate, wm_stream_t stream);
+                 int T, int accumulate, wm_stream_t stream);   /* dx == NULL: dw and db only (the _r1 entry points rebuild dx on load) */
 /* logits written as (B,T,NO) contiguous -- the layout Detector.forward's permuted view exposes.  NO = 1 + message_bits,
  * 1 <= NO <= 64 (message ids are int64, so at most 63 bits); T % 4 == 0.  headN_bwd: partial >= 256*(NO*64+NO) floats. */
 int wm_headN_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int NO, wm_stream_t stream);
