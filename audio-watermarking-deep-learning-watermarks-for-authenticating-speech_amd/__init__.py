@@ -13,7 +13,8 @@ from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_wa
                         evaluate_unseen_file, generate_watermarked_audio, load_audio, locate_watermark, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
                         save_audio,
                         save_audio_float)
-from .quality import stoi
+from .quality import stoi, nmr
+from .masking import masking, MaskingLoss
 from . import quality
 from .detection import (auc, calibrate_threshold, detection_report, eer, evaluate_detection, operating_point, roc_curve, tpr_at_fpr)
 from . import detection
@@ -35,4 +36,5 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "stoi", "quality",
            "detection", "evaluate_detection", "detection_report", "roc_curve", "auc", "eer", "tpr_at_fpr", "calibrate_threshold", "operating_point",
            "curate", "clip_features", "classify_speech_noise", "is_silent", "prepare_recording", "curate_files", "butter_bandpass_sos", "slaney_mel", "dct_ortho",
-           "lib", "LIB_PATH"]
+           "lib", "LIB_PATH",
+           "masking", "MaskingLoss", "nmr"]

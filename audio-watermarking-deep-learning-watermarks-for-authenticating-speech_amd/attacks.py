@@ -1163,7 +1163,13 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
     attacked clean half: the gap between the two is what the watermark adds under that attack) and "stoi_rows", the clips pooled --
     clips with fewer than 30 spectral frames have no score and are left out, not averaged in as the sentinel 1e-5 (NaN when none is
     left).  STOI assumes time-aligned signals: under TimeWarp it is low by construction and says nothing.  The default, quality=(), is
-    the call as it was."""
+    the call as it was.
+    `"nmr"` in quality adds five keys per row from ONE masking.masking call per attack on the same 2B rows against cat([s, s]): "nmr_db" and
+    "nmr_db_attack_only" (the mean over the pooled clips of the noise-to-mask ratio in dB of the attacked watermarked / attacked clean half),
+    "audible_share" and "audible_share_attack_only" (audible cells / cells over the pooled clips) and "nmr_rows", the clips pooled: those with
+    a frame (cells > 0) and a score that is not NaN in either half.  The clean half of "none" is s against s: -inf and share 0, reported as
+    such.  One simultaneous-masking model at an assumed playback level (see masking.py for the limits); like STOI it assumes time-aligned
+    signals, so under TimeWarp, TimeStretch and PitchShift the number is meaningless."""
     return _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, False)
 
 
@@ -1175,6 +1181,21 @@ def evaluate_robustness_by_class(generator, detector, batches, attacks, device="
     sample is in none.  With quality=("stoi",) a class's "stoi_rows" counts its scored clips.  (evaluate_robustness keeps its parameter
     list, so the per-class report is a call of its own rather than a by_class argument.)"""
     return _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, True)
+
+
+def _nmr_pool(parts, pick=None):
+    """the five "nmr" keys of one row of evaluate_robustness from the per-clip CPU tensors (nmr wm, nmr clean, audible wm, audible clean,
+    cells), over the clips of `pick` (all by default) that have a frame and a score in both halves"""
+    nw, nc, aw, ac, cells = parts
+    ok = (cells > 0) & ~torch.isnan(nw) & ~torch.isnan(nc)
+    if pick is not None:
+        ok = ok & pick
+    rows, total = int(ok.sum()), int(cells[ok].sum())
+    if rows == 0:
+        return {"nmr_db": math.nan, "nmr_db_attack_only": math.nan, "audible_share": math.nan, "audible_share_attack_only": math.nan,
+                "nmr_rows": 0}
+    return {"nmr_db": float(nw[ok].double().mean()), "nmr_db_attack_only": float(nc[ok].double().mean()),
+            "audible_share": int(aw[ok].sum()) / total, "audible_share_attack_only": int(ac[ok].sum()) / total, "nmr_rows": rows}
 
 
 def _evaluate_robustness(generator, detector, batches, attacks, device, message_bits, messages, quality, by_class):
@@ -1191,6 +1212,7 @@ def _evaluate_robustness(generator, detector, batches, attacks, device, message_
     acc = OrderedDict((name, {k: [] for k in keys}) for name, _ in named)
     stoi_acc = OrderedDict((name, ([], [])) for name, _ in named)
     stoi_all = OrderedDict((name, ([], [], [])) for name, _ in named)               # by_class: both halves unmasked, and the mask
+    nmr_all = OrderedDict((name, ([], [], [], [], [])) for name, _ in named)        # per clip: nmr wm / clean, audible wm / clean, cells
     classes = []
     for bi, s in enumerate(batches):
         s = s.to(device)
@@ -1215,6 +1237,12 @@ def _evaluate_robustness(generator, detector, batches, attacks, device, message_
                 if by_class:
                     for dst, v in zip(stoi_all[name], (d[:B], d[B:], scored)):
                         dst.append(v)
+            if "nmr" in quality:
+                from .masking import masking
+                B = s.shape[0]
+                m = masking(torch.cat([s, s], dim=0), attacked, SAMPLE_RATE)
+                for dst, v in zip(nmr_all[name], (m.nmr_db[:B], m.nmr_db[B:], m.audible[:B], m.audible[B:], m.cells[:B])):
+                    dst.append(v)
     res = OrderedDict((name, {k: float(torch.cat(v).double().mean()) if v else math.nan for k, v in a.items()})
                       for name, a in acc.items())
     if "stoi" in quality:
@@ -1223,6 +1251,12 @@ def _evaluate_robustness(generator, detector, batches, attacks, device, message_
             res[name]["stoi"] = float(pooled.double().mean()) if pooled.numel() else math.nan
             res[name]["stoi_attack_only"] = float(torch.cat(clean_half).double().mean()) if pooled.numel() else math.nan
             res[name]["stoi_rows"] = int(pooled.numel())
+    if "nmr" in quality:
+        empty = (torch.empty(0), torch.empty(0), torch.empty(0, dtype=torch.int32), torch.empty(0, dtype=torch.int32),
+                 torch.empty(0, dtype=torch.int32))
+        nmr_cpu = {name: (tuple(torch.cat(v).cpu() for v in parts) if parts[0] else empty) for name, parts in nmr_all.items()}
+        for name, parts in nmr_cpu.items():
+            res[name].update(_nmr_pool(parts))
     if by_class:
         from .curate import CLASSES, class_report
         cls = torch.cat(classes) if classes else torch.empty(0, dtype=torch.int64)
@@ -1238,5 +1272,8 @@ def _evaluate_robustness(generator, detector, batches, attacks, device, message_
             elif "stoi" in quality:
                 for c in CLASSES:
                     per[c].update(stoi=math.nan, stoi_attack_only=math.nan, stoi_rows=0)
+            if "nmr" in quality:
+                for i, c in enumerate(CLASSES):
+                    per[c].update(_nmr_pool(nmr_cpu[name], (cls.cpu() == i) if nmr_cpu[name][0].numel() else None))
             res[name]["by_class"] = per
     return res

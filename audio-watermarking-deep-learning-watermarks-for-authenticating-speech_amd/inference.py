@@ -348,14 +348,17 @@ def _embed_native(waveform, generator, message_bits, device, messages, max_batch
 
 
 def generate_watermarked_audio(input_file, generator, output_file=None, message_bits=16, device="cuda", orig_freq=None, native_rate=False,
-                               stoi=False):
+                               stoi=False, nmr=False):
     """py/main16.py:977-1066 with one batched Generator call; same result dict.  A path is loaded (and resampled) by
     load_audio; `orig_freq` is the rate of an in-memory (C, N) waveform that is not at 16 kHz.
     `native_rate=True`: a path is read by read_audio (its channels, its rate), an in-memory (C, N) waveform is at `orig_freq`; the three
     waveforms come back at that rate with all channels (embed_waveform), `output_file` is written at that rate with all channels, the
     metrics are taken at that rate (SI-SNR over the channel rows) and the dict gains "sample_rate".
     `stoi=True` adds metrics["stoi"]: STOI (quality.stoi) of the watermarked against the original waveform, the whole recording as ONE
-    row per channel at the rate the waveforms come back at, averaged over the channels; one upload, one wm_stoi call."""
+    row per channel at the rate the waveforms come back at, averaged over the channels; one upload, one wm_stoi call.
+    `nmr=True` adds metrics["nmr_db"] and metrics["audible_share"] (masking.masking: one simultaneous-masking model at an assumed playback
+    level) of the watermarked against the original waveform, the whole recording as ONE row per channel: the noise-to-mask ratio in dB
+    averaged over the channels, and audible cells / cells over all of them; one wm_masking_fwd call."""
     if native_rate:
         if isinstance(input_file, (str, os.PathLike)):
             waveform, rate = read_audio(input_file)
@@ -378,6 +381,8 @@ def generate_watermarked_audio(input_file, generator, output_file=None, message_
               "metrics": {"watermark_rms": watermark_rms, "si_snr_db": si_snr, "power_ratio_db": power_ratio_db}}
     if stoi:
         result["metrics"]["stoi"] = _stoi_whole(orig, wm, rate, device)
+    if nmr:
+        result["metrics"]["nmr_db"], result["metrics"]["audible_share"] = _nmr_whole(orig, wm, rate, device)
     if native_rate:
         result["sample_rate"] = rate
     return result
@@ -388,6 +393,14 @@ def _stoi_whole(original, processed, rate, device):
     from . import dsp
     d, _ = dsp.stoi(_as_channels(original).to(device), _as_channels(processed).to(device), rate)
     return float(d.double().mean())
+
+
+def _nmr_whole(original, processed, rate, device):
+    """(nmr_db averaged over the channels, audible cells / cells) of a whole (C, N) recording against its original, every channel as one row"""
+    from .masking import masking
+    m = masking(_as_channels(original).to(device), _as_channels(processed).to(device), rate)
+    cells = int(m.cells.sum())
+    return float(m.nmr_db.double().mean()), (int(m.audible.sum()) / cells if cells else math.nan)
 
 
 @torch.no_grad()
@@ -517,7 +530,7 @@ def _si_snr_rows(s, s_hat, eps=1e-8):
 
 @torch.no_grad()
 def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_bits=16, messages=None, max_batch=256,
-                         orig_freq=None, stoi=False):
+                         orig_freq=None, stoi=False, nmr=False):
     """py/main16.py:1263-1299 with all 1-s segments of the file as one batch: returns (mean clean detection probability,
     mean watermarked detection probability, mean SI-SNR, mean delta RMS) over the segments, or four Nones when the file
     cannot be read (:1264-1267).  A fresh random message per segment (:1287) unless `messages` is given.  Accepts a path
@@ -525,8 +538,10 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
     four scalars come back.
     `stoi=True`: a fifth element, STOI (quality.stoi) of the whole 16 kHz recording as ONE row, watermarked against original (the
     reference's baseline variant averages pystoi over the one-second segments instead, py/main14.py:1099-1203); five Nones when the
-    file cannot be read."""
-    nout = 5 if stoi else 4
+    file cannot be read.
+    `nmr=True`: one more element behind that, the noise-to-mask ratio in dB (masking.masking) of the whole 16 kHz recording as ONE row,
+    watermarked against original."""
+    nout = 4 + bool(stoi) + bool(nmr)
     if isinstance(filepath, (str, os.PathLike)):
         try:
             waveform, orig_freq = load_audio(filepath), None
@@ -542,7 +557,7 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
     if messages is None:
         messages = torch.randint(0, 2 ** message_bits, (S,), device=device)
     clean, wm, si, rms = [], [], [], []
-    whole = torch.empty(S, 1, segs.shape[2], device=device) if stoi else None       # the watermarked segments, for the one-row STOI
+    whole = torch.empty(S, 1, segs.shape[2], device=device) if stoi or nmr else None   # the watermarked segments, for the one-row measures
     for i in range(0, S, max_batch):
         seg = segs[i:i + max_batch].to(device)
         delta = generator(seg, messages[i:i + max_batch].to(device))
@@ -552,15 +567,20 @@ def evaluate_unseen_file(filepath, generator, detector, device="cuda", message_b
         clean.append(p[:k]); wm.append(p[k:])
         rms.append(torch.sqrt((delta ** 2).mean(dim=[1, 2])))
         si.append(_si_snr_rows(seg, seg_w))
-        if stoi:
+        if whole is not None:
             whole[i:i + k] = seg_w
     out = torch.stack([torch.cat(v).double().mean() for v in (clean, wm, si, rms)]).cpu()
     res = tuple(float(v) for v in out)
+    if whole is not None:
+        n = (S - 1) * segs.shape[2] + (remainder if remainder else segs.shape[2])     # the recording without the last segment's padding
     if stoi:
         from . import dsp
-        n = (S - 1) * segs.shape[2] + (remainder if remainder else segs.shape[2])     # the recording without the last segment's padding
         d, _ = dsp.stoi(segs.to(device).reshape(1, -1)[:, :n], whole.reshape(1, -1)[:, :n], SAMPLE_RATE)
         res += (float(d[0]),)
+    if nmr:
+        from .masking import masking
+        m = masking(segs.to(device).reshape(1, -1)[:, :n].contiguous(), whole.reshape(1, -1)[:, :n].contiguous(), SAMPLE_RATE)
+        res += (float(m.nmr_db[0]),)
     return res
 
 

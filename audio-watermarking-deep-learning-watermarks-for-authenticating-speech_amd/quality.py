@@ -18,7 +18,7 @@ _EPS = 2.0 ** -52
 _FRAME, _HOP, _NFFT, _SEG = 256, 128, 512, 30
 STOI_BANDS = ((7, 9), (9, 11), (11, 14), (14, 17), (17, 22), (22, 27), (27, 34), (34, 43), (43, 55), (55, 69), (69, 87), (87, 109),
               (109, 138), (138, 174), (174, 219))
-METRICS = ("stoi",)
+METRICS = ("stoi", "nmr")
 
 
 def _cut(v, count):
@@ -77,6 +77,17 @@ def stoi(reference, processed, sample_rate=16000):
     d, _ = dsp.stoi(reference, processed, sample_rate)
     lead = tuple(reference.shape[:-2]) if reference.dim() == 3 else tuple(reference.shape[:-1])
     return d.reshape(lead)
+
+
+def nmr(reference, processed, sample_rate=16000):
+    """Noise-to-mask ratio in dB of `processed` against `reference` (masking.masking: one simultaneous-masking model at an assumed playback
+    level, see that module for what it is not): tensors of equal shape (B, 1, T), (C, N) or (N,) at `sample_rate`; returns nmr_db with the
+    input's leading shape, float32 on the inputs' device.  Below 0 dB the difference is, on average, under the mask.  A row under 512 samples
+    at 16 kHz or with a non-finite sample scores NaN; processed == reference scores -inf."""
+    from .masking import masking
+    res = masking(reference, processed, sample_rate)
+    lead = tuple(reference.shape[:-2]) if reference.dim() == 3 else tuple(reference.shape[:-1])
+    return res.nmr_db.reshape(lead)
 
 
 def check_metrics(quality):

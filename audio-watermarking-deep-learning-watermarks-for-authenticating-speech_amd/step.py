@@ -7,21 +7,26 @@ from collections import OrderedDict
 import torch
 
 from . import losses as L, ops
+from .masking import MaskingLoss
 
 # py/main16.py:38-43
 LOSS_WEIGHTS = OrderedDict(l1=1.0, mel=4.0, loud=20.0, loc=10.0, bce=1.0, hf=5.0)
 
 _mel = L.MultiScaleMelLoss()
 _loud = L.TFLoudnessLoss()
+_mask = MaskingLoss()
 
 
-def forward_losses(generator, detector, s, message, codec=None, tamper=None):
+def forward_losses(generator, detector, s, message, codec=None, tamper=None, masking=None):
     """delta -> post-processing -> detector on cat([s_w, s]) -> the six loss terms and both totals.
     `codec` (a codec.PcmCodec): the main15c graph -- s_w = codec(s + delta) is what the Detector, mel and loudness see.
     `tamper` (an attacks.Splice): the Detector sees cat([s_t, s]) with s_t, labels = tamper(s_w, s) -- the splice comes last, behind any
     codec -- and loc / bce are taken against the per-sample labels (losses.detection_losses_masked) behind the plain
     detector(x, input_grad_rows=B): the fused Detector tail hard-codes "row < B => 1" and is not used.  Mel, loudness, l1 and hf see the
-    unspliced signals exactly as without it; `out` gains "labels" and "s_t".  None: the call as it was."""
+    unspliced signals exactly as without it; `out` gains "labels" and "s_t".  None: the call as it was.
+    `masking` (a float, the weight): a seventh term, out["mask"] = masking.MaskingLoss()(s, s_w) -- the mean number of dB by which
+    s_w - s is above the masking threshold of s, s_w taken behind any codec like mel and loudness -- and total += masking * mask.
+    raw_total and LOSS_WEIGHTS are as they were.  None: the call as it was, bit for bit."""
     B = s.shape[0]
     delta_raw = generator(s, message)                                  # :244
     delta = L.postprocess(delta_raw)                                   # :245-247
@@ -45,15 +50,21 @@ def forward_losses(generator, detector, s, message, codec=None, tamper=None):
                       bce=bce, hf=hf, raw_total=raw, total=total)
     if tamper is not None:
         out["labels"], out["s_t"] = labels, s_t
+    if masking is not None:
+        out["mask"] = _mask(s, s_w)
+        total = total + float(masking) * out["mask"]
+        out["total"] = total
     return total, out
 
 
-def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec=None, tamper=None):
+def _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec=None, tamper=None, masking=None):
     """the step around a model family's forward_losses: zero_grad, forward, backward, gradient sync, message-id check, update.
-    `codec` and `tamper` are handed to forward_losses only when given (a family without them keeps its signature)."""
+    `codec`, `tamper` and `masking` are handed to forward_losses only when given (a family without them keeps its signature)."""
     extra = {} if codec is None else {"codec": codec}
     if tamper is not None:
         extra["tamper"] = tamper
+    if masking is not None:
+        extra["masking"] = masking
     optimizer.zero_grad(set_to_none=not hasattr(optimizer, "flat"))
     if hasattr(grad_sync, "begin_step"):
         grad_sync.begin_step()
@@ -75,12 +86,12 @@ def _train_step(forward_losses, generator, detector, optimizer, s, message, grad
     return out
 
 
-def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec=None, tamper=None):
+def train_step(generator, detector, optimizer, s, message, grad_sync=None, codec=None, tamper=None, masking=None):
     """One iteration of train_one_epoch's loop body (:242-278): zero_grad, forward, backward, optimizer step.
     `grad_sync` (optional callable) runs between backward and the update -- the data-parallel all-reduce.
     `codec` (a codec.PcmCodec): main15c's step, see forward_losses.  `tamper` (an attacks.Splice): the splice attack with per-sample
-    labels, see forward_losses."""
-    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec, tamper)
+    labels, see forward_losses.  `masking` (a float): the weight of the masking loss as a seventh term, see forward_losses."""
+    return _train_step(forward_losses, generator, detector, optimizer, s, message, grad_sync, codec, tamper, masking)
 
 
 def _eval_reductions(logits, message, delta):

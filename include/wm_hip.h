@@ -711,6 +711,54 @@ int wm_lpc_codec(const float* x, float* y, const float* coeffs_in, float* coeffs
 int wm_stoi_plan(long long rows, long long n, long long* scratch_bytes, wm_stream_t stream);
 int wm_stoi(const float* x, const float* y, float* d, int* kept, void* scratch, long long rows, long long n, wm_stream_t stream);
 
+/* ---- spectral masking: noise-to-mask ratio of a processed signal against its reference, and the masking loss with its gradient -------
+ * The reference's README speaks of a watermark "below psychoacoustic thresholds" and computes none (TFLoudnessLoss, py/main16.py:204-217,
+ * is a gated squared magnitude difference).  This is ONE simultaneous-masking model of the 1988 kind -- Bark bands, the Schroeder spreading
+ * function, Johnston's tonality offset, Terhardt's threshold in quiet -- at an ASSUMED playback level (a full-scale sine = 96 dB SPL).  No
+ * temporal masking; the mask is not differentiated; parity with PEAQ, with an MPEG encoder's model and with listeners is unmeasured.
+ * x (the reference) and y (the processed signal) are (rows, n) fp32 AT 16 kHz, rows >= 1, 1 <= n <= 2^34, rows * n <= 2^46; every row
+ * pair on its own; d = y - x.
+ *   1 frames     N = 512, hop 256, periodic Hann w[t] = 0.5 (1 - cos(2 pi t / 512)), no padding: F = 1 + (n - 512) / 256 (integer division)
+ *                for n >= 512, else 0.  A tail shorter than a hop is not judged and gets zero gradient.
+ *   2 power      k = 0..256:  P_v[f,k] = c_k |sum_t w[t] v[256 f + t] e^(-2 pi i k t / 512)|^2,  c_k = 2 (8/3) / 512^2 for 0 < k < 256 and
+ *                (8/3) / 512^2 at k = 0 and 256 (8/3 undoes the window's power loss: a full-scale sine sums to about 0.5)
+ *   3 bands      z(f) = 13 atan(0.00076 f) + 3.5 atan((f / 7500)^2),  band(k) = min(floor(z(k 16000 / 512)), Z - 1),  Z = floor(z(8000)) + 1
+ *                = 22; bins per band: 4 3 3 4 3 4 4 5 5 6 6 8 8 11 13 16 20 23 28 32 38 13 (257 in all).  E_x[f,b], E_d[f,b]: the band sums
+ *                of P_x and P_d
+ *   4 spreading  S[b,j] = 10^(SF(b - j) / 10),  SF(D) = 15.81 + 7.5 (D + 0.474) - 17.5 sqrt(1 + (D + 0.474)^2);
+ *                C[f,b] = sum_j S[b,j] E_x[f,j],  G[b] = sum_j S[b,j]
+ *   5 tonality   over bins 1..255 of P_x:  sfm_dB = 10 log10(exp(mean ln(P + 1e-30)) / (mean P + 1e-30)),  alpha = clip(sfm_dB / -60, 0, 1),
+ *                O[f,b] = alpha (14.5 + b) + (1 - alpha) 5.5  dB
+ *   6 quiet      ath(f) = 3.64 f^-0.8 - 6.5 e^(-0.6 (f - 3.3)^2) + 1e-3 f^4 dB SPL, f in kHz, at the bin centres (bin 0 at bin 1's
+ *                frequency);  A[b] = 0.5 * 10^((min over the band's bins of ath - 96) / 10)
+ *   7 mask       T[f,b] = max(C[f,b] 10^(-O[f,b] / 10) / G[b], A[b]),  r[f,b] = E_d[f,b] / T[f,b]
+ *   8 outputs    nmr_db = 10 log10(mean over f,b of r);  over_db = mean over f,b of max(0, 10 log10 r);  counts[2 row] = audible = #{r > 1},
+ *                counts[2 row + 1] = cells = 22 F.  F = 0: NaN, 0, 0, 0.  d == 0: -inf, 0.  A non-finite sample anywhere in the row of x or
+ *                y: both floats NaN, both counts 0, for that row only.
+ *   9 gradient   d over_db / d y only; the mask is a function of x alone and a constant of the backward pass, x gets no gradient.  With
+ *                g[f,b] = (10 / ln 10) / E_d[f,b] where r > 1, else 0 (this is `coef`; E_d > T >= A[b] > 0 there: no division near zero):
+ *                  gy[t] = gout[row] / cells * sum_f w[t - 256 f] Re sum_k 2 g[f,band(k)] c_k D[f,k] e^(+2 pi i k (t - 256 f) / 512),
+ *                D the windowed spectrum of d.  Samples no frame covers are written as 0.  A row that scored NaN: gy unspecified.
+ * tables: ONE device buffer of 1042 words from the caller, formed in float64 and rounded once (the package's masking_tables()):
+ *   c_k[257] | band[257] as int32 | S[22][22] | G[22] | A[22].  The window is not among them: both directions form it themselves, the
+ *   forward in fp64 (its fp32 rounding alone would cost 5e-7 dB of over_db on a one-frame row).  wm_masking_bwd takes no tables at all:
+ *   c_k and band(k) are closed forms too (the bin counts above).
+ * coef (nullable, (rows, F, 22) fp32): written by wm_masking_fwd when given, read by wm_masking_bwd (required there when F > 0).
+ * The forward is computed in fp64 from the window on (the tables stay fp32), the backward in fp32 (csrc/masking.hip).  Forward: one launch over (row, chunk of `chunk` frames) -- the frames
+ * in pairs, two frames of ONE signal per complex 512-point transform -- and one launch that finishes each row in a fixed order.  Backward:
+ * one launch over (row, 256 output samples); each workgroup forms the two frames that cover its samples.  No atomics: a row's bits depend
+ * on its samples and n only, never on rows, its place in the batch or the grid; two launches give identical bits.
+ * wm_masking_plan: host-only query (the three results are HOST pointers, stream unused): frames = F, chunk = the frames one workgroup of
+ * the forward handles, scratch_bytes = what `scratch` must hold (caller-allocated, contents unspecified before and after).
+ * Every pointer may start at any multiple of 4 bytes; inputs are borrowed.
+ * hipErrorInvalidValue before any launch: rows or n out of range, rows * n > 2^46, a null or misaligned pointer (coef may be null in the
+ * forward, and in the backward when F = 0), an output overlapping an input or another output. */
+int wm_masking_plan(long long rows, long long n, long long* frames, long long* chunk, long long* scratch_bytes, wm_stream_t stream);
+int wm_masking_fwd(const float* x, const float* y, const float* tables, float* nmr_db, float* over_db, int* counts, float* coef,
+                   void* scratch, long long rows, long long n, wm_stream_t stream);
+int wm_masking_bwd(const float* x, const float* y, const float* coef, const float* gout, float* gy, long long rows, long long n,
+                   wm_stream_t stream);
+
 /* ---- splice attack and localisation: per-sample labels, the detection losses against them, confusion counts ------------------------
  * the editing attack: part of a watermarked recording is cut out and replaced by unmarked audio, by silence, or by audio moved from
  * elsewhere in the same recording (the reference ships no code for it; its target is all ones on the watermarked half, py/main16.py:255-258).
