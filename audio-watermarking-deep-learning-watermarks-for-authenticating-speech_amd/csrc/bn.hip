@@ -10,6 +10,18 @@ using namespace wm;
 
 namespace {
 
+// The power of two gs with m * gs in (2^(L-1), 2^L] for a finite m > 0: gs = 2^floor(L - log2 m), with the exponent taken from m itself.
+// m = f 2^e, f in [0.5, 1), so floor(L - log2 m) = floor(L) - e, and one more where f <= 2^(frac(L) - 1) (integral L: m a power of two).
+// Not exp2f(floorf(L - log2f(m))): for m up to some thirty ulp above a power of two log2f(m), or its difference to L, rounds to the
+// integer, which gives a scale one binade too large (max |x| gs in (2^L, 2^(L+1)]).  Out of range: ldexpf gives inf or 0, clamped.
+__device__ __forceinline__ float pow2_scale(float m, float L) {
+    int e;
+    const float f = frexpf(m, &e);
+    const float Li = floorf(L), fr = L - Li;
+    const float thr = fr == 0.f ? 0.5f : exp2f(fr - 1.f);
+    return ldexpf(1.f, (int)Li - e + (f <= thr ? 1 : 0));
+}
+
 // sum partials[p][which][c] over p in double: 1024 threads = 64 channels x 16 slices, LDS tree at the end
 __device__ __forceinline__ void reduce_partials_1024(const float* __restrict__ partials, int nparts, double& s1, double& s2,
                                                      double (*red)[2][64]) {
@@ -237,7 +249,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
             // pathological spike saturates one element instead of producing an infinity), tiny elements keep 2^-33 of the maximum
             const float big = amax * mx;
             float gs = 1.f;
-            if (big > 0.f && big < 3.0e38f) gs = exp2f(floorf(log2f(512.f / big)));
+            if (big > 0.f && big < 3.0e38f) gs = pow2_scale(big, 9.f);
             gs = fminf(fmaxf(gs, 1.0e-30f), 1.0e30f);
             gscale[0] = gs;
             gscale[1] = 1.f / gs;
@@ -281,7 +293,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float4* __restrict__ 
     if (threadIdx.x == 0) {
         mm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         float gs = 1.f;
-        if (mm > 0.f && mm < 3.0e38f) gs = exp2f(floorf(log2_target - log2f(mm)));      // NaN / inf / all-zero input: scale 1
+        if (mm > 0.f && mm < 3.0e38f) gs = pow2_scale(mm, log2_target);      // NaN / inf / all-zero input: scale 1
         gs = fminf(fmaxf(gs, 1.0e-30f), 1.0e30f);
         gscale[0] = gs; gscale[1] = 1.f / gs;
         g_absmax_ticket = 0;
@@ -299,7 +311,7 @@ __global__ __launch_bounds__(256) void gscale_from_max_kernel(const float* __res
     if (threadIdx.x == 0) {
         m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         float gs = 1.f;
-        if (m > 0.f && m < 3.0e38f) gs = exp2f(floorf(log2_target - log2f(m)));      // NaN / inf / all-zero input: scale 1
+        if (m > 0.f && m < 3.0e38f) gs = pow2_scale(m, log2_target);      // NaN / inf / all-zero input: scale 1
         gs = fminf(fmaxf(gs, 1.0e-30f), 1.0e30f);
         gscale[0] = gs; gscale[1] = 1.f / gs;
     }

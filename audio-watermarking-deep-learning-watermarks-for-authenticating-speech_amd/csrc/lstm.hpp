@@ -67,8 +67,12 @@ __device__ __forceinline__ float quad_bcast(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false));
 }
 
-// sigmoid via v_exp_f32 + v_rcp_f32.  The absolute error of sigma is sigma*(1-sigma)*|z|*O(1e-7)
-// <= 3e-8 for every z (the derivative vanishes where |z| is large), well inside fp32 round-off.
+// sigmoid via v_exp_f32 + v_rcp_f32.  With U = 2^-24: the exponential carries |z| U from the rounded product z log2(e) and 2 U (1 ulp)
+// from v_exp_f32, which move sigma by sigma (1 - sigma) times that (the derivative vanishes where |z| is large); the sum 1 + e (U) and
+// v_rcp_f32 (1 ulp) move it by sigma times theirs:  |error| <= sigma (1 - sigma) (|z| + 2) U + 3 U sigma  <= 1.9e-7 for every z,
+// fp32 round-off of a value near 1 (the first term alone is below 3e-8; correctly rounded fp32 arithmetic is no closer than the sum).
+// tanh_s doubles it and rounds once more, <= 4.3e-7 absolute: near z = 0 that is a relative error of order U / |z| (2 s - 1 cancels).
+// tests/lstm_yardstick.py derives both bounds, tests/test_gpu_lstm_edges.py holds the functions to them over +-1e4.
 __device__ __forceinline__ float sigm(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
 __device__ __forceinline__ float tanh_s(float z) { return fmaf(2.0f, sigm(2.0f * z), -1.0f); }
 // one transcendental pair per lane whatever the gate: tanh(x) = 2*sigmoid(2x) - 1 for the g lanes
