@@ -63,7 +63,9 @@ static __device__ unsigned long long* g_wm_stamp = nullptr;
 
 namespace {
 enum { PRO_NONE = 0, PRO_BNRELU = 1, PRO_ADDVEC = 2, PRO_BNBWD = 3,
-       PRO_TAIL = 4 };    // conv64bf3 (f16 build) only: the previous ResBlock's tail relu(x + x2 * pa + pb), also stored to tout / tmask
+       PRO_TAIL = 4,      // conv64bf3 (f16 build) only: the previous ResBlock's tail relu(x + x2 * pa + pb), also stored to tout / tmask
+       PRO_STEM = 5 };    // conv64bf3 (f16 build) only: the stem's output pb[c] + sum_j pa[c][j] x[b, t + j - 3] of the clips x [B,1,T], also stored to tout;
+                          // dwgrad64bf (XPRO, f16 build): the same value as the weight-gradient operand, from DWArgs' ss / sw / sb
 enum { EPI_BIAS = 0, EPI_RELUMASK = 1, EPI_ADD = 2, EPI_NONE = 3, EPI_BNADDRELU = 4,    // 4: relu(e1 + (acc + bias) * ea + eb), conv64bf3 only
        EPI_BIASELU = 5, EPI_BIASADDELU = 6, EPI_MULDELU = 7,    // main14b_2's 64-channel blocks (conv64bf_kernel only): elu(acc + bias),
                                                                  // elu(acc + bias + e1), acc * ELU'(e1) with e1 = the ELU output y
@@ -83,7 +85,7 @@ struct Conv64Args {
     float* y;           // [B,64,T]
     float* stats;       // [gridDim.x][2][64] partial sums or nullptr
     int B, T;
-    float* tout = nullptr;       // [B,64,T] PRO_TAIL: the formed input, as wm_bn_add_relu_mask writes it
+    float* tout = nullptr;       // [B,64,T] PRO_TAIL: the formed input, as wm_bn_add_relu_mask writes it; PRO_STEM: as wm_stem_fwd writes it
     unsigned* tmask = nullptr;   // [B*64][T/32] PRO_TAIL: its sign bits (wm_bn_add_relu_mask's layout) or nullptr
 };
 

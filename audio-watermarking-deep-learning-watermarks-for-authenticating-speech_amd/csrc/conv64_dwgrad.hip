@@ -37,6 +37,7 @@ struct DWArgs {
                                                         // gradient (wm_bn_bwd_finalize); the weight image carries its own scale
     float* dzmax;                                       // H, epi 1 / 2 / 8: max |y| per workgroup [grid] (sizes the NEXT launch's scale)
     const float* g1; const float* hw;                   // R1: the rank-one frame w[c] g1[b][t] that stands in for g (conv2 pair) / e1 (conv1 pair)
+    const float* ss; const float* sw; const float* sb;  // XS: the clips [B,1,T] and the stem's w [64][7], bias [64] whose output stands in for x
 };
 
 // H = false: bf16 three-piece split, six piece products per product (bf16x6).  H = true: f16 TWO-piece split (hi = RNE_f16(x s),
@@ -49,9 +50,15 @@ struct DWArgs {
 // hw[c] g1[b][t] (head1_bwd_kernel's dx).  It is not read from memory but formed from the clip's row g1 [B][T] and the 64 weights with
 // that kernel's one multiply, in front of the mask AND: as the gradient operand g (conv2 pair: one dwordx4 of g1 per unit instead of
 // one per channel and unit) / as the epilogue addend e1 (conv1 pair: one dwordx4 of g1 per lane instead of four row fetches).
+// XPRO = PRO_STEM (XS; the first block behind a stem: conv1 pair, no mask, H): the weight-gradient operand x is the stem's output Conv1d(1, 64, 7,
+// padding = 3)(s).  It is not read from memory but formed from the clip's samples and the stem's parameters with stem_fwd_kernel's
+// fmaf chain (small_convs.hip): per unit the ten samples around its time quad (three loads) instead of two frame quads, per halo
+// column two.  Buffer loads over the clip: a quad outside [0, T) reads zero, the stem's padding.  One seven-FMA chain per slice.
 template <int EPI, int XPRO, bool GM, bool H, bool R1 = false>
 __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
-    static_assert((EPI == EPI_RELUMASK && XPRO == PRO_BNRELU) || ((EPI == EPI_ADD || EPI == EPI_ADDSTATS) && XPRO == PRO_NONE), "conv2 pair or conv1 pair");
+    constexpr bool XS = (XPRO == PRO_STEM);
+    static_assert((EPI == EPI_RELUMASK && XPRO == PRO_BNRELU) || ((EPI == EPI_ADD || EPI == EPI_ADDSTATS) && XPRO == PRO_NONE) ||
+                  (EPI == EPI_ADD && XS && !GM && H && !R1), "conv2 pair, conv1 pair, or the plain f16 conv1 pair behind a stem");
     static_assert(!R1 || (GM && H && (EPI == EPI_RELUMASK || EPI == EPI_ADD)), "rank-one gradient: masked on load, f16 build");
     constexpr bool R1G = R1 && EPI == EPI_RELUMASK, R1E = R1 && EPI == EPI_ADD;     // ... as g / as e1
     constexpr int NCS = R1 ? 9 : 8;                        // rows of Cs: R1 adds the head's weights
@@ -105,6 +112,11 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     float4 gz_;                                                // the rebuilt gradient of the (unit, channel) being split
     unsigned gp_[2][2][6];                                     // its bf16 pieces [unit][channel][piece * 2 + time pair] (phase A -> phase B)
     float hg = 0.f, hy = 0.f, hxv = 0.f;
+    // XS: the samples s[tq - 3 .. tq + 6] of a unit (three loads; what no tap reads is not loaded: a register that is loaded and never
+    // read is handed out again at once, and the write to it then waits for the load) / s[hq .. hq + 7] of the halo column
+    f32x3 sxl_[XS ? 2 : 1], sxr_[XS ? 2 : 1];
+    f32x4 sxm_[XS ? 2 : 1], hxq_[2];
+    unsigned voffs = 0, voffs0 = 0, hoffs0 = 0, hoffs1 = 0;
     wm_srd_t dsg = make_srd(a.g, 0), dsy = dsg, dsx = dsg, dsm = dsg;
     unsigned voff = 0, hoff = 0;
     unsigned voffr = 0, hoffr = 0;                       // R1G: the same places in the clip's row of g1
@@ -118,9 +130,17 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         const size_t clip = (size_t)b * 64 * T, bytes = (size_t)64 * T * sizeof(float);
         dsg = R1G ? make_srd(a.g1 + (size_t)b * T, (size_t)T * sizeof(float)) : make_srd(a.g + clip, bytes);
         dsy = make_srd(a.g2 + clip, bytes);
-        dsx = make_srd(a.x + clip, bytes);
+        if (XS) dsx = make_srd(a.ss + (size_t)b * T, (size_t)T * sizeof(float));
+        else dsx = make_srd(a.x + clip, bytes);
         voff = (unsigned)(c0 * T + t0 + 4 * q0) * 4u;
         const int th = hh ? t0 + NT : t0 - 1;
+        if (XS) {               // (the quad in front of the clip takes an offset past every clip instead of a negative one)
+            const int tq = t0 + 4 * q0, hq = hh ? t0 + NT - 4 : t0 - 4;      // column t0 - 1: s[t0 - 4 .. t0 + 2]; column t0 + NT: s[t0 + NT - 3 .. t0 + NT + 3]
+            voffs = (unsigned)tq * 4u;
+            voffs0 = tq >= 4 ? voffs - 12u : 0xFFFFFF00u;
+            hoffs0 = hq >= 0 ? (unsigned)hq * 4u : 0xFFFFFF00u;
+            hoffs1 = (unsigned)(hq + 4) * 4u;
+        }
         hoff = (unsigned)(hc * T + min(max(th, 0), T - 1)) * 4u;
         okh = th >= 0 && th < T;
         if (R1G) {
@@ -145,7 +165,13 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         ya_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, 0u));
         yb_[u] = __builtin_bit_cast(float4, buf_load4(dsy, voff + 128u * u, rowT));
     };
+    auto load_xs = [&](int u, int k) {              // XS: quad k of unit u (unit 1 sits 32 steps behind unit 0: its first quad is inside)
+        if (k == 0) sxl_[XS ? u : 0] = buf_load3(dsx, u ? voffs + 116u : voffs0, 0u);
+        if (k == 1) sxm_[XS ? u : 0] = buf_load4(dsx, voffs + 128u * u, 0u);
+        if (k == 2) sxr_[XS ? u : 0] = buf_load3(dsx, voffs + 128u * u + 16u, 0u);
+    };
     auto load_x = [&](int u) {
+        if (XS) { load_xs(u, 0); load_xs(u, 1); load_xs(u, 2); return; }
         xa_[u] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u * u, 0u));
         xb_[u] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u * u, rowT));
     };
@@ -171,6 +197,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         }
     };
     auto refillB = [&](int v) {                     // phase-B free slice v
+        if (XS) { if ((v & 3) == 1) load_xs(v / 12, (v % 12) >> 2); return; }      // v = 1, 5, 9 | 13, 17, 21
         if (v == 1) xa_[0] = __builtin_bit_cast(float4, buf_load4(dsx, voff, 0u));
         if (v == 7) xb_[0] = __builtin_bit_cast(float4, buf_load4(dsx, voff, rowT));
         if (v == 13) xa_[1] = __builtin_bit_cast(float4, buf_load4(dsx, voff + 128u, 0u));
@@ -184,7 +211,10 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         mk_[u][0] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u * u, 0u));
         mk_[u][1] = __builtin_bit_cast(unsigned, buf_load(dsm, voffm + 4u * u, nwm * 4u));
     };
-    auto load_xhalo = [&]() { hxv = buf_load(dsx, hoff, 0u); };
+    auto load_xhalo = [&]() {
+        if (XS) { hxq_[0] = buf_load4(dsx, hoffs0, 0u); hxq_[1] = buf_load4(dsx, hoffs1, 0u); return; }
+        hxv = buf_load(dsx, hoff, 0u);
+    };
 
     const int tstep = gridDim.x;
     int tile = WM_XCD_MAP ? xcd_slot() : (int)blockIdx.x;          // grid <= ntiles
@@ -216,6 +246,13 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     }
     // R1G: the head's weights of the staging channels / of the halo channel
     const float kw[2] = {R1G ? Cs[512 + c0] : 0.f, R1G ? Cs[512 + c0 + 1] : 0.f}, khw = R1G ? Cs[512 + hc] : 0.f;
+    // XS: the seven taps and the bias of the two staging channels and of the halo channel
+    float ksw[2][XS ? 7 : 1], ksh[XS ? 7 : 1], ksb[2] = {0.f, 0.f}, ksbh = 0.f;
+    if (XS) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { ksw[0][XS ? j : 0] = a.sw[c0 * 7 + j]; ksw[1][XS ? j : 0] = a.sw[(c0 + 1) * 7 + j]; ksh[XS ? j : 0] = a.sw[hc * 7 + j]; }
+        ksb[0] = a.sb[c0]; ksb[1] = a.sb[c0 + 1]; ksbh = a.sb[hc];
+    }
     const float hga = Cs[hc] * gs, hgb = Cs[64 + hc] * gs, hgc = Cs[128 + hc] * gs, hgl = Cs[192 + hc] * gs, hxa = Cs[256 + hc], hxb = Cs[320 + hc];
 
     // ---- split stages on a value pair (va, vb) -> pieces (p0, p1, [lo]) and a second pair (vc, vd) -> (q0_, q1_, [lo])
@@ -305,6 +342,18 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
         va = xx.x; vb = xx.y; vc = xx.z; vd = xx.w;
         asm volatile("" : "+v"(va), "+v"(vb), "+v"(vc), "+v"(vd));
     };
+    // XS: step e of channel j of unit u -- stem_fwd_kernel's chain to the letter: o = bias, then o = fmaf(w[k], s[t + k - 3], o), k = 0..6
+    // (a tap outside the clip multiplies the zero that was loaded; nothing is skipped, nothing regrouped)
+    auto xs_form = [&](int u, int j, int e) -> float {
+        const f32x3 g0 = sxl_[XS ? u : 0], g2 = sxr_[XS ? u : 0];
+        const f32x4 g1 = sxm_[XS ? u : 0];
+        const float g[10] = {g0[0], g0[1], g0[2], g1[0], g1[1], g1[2], g1[3], g2[0], g2[1], g2[2]};       // s[tq - 3 .. tq + 6]
+        float o = ksb[j];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) o = fmaf(ksw[j][XS ? k : 0], g[e + k], o);
+        asm volatile("" : "+v"(o));
+        return o;
+    };
     // image D wants channel pairs (c0, c0 + 1) at ONE time step; the pieces of a value do not depend on what it is paired with, so
     // they are taken from the time-pair dwords of the two channels with one v_perm each instead of splitting the gradient again
     auto d_out = [&](int u, int e) {
@@ -322,6 +371,12 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     // halos: the gradient's for image D (rows 0 and 65), the input operand's for image X' (elements XO - 1, XO + 64)
     auto hx_pick = [&]() {
         float v = hxv;
+        if (XS) {
+            const float g[8] = {hxq_[0][0], hxq_[0][1], hxq_[0][2], hxq_[0][3], hxq_[1][0], hxq_[1][1], hxq_[1][2], hxq_[1][3]};
+            v = ksbh;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) v = fmaf(ksh[XS ? k : 0], hh ? g[k + 1] : g[k], v);
+        }
         if (XPRO == PRO_BNRELU) v = pro_apply<PRO_BNRELU>(v, 0.f, hxa, hxb, 0.f);
         va = okh_cur ? v : 0.f; vb = 0.f;
         asm volatile("" : "+v"(va), "+v"(vb));
@@ -356,7 +411,10 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
     //   v 0..35  gradient: per (unit, channel) 9 slices: rebuild x 4 | pick | hi a | mid a + hi b | mid b | lo + write
     //   v 36..59 input:    per (unit, channel) 6 slices: pick (+ BN + ReLU) | hi a | mid a | hi b | mid b | lo + write
     //   v 60..63 input halo
-    constexpr int NSA = 64;
+    // XS (all 72 slices of the phase; the f16 build fetches no epilogue operand here):
+    //   v 36..67 input:    per (unit, channel) 8 slices: form a | form b | hi (a, b) | form c | form d | hi (c, d) | lo + write | -
+    //   v 68..71 input halo
+    constexpr int NSA = XS ? 72 : 64;
     auto sideA = [&](int v, unsigned short* G, unsigned short* X) __attribute__((always_inline)) {
         if (v < 36) {
             const int uj = v / 9, st = v % 9, u = uj >> 1, j = uj & 1;
@@ -369,7 +427,16 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
                 out4(G + (c0 + j) * PG + 4 * (q0 + 8 * u), 64 * PG);
                 gp_[u][j][0] = p0; gp_[u][j][1] = r0; gp_[u][j][2] = p1; gp_[u][j][3] = r1; gp_[u][j][4] = l0; gp_[u][j][5] = l1;
             }
-        } else if (v < 60) {
+        } else if (XS && v < 68) {
+            const int w = v - 36, uj = w / 8, st = w % 8, u = uj >> 1, j = uj & 1;
+            if (st == 0) va = xs_form(u, j, 0);
+            if (st == 1) vb = xs_form(u, j, 1);
+            if (st == 2) s1a();
+            if (st == 3) vc = xs_form(u, j, 2);
+            if (st == 4) vd = xs_form(u, j, 3);
+            if (st == 5) s1b();
+            if (st == 6) out4(X + (c0 + j) * PX + XO + 4 * (q0 + 8 * u), 64 * PX);
+        } else if (!XS && v < 60) {
             const int w = v - 36, uj = w / 6, st = w % 6, u = uj >> 1, j = uj & 1;
             if (st == 0) x_pick_t(u, j);
             if (st == 1) s1a();
@@ -378,7 +445,7 @@ __global__ __launch_bounds__(256) void dwgrad64bf_kernel(DWArgs a) {
             if (st == 4) s2b();
             if (st == 5) out4(X + (c0 + j) * PX + XO + 4 * (q0 + 8 * u), 64 * PX);
         } else {
-            const int st = v - 60;
+            const int st = v - (XS ? 68 : 60);
             if (st == 0) { hx_pick(); load_xhalo(); }
             if (st == 1) s1a();
             if (st == 2) s2a();
@@ -852,6 +919,23 @@ int wm_dwgrad64_bf_r1(const float* g, const float* g2, const float* ga, const fl
     else if (epi == EPI_ADD && xpro == PRO_NONE && g && !e1 && !stats)
         rc = launch_dwgrad64bf<EPI_ADD, PRO_NONE, true, true, true>(a, &grid, stream);
     if (rc) return rc;
+    return reduce_dwgrad_slabs(partial, grid, dw, dbias, accumulate, stream);
+}
+
+// wm_dwgrad64_bf's plain conv1 pair (xpro 0, epi 2, no gmask, arith 1) for the first block behind a stem: the weight-gradient operand
+// x = Conv1d(1, 64, 7, padding = 3)(s) is formed on load from the clips s [B,1,T] and the stem's stem_w [64,7], stem_b [64] instead
+// of being read.  e1 = the addend of the data gradient.  Everything else, and every result bit for bit, as wm_dwgrad64_bf on the
+// materialised x.  A null pointer (dzmax may be null) or T % 64 != 0 is hipErrorInvalidValue, and nothing is written.
+int wm_dwgrad64_bf_stem(const float* g, const float* g2, const float* ga, const float* gb, const float* gc, const void* wpb,
+                        const float* e1, float* y, float* partial, float* dw, float* dbias, int B, int T, int accumulate,
+                        const float* gscale, float* dzmax, const float* s, const float* stem_w, const float* stem_b,
+                        hipStream_t stream) {
+    if (B <= 0 || T <= 0 || (T & 63) || T >= (1 << 29)) return (int)hipErrorInvalidValue;            // clip offsets are 32-bit bytes
+    if (!g || !g2 || !ga || !gb || !gc || !wpb || !e1 || !y || !partial || !dw || !gscale || !s || !stem_w || !stem_b) return (int)hipErrorInvalidValue;
+    DWArgs a{g, g2, ga, gb, gc, wpb, nullptr, nullptr, nullptr, e1, nullptr, nullptr, y, nullptr, partial, B, T, nullptr,
+             nullptr, nullptr, gscale, dzmax, nullptr, nullptr, s, stem_w, stem_b};
+    int grid = 0;
+    if (int rc = launch_dwgrad64bf<EPI_ADD, PRO_STEM, false, true>(a, &grid, stream)) return rc;
     return reduce_dwgrad_slabs(partial, grid, dw, dbias, accumulate, stream);
 }
 }  // extern "C"

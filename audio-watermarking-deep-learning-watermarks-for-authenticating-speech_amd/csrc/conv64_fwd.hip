@@ -267,8 +267,10 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     constexpr int KW = 3, NT = 128, ROWS = NT + 2, PITCH = 72, NP = H ? 2 : 3, NC = 4;
     constexpr int XBUF = NP * ROWS * PITCH;               // bf16 elements per input image
     constexpr bool TAIL = (PRO == PRO_TAIL);              // the input is the previous ResBlock's tail, formed here from x and x2 = y2
+    constexpr bool STEM = (PRO == PRO_STEM);              // the input is the stem's output, formed here from the clips x = s [B,1,T]
+    constexpr bool FORM = TAIL || STEM;                   // the formed input also leaves through tout
     constexpr bool TWO = (PRO == PRO_BNBWD || TAIL);
-    static_assert(!TAIL || H, "the tail prologue exists in the f16 build only");
+    static_assert(!FORM || H, "the tail and stem prologues exist in the f16 build only");
     constexpr bool E1 = (EPI == EPI_RELUMASK || EPI == EPI_ADD || EPI == EPI_BNADDRELU);
     extern __shared__ __align__(16) unsigned char smem_raw[];
     unsigned short* Xb0 = reinterpret_cast<unsigned short*>(smem_raw);             // 2 x [NP][ROWS][PITCH]
@@ -304,10 +306,27 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     const int hc = (tid & 127) >> 1, hh = tid & 1;
     float4 sa[NC], sb[NC], sa2[TWO ? NC : 1], sb2[TWO ? NC : 1];
     float hl, hl2 = 0.f;
+    // PRO_STEM stages the clip instead of a frame: per combo the ten samples s[tq - 3 .. tq + 6] around its time quad tq as three
+    // loads out of the aligned quads at tq - 4, tq, tq + 4, per halo column the two quads that hold its seven taps.  Buffer loads over
+    // the clip's T samples: a quad outside [0, T) reads zero, which is the stem's padding (T % 128 == 0, so a quad is inside or
+    // outside as a whole; the one in front of the clip takes an offset past every clip instead of a negative one).  The signal is
+    // 1/64 of a frame and stays in L2.  Only what the taps read is loaded (s[tq - 4] and s[tq + 7] are not): a register that is loaded
+    // and never read is handed out again at once, and the write to it then waits for the load -- with the stores in front of it.
+    f32x3 sgl[STEM ? NC : 1], sgr[STEM ? NC : 1];
+    f32x4 sgm[STEM ? NC : 1], hg[2];
+    auto clip_srd = [&](int b) { return make_srd(a.x + (size_t)b * T, (size_t)T * sizeof(float)); };
     // global -> register staging of one tile, in five pieces (4 combos + halo) so that the main loop can issue them
     // a few at a time: a 32-KB burst per CU backs up the memory pipeline and blocks the wave at issue for ~2.5 K cycles
     auto load_combo = [&](int tile, int i) {
         const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
+        if (STEM) {
+            const wm_srd_t sc = clip_srd(b);
+            const int tq = t0 + 4 * (q0 + 8 * i);
+            sgl[STEM ? i : 0] = buf_load3(sc, tq >= 4 ? (unsigned)(tq - 3) * 4u : 0xFFFFFF00u, 0);
+            sgm[STEM ? i : 0] = buf_load4(sc, (unsigned)tq * 4u, 0);
+            sgr[STEM ? i : 0] = buf_load3(sc, (unsigned)(tq + 4) * 4u, 0);
+            return;
+        }
         const size_t o = ((size_t)b * 64 + c0) * T + t0 + 4 * (q0 + 8 * i);
         sa[i] = *reinterpret_cast<const float4*>(a.x + o);
         sb[i] = *reinterpret_cast<const float4*>(a.x + o + T);
@@ -315,6 +334,13 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     };
     auto load_halo = [&](int tile) {              // branch-free: clamped address, masked when written to LDS
         const int b = tile / tilesPerClip, t0 = (tile - b * tilesPerClip) * NT;
+        if (STEM) {                               // column t0 - 1: s[t0 - 4 .. t0 + 2]; column t0 + NT: s[t0 + NT - 3 .. t0 + NT + 3]
+            const wm_srd_t sc = clip_srd(b);
+            const int hq = hh ? t0 + NT - 4 : t0 - 4;
+            hg[0] = buf_load4(sc, hq >= 0 ? (unsigned)hq * 4u : 0xFFFFFF00u, 0);
+            hg[1] = buf_load4(sc, (unsigned)(hq + 4) * 4u, 0);
+            return;
+        }
         const int ht = min(max(hh ? t0 + NT : t0 - 1, 0), T - 1);
         hl = a.x[((size_t)b * 64 + hc) * T + ht];
         if (TWO) hl2 = a.x2[((size_t)b * 64 + hc) * T + ht];
@@ -348,11 +374,41 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     const float kc0 = Cs[128 + c0], kc1 = Cs[128 + c0 + 1];
     const float kl0 = (PRO == PRO_BNBWD) ? Cs[192 + c0] : 0.f, kl1 = (PRO == PRO_BNBWD) ? Cs[192 + c0 + 1] : 0.f;
     const float ha = Cs[hc], hb = Cs[64 + hc], hcc = Cs[128 + hc], hlo = (PRO == PRO_BNBWD) ? Cs[192 + hc] : 0.f;
+    // PRO_STEM: the seven taps and the bias of the two staging channels and of the halo channel (pa = the stem's w [64][7], pb = its bias)
+    float kw0[STEM ? 7 : 1], kw1[STEM ? 7 : 1], kwh[STEM ? 7 : 1], kbs0 = 0.f, kbs1 = 0.f, kbsh = 0.f;
+    if (STEM) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { kw0[STEM ? j : 0] = a.pa[c0 * 7 + j]; kw1[STEM ? j : 0] = a.pa[(c0 + 1) * 7 + j]; kwh[STEM ? j : 0] = a.pa[hc * 7 + j]; }
+        kbs0 = a.pb[c0]; kbs1 = a.pb[c0 + 1]; kbsh = a.pb[hc];
+    }
+    // stem_fwd_kernel's chain (small_convs.hip), to the letter: o = bias, then o = fmaf(w[j], s[t + j - 3], o) for j = 0..6 -- a tap
+    // outside the clip is a multiply by the zero that was loaded, never skipped
+    auto stem_form = [&](int i, int e, const float* w, float bias) -> float {
+        const f32x3 g0 = sgl[STEM ? i : 0], g2 = sgr[STEM ? i : 0];
+        const f32x4 g1 = sgm[STEM ? i : 0];
+        const float g[10] = {g0.x, g0.y, g0.z, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z};       // s[tq - 3 .. tq + 6]
+        float o = bias;
+        // the chain starts and ends at an opaque point of its own slice: left to the optimiser, the two channels' chains are paired into
+        // v_pk_fma_f32 (dearer beside MFMAs than the two v_fma_f32) and later elements' chains are hoisted out of their slices
+        asm volatile("" : "+v"(o));
+#pragma unroll
+        for (int j = 0; j < 7; ++j) o = fmaf(w[STEM ? j : 0], g[e + j], o);
+        asm volatile("" : "+v"(o));
+        return o;
+    };
+    auto stem_form_halo = [&]() -> float {
+        const float g[8] = {hg[0].x, hg[0].y, hg[0].z, hg[0].w, hg[1].x, hg[1].y, hg[1].z, hg[1].w};
+        float o = kbsh;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) o = fmaf(kwh[STEM ? j : 0], hh ? g[j + 1] : g[j], o);
+        return o;
+    };
 
     // PRO_TAIL: the formed value goes back into its staging register, and tail_store() writes the combo's two rows x one time quad
     // to `tout` as the tail kernel would have (16-B stores), with their sign bits: the eight lanes that share lane & 7 hold the 32
     // steps of one mask word of each row; lane >> 3 == 0 stores the first row's word, == 1 the second's (a null tmask: a descriptor
     // of zero bytes, every store dropped).  A halo column is rebuilt from x and x2 and never stored.
+    // PRO_STEM: the same two 16-B stores of the formed rows, no sign bits (nothing behind the stem clamps).
     auto keep_formed = [&](int i, int e, float va, float vb) {
         if (e == 0) { sa[i].x = va; sb[i].x = vb; } else if (e == 1) { sa[i].y = va; sb[i].y = vb; }
         else if (e == 2) { sa[i].z = va; sb[i].z = vb; } else { sa[i].w = va; sb[i].w = vb; }
@@ -362,6 +418,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         const size_t o = ((size_t)tb * 64 + c0) * T + tt0 + 4 * (q0 + 8 * i);
         *reinterpret_cast<float4*>(a.tout + o) = sa[i];
         *reinterpret_cast<float4*>(a.tout + o + T) = sb[i];
+        if (STEM) return;
         const unsigned ma = mask_merge8(sign_nibble(sa[i]) << (4 * q0)), mb = mask_merge8(sign_nibble(sb[i]) << (4 * q0));
         const unsigned word = (unsigned)(tb * 64 + c0 + (q0 & 1)) * (unsigned)(T >> 5) + (unsigned)((tt0 >> 5) + i);
         __builtin_amdgcn_raw_buffer_store_b32((q0 & 1) ? mb : ma, smask, (int)(q0 < 2 ? word * 4u : 0xFFFFFF00u), 0, 0);
@@ -372,7 +429,10 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         const float4 fa = sa[i], fb = sb[i];
         float va = (e == 0) ? fa.x : (e == 1) ? fa.y : (e == 2) ? fa.z : fa.w;
         float vb = (e == 0) ? fb.x : (e == 1) ? fb.y : (e == 2) ? fb.z : fb.w;
-        if (PRO != PRO_NONE) {
+        if (STEM) {
+            va = stem_form(i, e, kw0, kbs0); vb = stem_form(i, e, kw1, kbs1);
+            keep_formed(i, e, va, vb);
+        } else if (PRO != PRO_NONE) {
             float wa = 0.f, wb = 0.f;
             if (TWO) {
                 const float4 ga = sa2[i], gb = sb2[i];
@@ -398,7 +458,8 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         {                                             // threads 128..255 repeat the writes of 0..127 (no branch)
             const int t = hh ? t0 + NT : t0 - 1;
             float v = hl;
-            if (PRO != PRO_NONE) v = pro_apply<PRO>(v, hl2, ha, hb, hcc, hlo);
+            if (STEM) v = stem_form_halo();
+            else if (PRO != PRO_NONE) v = pro_apply<PRO>(v, hl2, ha, hb, hcc, hlo);
             if (t < 0 || t >= T) v = 0.f;
             const int o = (hh ? NT + 1 : 0) * PITCH + hc;
             if (H) {
@@ -433,6 +494,16 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
         sva = va; svb = vb;
         asm volatile("" : "+v"(sva), "+v"(svb));
     };
+    // PRO_STEM's pick in two slices, one seven-FMA chain each: the first channel, then the second and the hand-over
+    auto stem_pick_a = [&](int i, int e) {
+        sva = stem_form(i, e, kw0, kbs0);
+        asm volatile("" : "+v"(sva));
+    };
+    auto stem_pick_b = [&](int i, int e) {
+        svb = stem_form(i, e, kw1, kbs1);
+        keep_formed(i, e, sva, svb);
+        asm volatile("" : "+v"(sva), "+v"(svb));
+    };
     auto split_st1 = [&]() {
         if (H) {
             const h16x2 hh_ = __builtin_convertvector(f32x2{sva, svb}, h16x2);
@@ -465,7 +536,8 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
     auto halo_pick = [&](int t0) {
         const int t = hh ? t0 + NT : t0 - 1;
         float v = hl;
-        if (PRO != PRO_NONE) v = pro_apply<PRO>(v, hl2, ha, hb, hcc, hlo);
+        if (STEM) v = stem_form_halo();
+        else if (PRO != PRO_NONE) v = pro_apply<PRO>(v, hl2, ha, hb, hcc, hlo);
         if (t < 0 || t >= T) v = 0.f;
         sva = v; svb = 0.f;
         asm volatile("" : "+v"(sva), "+v"(svb));
@@ -480,7 +552,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
 #pragma unroll
         for (int u = 0; u < 16; ++u) split_unit(reinterpret_cast<unsigned*>(Xb0), t0, u >> 2, u & 3);
         split_halo(Xb0, t0);
-        if (TAIL) {
+        if (FORM) {
 #pragma unroll
             for (int i = 0; i < NC; ++i) tail_store(min(tile, ntiles - 1) / tilesPerClip, t0, i);
         }
@@ -585,7 +657,12 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
 #define FENCE __builtin_amdgcn_sched_barrier(0)
 #define BF3_SLICE(k)                                                                                                        \
     {                                                                                                                           \
-        if (h < 16) {                                                                                                           \
+        if (STEM && h < 16) {                                                                                                   \
+            if ((k) == 0) stem_pick_a(h >> 2, h & 3);                                                                           \
+            if ((k) == 1) stem_pick_b(h >> 2, h & 3);                                                                           \
+            if ((k) == 2) { split_st1(); if ((h & 3) == 3) tail_store(nb_, nt0, h >> 2); }                                      \
+            if ((k) == 3) { split_out(reinterpret_cast<unsigned*>(xnxt), h >> 2, h & 3); if ((h & 3) == 3) load_combo(next2, h >> 2); } \
+        } else if (h < 16) {                                                                                                    \
             if ((k) == 0) split_pick(h >> 2, h & 3);                                                                            \
             if ((k) == 1) split_st1();                                                                                          \
             if ((k) == 2) { split_st2(); if (TAIL && (h & 3) == 3) tail_store(nb_, nt0, h >> 2); }                              \
@@ -616,7 +693,7 @@ __global__ __launch_bounds__(256) void conv64bf3_kernel(Conv64Args a) {
             FENCE;
             if (H) {                                     // lo hi, hi lo, hi hi: two slices behind every MFMA
                 acc[nt] = mma(Wr[s][1], Bf[0], acc[nt]); FENCE; BF3_SLICE(0) FENCE; BF3_SLICE(1) FENCE;
-                if (TAIL) {                              // slice 2 (free in this build) stores a finished combo of the formed tile
+                if (FORM) {                              // slice 2 (free in this build) stores a finished combo of the formed tile
                     acc[nt] = mma(Wr[s][0], Bf[1], acc[nt]); FENCE; BF3_SLICE(2) FENCE; BF3_SLICE(3) FENCE;
                     acc[nt] = mma(Wr[s][0], Bf[0], acc[nt]); FENCE; BF3_SLICE(4) FENCE; BF3_SLICE(5) FENCE;
                 } else {
@@ -886,6 +963,19 @@ int wm_conv64_bf_tail(const float* x, const float* y2, const void* wpb_h, const 
     Conv64Args a{x, y2, reinterpret_cast<const float*>(wpb_h), sc2, sh2, nullptr, bias, nullptr, nullptr, nullptr, y, stats, B, T,
                  out, reinterpret_cast<unsigned*>(mask)};
     return launch_conv64bf3<PRO_TAIL, EPI_BIAS, true, true>(a, stream);
+}
+
+// The first training ResBlock's conv1 with the stem in front formed on load: y0 = Conv1d(1, 64, 7, padding = 3)(s) leaves as a side
+// product exactly as wm_stem_fwd writes it, y = conv(y0) + bias and stats exactly as wm_conv64_bf(pro 0, epi 0, arith 1) on that y0.
+// s [B,1,T], stem_w [64,7], stem_b [64]; wpb_h from wm_pack_w64_h (mode 0).  wm_conv64_bf_tail's conditions: anything else
+// (T % 128 != 0, schedule 0, a null pointer) is hipErrorInvalidValue and nothing is written.
+int wm_conv64_bf_stem(const float* s, const float* stem_w, const float* stem_b, const void* wpb_h, const float* bias, float* y0,
+                      float* y, float* stats, int B, int T, hipStream_t stream) {
+    if (B <= 0 || T <= 0 || (T & 127) || T >= (1 << 29) || g_bf_schedule != 2) return (int)hipErrorInvalidValue;   // clip offsets are 32-bit bytes
+    if (!s || !stem_w || !stem_b || !wpb_h || !y0 || !y || !stats) return (int)hipErrorInvalidValue;
+    Conv64Args a{s, nullptr, reinterpret_cast<const float*>(wpb_h), stem_w, stem_b, nullptr, bias, nullptr, nullptr, nullptr, y, stats, B, T,
+                 y0, nullptr};
+    return launch_conv64bf3<PRO_STEM, EPI_BIAS, true, true>(a, stream);
 }
 
 // f16 two-piece weight image for wm_dwgrad64_bf arith 1: 2 * 3 * 4096 f16 + 2 floats (mode 0 forward | 1 data gradient, as wm_pack_w64_bf)

@@ -76,12 +76,18 @@ class Generator(nn.Module):
         self.decoder = nn.Sequential(nn.ConvTranspose1d(64, 64, 7, padding=3), ResBlock(64), _Head1(64, 1, 1))
 
     def forward(self, s, message=None):
-        e1, e2, x = self.encoder[1], self.encoder[2], self.encoder[0](s)         # (B,64,T)
+        stem, e1, e2 = self.encoder
         lstm = (self.lstm.weight_ih_l0, self.lstm.weight_hh_l0, self.lstm.bias_ih_l0, self.lstm.bias_hh_l0)
-        if (e1.training and e2.training and not _hooked(self.encoder, e1, e2, self.lstm) and ops.tail_in_consumer_applies(x, lstm=True)):
-            x = ops.EncoderLSTMFn.apply(x, *_rb_args(e1), *_rb_args(e2), *lstm)  # both tails ride in the kernels that read them next
+        fold = e1.training and e2.training and not _hooked(self.encoder, e1, e2, self.lstm)
+        if fold and not _hooked(stem) and ops.stem_in_conv1_applies(s, lstm=True):
+            # the stem's output is formed by encoder.1's conv1 launch; both tails ride in the kernels that read them next
+            x = ops.StemEncoderLSTMFn.apply(s, stem.weight, stem.bias, *_rb_args(e1), *_rb_args(e2), *lstm)
         else:
-            x = ops.LSTMFn.apply(resblock_pair(e1, e2, x), *lstm)
+            x = stem(s)                                                          # (B,64,T)
+            if fold and ops.tail_in_consumer_applies(x, lstm=True):
+                x = ops.EncoderLSTMFn.apply(x, *_rb_args(e1), *_rb_args(e2), *lstm)  # both tails ride in the kernels that read them next
+            else:
+                x = ops.LSTMFn.apply(resblock_pair(e1, e2, x), *lstm)
         vec = None
         if self.message_bits > 0 and message is not None:
             if message.dim() != 1 or message.shape[0] != s.shape[0]:
@@ -113,8 +119,12 @@ class Detector(nn.Module):
     def forward(self, x, input_grad_rows=None):
         """`input_grad_rows` (optional, not in the reference): only clips [0, input_grad_rows) get an input gradient --
         the train step feeds [watermarked; clean] (py/main16.py:249) and the clean half is data."""
-        x = self.model[0](x) if input_grad_rows is None else self.model[0](x, input_grad_rows)
-        return self.model[3](resblock_pair(self.model[1], self.model[2], x))
+        stem, m1, m2, head = self.model
+        if m1.training and m2.training and not _hooked(stem, m1, m2) and ops.stem_in_conv1_applies(x):
+            # the stem's output is formed by model.1's conv1 launch
+            return head(ops.StemResBlockPairFn.apply(x, stem.weight, stem.bias, input_grad_rows, *_rb_args(m1), *_rb_args(m2), True))
+        x = stem(x) if input_grad_rows is None else stem(x, input_grad_rows)
+        return head(resblock_pair(m1, m2, x))
 
     def forward_with_losses(self, x, message, input_grad_rows=None):
         """(logits, loc, bce) = (self(x), *detection_losses(self(x), message)) as one tape node behind the stem (ops.DetectorTailFn), or
@@ -126,7 +136,11 @@ class Detector(nn.Module):
               and message.dtype == torch.int64 and message.dim() == 1 and x.shape[0] == 2 * message.shape[0])
         if not ok:
             return None
-        x = self.model[0](x) if input_grad_rows is None else self.model[0](x, input_grad_rows)
+        stem = self.model[0]
+        if not _hooked(stem) and ops.stem_in_conv1_applies(x):                  # the stem's output is formed by model.1's conv1 launch
+            return ops.StemDetectorTailFn.apply(x, stem.weight, stem.bias, input_grad_rows, message.contiguous(), *_rb_args(m1),
+                                                *_rb_args(m2), head.weight, head.bias)
+        x = stem(x) if input_grad_rows is None else stem(x, input_grad_rows)
         return ops.DetectorTailFn.apply(x, message.contiguous(), *_rb_args(m1), *_rb_args(m2), head.weight, head.bias)
 
 

@@ -381,6 +381,42 @@ def tail_in_consumer_applies(x, lstm: bool = False) -> bool:
     return _tail_in_consumer_launches(x, lstm) and bool(pair_node_applies(x))
 
 
+# The stem's output y0 = Conv1d(1, 64, 7, padding=3)(s) is formed by the first ResBlock's conv1 launch while it stages its input
+# (wm_conv64_bf_stem, which also writes y0 for the second block's conv1) and by that block's conv1 pair in the backward
+# (wm_dwgrad64_bf_stem): no wm_stem_fwd launch, two frame passes less per network.  WM_STEM_IN_CONV1=0/1 sets the default ("1" = on,
+# else off).  Kept outside SWITCHES like _TAILC.
+def read_stem_in_conv1(environ) -> bool:
+    """what the switch starts with under `environ` (pure, as read_switches)"""
+    return environ.get("WM_STEM_IN_CONV1", "1") == "1"
+
+
+_STEMC = {"on": read_stem_in_conv1(os.environ)}
+
+
+def set_stem_in_conv1(on: bool):
+    """1 (default): the nodes behind a stem take the clips and the stem's parameters (StemEncoderLSTMFn, StemDetectorTailFn,
+    StemResBlockPairFn) where stem_in_conv1_applies(); 0: StemFn in front of the nodes of today.  Bit-identical either way: the formed
+    element is stem_fwd_kernel's own fmaf chain, no sum is regrouped."""
+    _STEMC["on"] = bool(on)
+
+
+def _stem_in_conv1_launches(s) -> bool:
+    """the switch and what wm_conv64_bf_stem needs: the tail-in-consumer launches' conditions on a [B,1,T] fp32 clip batch.  What a
+    tape node asks inside its forward, where autograd has gradients switched off."""
+    return bool(_STEMC["on"] and s.dim() == 3 and s.shape[1] == 1 and s.dtype == torch.float32 and _tail_in_consumer_launches(s))
+
+
+def stem_in_conv1_applies(s, lstm: bool = False) -> bool:
+    """_stem_in_conv1_launches and the nodes' own precondition: tail_in_consumer_applies (so: gradients wanted, the fused backward, no
+    side-stream weight gradients).  The caller adds: training-mode blocks, no forward hooks on the stem and the blocks."""
+    return _stem_in_conv1_launches(s) and tail_in_consumer_applies(s, lstm)
+
+
+def _stem_in_dwgrad_launches(x) -> bool:
+    """what wm_dwgrad64_bf_stem needs beyond the switch: the fused backward in its f16 build (asked in a node's backward)"""
+    return bool(_STEMC["on"] and _CONV["bwd_f16x3"] and x.shape[-1] % 64 == 0)
+
+
 def set_gconv_f16x3(on: bool):
     """generic convolution family (wm_gconv: forward, transposed, data gradients) for layers with Cin % 16 == 0: 1 (default) the f16
     two-piece split on the f16 matrix cores (wm_gconv_h; weights scaled by 2^8, a gradient input from max |g|, an activation from max |x|
@@ -476,18 +512,26 @@ def pack_w64(w: torch.Tensor, kw: int, mode: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ ResBlock
-def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None):
+def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None, stem=None):
     """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for params = (w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2).
     Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx.
     tail=False (training mode only): stop in front of the tail -- (None, saved) with mask = None; the kernel that follows forms
     out = relu(x + y2 * cst[4] + cst[5]) and the mask (ResBlockHead1Fn, DetectorTailFn, or the next block through `pending`).
     pending (training mode, tail_in_consumer_applies): the `saved` of the block in front, run with tail=False; x is ignored.  This
     block's conv1 launch (wm_conv64_bf_tail) forms that block's tail on load and writes it -- this block's x -- and its mask; the
-    return value is then (out, saved, that mask)."""
+    return value is then (out, saved, that mask).
+    stem = (s, w, b) of the Conv1d(1, 64, 7) in front (x is ignored): this block's x is that stem's output, formed and written by the
+    conv1 launch itself (wm_conv64_bf_stem) where _stem_in_conv1_launches(s) in training mode, else by wm_stem_fwd first."""
     w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = params
     if pending is not None:
         px, py2, pcst = pending[0], pending[2], pending[4]
         x, pmask = torch.empty_like(px), _tail_mask(px, want_grad)
+    if stem is not None:
+        ss, sw, sb = stem
+        x = _f32(ss.shape[0], 64, ss.shape[2], device=ss.device)
+        if not (training and _stem_in_conv1_launches(ss)):
+            lib.wm_stem_fwd(_p(ss), _p(sw), _p(sb), _p(x), ss.shape[0], ss.shape[2], _stream())
+            stem = None
     x = _frames(x, "ResBlock input", 64)
     B, _, T = x.shape
     dev, st = x.device, _stream()
@@ -500,6 +544,8 @@ def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None):
         if pending is not None:
             lib.wm_conv64_bf_tail(_p(px), _p(py2), _p(pack_w64_h(w1, 0)), _p(pcst[4]), _p(pcst[5]), _p(b1), _p(x), _p(pmask), _p(y1),
                                   _p(stats), B, T, st)
+        elif stem is not None:
+            lib.wm_conv64_bf_stem(_p(ss), _p(sw), _p(sb), _p(pack_w64_h(w1, 0)), _p(b1), _p(x), _p(y1), _p(stats), B, T, st)
         else:
             _conv3(x, None, w1, 0, None, None, None, b1, None, None, None, y1, stats, B, T, 0, 0)
         lib.wm_bn_finalize(_p(stats), NCU, float(B * T), _p(g1), _p(be1), _p(rm1), _p(rv1), _p(nbt1), BN_MOMENTUM, BN_EPS,
@@ -607,7 +653,7 @@ def _resblock_bwd(saved, training, gdst, g_out):
     return (dx,) + g1_ + (dg1, dbe1) + g2_ + (dg2, dbe2)
 
 
-def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None):
+def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None, stem=None):
     """Backward of one ResBlock on the fused path (data + weight gradient of each convolution in one launch, T % 64 == 0).
     g_out: gradient w.r.t. the block output.  `pre` = (stats partials [NCU,2,64], max |dz| per workgroup [NCU]) when g_out ALREADY is
     dz2 = g (out > 0) and its two BatchNorm sums exist (made by the next block's folded conv1 launch): no reduction pass, no mask.
@@ -615,6 +661,8 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None)
     gradient and returns (its BatchNorm-sum partials, its max |dz| per workgroup) as the third value.
     `rank1` = (g1 [B,1,T], hw [1,64,1]) with g_out None: the gradient w.r.t. the block output is hw[c] g1[b,t] and is formed on load
     (head1_rank1_applies; neither `pre` nor `fold`).
+    `stem` = (s, w, b) of the Conv1d(1, 64, 7) whose output is this block's x (with `pre`): where _stem_in_dwgrad_launches, the conv1
+    pair forms its weight-gradient operand from them instead of reading x (wm_dwgrad64_bf_stem).
     Returns (dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fold outputs | None)."""
     x, y1, y2, mask, cst, w1, w2, g1, g2 = saved
     sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
@@ -683,6 +731,9 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None)
             lib.wm_dwgrad64_bf_r1(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
                                   None, None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax),
                                   _p(r1g), _p(r1w), st)
+        elif stem is not None and gm is None and _stem_in_dwgrad_launches(x):
+            lib.wm_dwgrad64_bf_stem(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(gsrc), _p(dx), _p(wpart),
+                                    _p(dw1), _p(db1), B, T, 0, _p(gs1), _p(xmax), _p(stem[0]), _p(stem[1]), _p(stem[2]), st)
         else:
             lib.wm_dwgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
                                _p(gsrc), None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax), st)
@@ -697,15 +748,15 @@ def pair_node_applies(x) -> bool:
             and _CONV["fused_bwd"] and _CONV["mask_on_load"] and _CONV["pair_fold"] and not _ASYNC["on"])
 
 
-def _pair_fwd(x, p1, p2, training, want_grad, tail=True):
+def _pair_fwd(x, p1, p2, training, want_grad, tail=True, stem=None):
     """Two ResBlocks in a row, the second one up to `tail` (as _resblock_fwd's): (out | None, first, second), the two blocks' `saved`.
     Where the tail-in-consumer launches apply, the first block's tail is formed by the second block's conv1 launch; same tensors
-    either way."""
-    if training and _tail_in_consumer_launches(x):
-        _, first = _resblock_fwd(x, p1, True, want_grad, tail=False)
+    either way.  stem: _resblock_fwd's, for the first block (x is then ignored)."""
+    if training and _tail_in_consumer_launches(x if stem is None else stem[0]):
+        _, first = _resblock_fwd(x, p1, True, want_grad, tail=False, stem=stem)
         out, second, pmask = _resblock_fwd(None, p2, True, want_grad, tail=tail, pending=first)
         return out, first[:3] + (pmask,) + first[4:], second
-    mid, first = _resblock_fwd(x, p1, training, want_grad)
+    mid, first = _resblock_fwd(x, p1, training, want_grad, stem=stem)
     out, second = _resblock_fwd(mid, p2, training, want_grad, tail=tail)
     return out, first, second
 
@@ -719,20 +770,57 @@ class ResBlockPairFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, *args):
-        p1, p2, training = args[:14], args[14:28], args[28]
-        out, first, second = _pair_fwd(x, p1, p2, training, wants_grad(ctx))
-        ctx.save_for_backward(*(first + second))
-        ctx.training = bool(training)
-        return out
+        return _pair_node_fwd(ctx, x, args, None)
 
     @staticmethod
     def backward(ctx, g_out):
-        sv = ctx.saved_tensors
-        s1_, s2_ = sv[:9], sv[9:]
-        g_out = g_out.contiguous()
-        dmid, grads2, fout = _resblock_bwd_fused(s2_, ctx.training, g_out, fold=(s1_[3], s1_[2]))
-        dx, grads1, _ = _resblock_bwd_fused(s1_, ctx.training, dmid, pre=fout)
-        return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (None,)
+        return _pair_node_bwd(ctx, g_out, None)
+
+
+def _pair_node_fwd(ctx, x, args, stem):
+    p1, p2, training = args[:14], args[14:28], args[28]
+    out, first, second = _pair_fwd(x, p1, p2, training, wants_grad(ctx), stem=stem)
+    ctx.save_for_backward(*(first + second + (stem or ())))
+    ctx.training = bool(training)
+    return out
+
+
+def _pair_node_bwd(ctx, g_out, stem):
+    sv = ctx.saved_tensors
+    s1_, s2_ = sv[:9], sv[9:18]
+    g_out = g_out.contiguous()
+    dmid, grads2, fout = _resblock_bwd_fused(s2_, ctx.training, g_out, fold=(s1_[3], s1_[2]))
+    dx, grads1, _ = _resblock_bwd_fused(s1_, ctx.training, dmid, pre=fout, stem=stem)
+    return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (None,)
+
+
+def _stem_of(ctx):
+    """the (s, w, b) a Stem* node saved behind everything else"""
+    return tuple(ctx.saved_tensors[-3:])
+
+
+def _behind_stem(ctx, grads, extra=0):
+    """a Stem* node's backward from its plain twin's `grads` = (dx of the first block, ...): wm_stem_bwd on dx exactly as
+    StemFn.backward runs it -> (ds, dw, db) + `extra` Nones + the rest"""
+    s, w, _ = _stem_of(ctx)
+    return _stem_bwd(s, w, grads[0], ctx.grad_rows, ctx.needs_input_grad[0]) + (None,) * extra + grads[1:]
+
+
+class StemResBlockPairFn(GradAwareFunction):
+    """model.0 -> model.1 -> model.2 (py/main16.py:177-179) as one tape node where stem_in_conv1_applies(s): ResBlockPairFn on the
+    stem's output, which model.1's conv1 launch forms from the clips and writes (wm_conv64_bf_stem), and which model.1's conv1 pair in
+    the backward forms again instead of reading it (wm_dwgrad64_bf_stem).  Inputs (s, stem w, stem b, grad_rows | None, ...
+    ResBlockPairFn's); backward = ResBlockPairFn's, then StemFn's."""
+
+    @staticmethod
+    def forward(ctx, s, sw, sb, grad_rows, *args):
+        s = _frames(s, "clip batch", 1)
+        ctx.grad_rows = _stem_grad_rows(grad_rows, s.shape[0])
+        return _pair_node_fwd(ctx, None, args, (s, sw, sb))
+
+    @staticmethod
+    def backward(ctx, g_out):
+        return _behind_stem(ctx, _pair_node_bwd(ctx, g_out, _stem_of(ctx)), extra=1)
 
 
 # ------------------------------------------------------------------------------------------ stem / heads
@@ -746,21 +834,30 @@ class StemFn(torch.autograd.Function):
         y = _f32(B, 64, T, device=s.device)
         lib.wm_stem_fwd(_p(s), _p(w), _p(b), _p(y), B, T, _stream())
         ctx.save_for_backward(s, w)
-        ctx.grad_rows = B if grad_rows is None else max(0, min(int(grad_rows), B))
+        ctx.grad_rows = _stem_grad_rows(grad_rows, B)
         return y
 
     @staticmethod
     def backward(ctx, g):
         s, w = ctx.saved_tensors
-        g = g.contiguous()
-        B, _, T = s.shape
-        ds = None
-        if ctx.needs_input_grad[0]:        # rows >= grad_rows are known not to need a gradient (the clean half): left zero
-            ds = torch.empty_like(s) if ctx.grad_rows == B else torch.zeros_like(s)
-        part = _f32(2 * NCU * 512, device=s.device)
-        dw, db = torch.empty_like(w), _f32(64, device=s.device)
-        lib.wm_stem_bwd(_p(g), _p(s), _p(w), _p(ds), _p(part), _p(dw), _p(db), B, T, ctx.grad_rows, 0, _stream())
-        return ds, dw, db, None
+        return _stem_bwd(s, w, g, ctx.grad_rows, ctx.needs_input_grad[0]) + (None,)
+
+
+def _stem_grad_rows(grad_rows, B):
+    return B if grad_rows is None else max(0, min(int(grad_rows), B))
+
+
+def _stem_bwd(s, w, g, grad_rows, need_ds):
+    """StemFn's backward launch on the gradient g of the stem's output: (ds | None, dw, db)"""
+    g = g.contiguous()
+    B, _, T = s.shape
+    ds = None
+    if need_ds:                            # rows >= grad_rows are known not to need a gradient (the clean half): left zero
+        ds = torch.empty_like(s) if grad_rows == B else torch.zeros_like(s)
+    part = _f32(2 * NCU * 512, device=s.device)
+    dw, db = torch.empty_like(w), _f32(64, device=s.device)
+    lib.wm_stem_bwd(_p(g), _p(s), _p(w), _p(ds), _p(part), _p(dw), _p(db), B, T, grad_rows, 0, _stream())
+    return ds, dw, db
 
 
 class Head1Fn(torch.autograd.Function):
@@ -873,45 +970,69 @@ class DetectorTailFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, message, *args):
-        p1, p2, hw, hb = args[:14], args[14:28], args[28], args[29]
-        want = wants_grad(ctx)
-        _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False)
-        mid, y2, cst = second[0], second[2], second[4]
-        R, _, T = mid.shape
-        NO, B, dev = hw.shape[0], message.shape[0], mid.device
-        out, mask = torch.empty_like(mid), _tail_mask(mid, want)
-        logits = _f32(R, T, NO, device=dev)
-        part = _f32(2 * R * ((T + 255) // 256), device=dev)
-        losses = torch.zeros(2, dtype=torch.float32, device=dev)
-        lib.wm_headN_tail_fwd(_p(mid), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(message), B, _p(part), _p(losses[0]), _p(losses[1]),
-                              _p(out), _p(mask), _p(logits), R, T, NO, _stream())
-        ctx.set_materialize_grads(False)
-        if want:
-            ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + (out, hw, logits, message)))
-        return logits, losses[0], losses[1]
+        return _detector_tail_fwd(ctx, x, message, args, None)
 
     @staticmethod
     def backward(ctx, g_logits, g_loc, g_bce):
-        sv = ctx.saved_tensors
-        s1_, s2_, (out, hw, logits, message) = sv[:9], sv[9:18], sv[18:]
-        R, T, NO = logits.shape
-        dev, st = logits.device, _stream()
-        gl = g_loc.contiguous().float().reshape(1) if g_loc is not None else torch.zeros(1, device=dev)
-        gb = g_bce.contiguous().float().reshape(1) if g_bce is not None else torch.zeros(1, device=dev)
-        dout = torch.empty_like(out)
-        part = _f32(NCU * (NO * 64 + NO), device=dev)
-        dhw, dhb = torch.empty_like(hw), _f32(NO, device=dev)
-        if g_logits is None:
-            lib.wm_headN_bwd_bce(_p(logits), _p(message), _p(gl), _p(gb), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb),
-                                 message.shape[0], R, T, NO, 0, st)
-        else:
-            d = torch.empty_like(logits)
-            lib.wm_bce_bwd(_p(logits), _p(message), _p(gl), _p(gb), _p(d), message.shape[0], R, T, NO, st)
-            d += g_logits
-            lib.wm_headN_bwd(_p(d), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), R, T, NO, 0, st)
-        dmid, grads2, fout = _resblock_bwd_fused(s2_, True, dout, fold=(s1_[3], s1_[2]))
-        dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout)
-        return (dx, None) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (dhw, dhb)
+        return _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, None)
+
+
+class StemDetectorTailFn(GradAwareFunction):
+    """model.0 in front of DetectorTailFn as one tape node where stem_in_conv1_applies(s): as StemResBlockPairFn.  Inputs (s, stem w,
+    stem b, grad_rows | None, message, ... DetectorTailFn's); backward = DetectorTailFn's, then StemFn's."""
+
+    @staticmethod
+    def forward(ctx, s, sw, sb, grad_rows, message, *args):
+        s = _frames(s, "clip batch", 1)
+        ctx.grad_rows = _stem_grad_rows(grad_rows, s.shape[0])
+        return _detector_tail_fwd(ctx, None, message, args, (s, sw, sb))
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loc, g_bce):
+        grads = _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, _stem_of(ctx))
+        return _behind_stem(ctx, grads[:1] + grads[2:], extra=2)          # (grad_rows, message: none)
+
+
+def _detector_tail_fwd(ctx, x, message, args, stem):
+    p1, p2, hw, hb = args[:14], args[14:28], args[28], args[29]
+    want = wants_grad(ctx)
+    _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False, stem=stem)
+    mid, y2, cst = second[0], second[2], second[4]
+    R, _, T = mid.shape
+    NO, B, dev = hw.shape[0], message.shape[0], mid.device
+    out, mask = torch.empty_like(mid), _tail_mask(mid, want)
+    logits = _f32(R, T, NO, device=dev)
+    part = _f32(2 * R * ((T + 255) // 256), device=dev)
+    losses = torch.zeros(2, dtype=torch.float32, device=dev)
+    lib.wm_headN_tail_fwd(_p(mid), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(message), B, _p(part), _p(losses[0]), _p(losses[1]),
+                          _p(out), _p(mask), _p(logits), R, T, NO, _stream())
+    ctx.set_materialize_grads(False)
+    if want:
+        ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + (out, hw, logits, message) + (stem or ())))
+    return logits, losses[0], losses[1]
+
+
+def _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, stem):
+    sv = ctx.saved_tensors
+    s1_, s2_, (out, hw, logits, message) = sv[:9], sv[9:18], sv[18:22]
+    R, T, NO = logits.shape
+    dev, st = logits.device, _stream()
+    gl = g_loc.contiguous().float().reshape(1) if g_loc is not None else torch.zeros(1, device=dev)
+    gb = g_bce.contiguous().float().reshape(1) if g_bce is not None else torch.zeros(1, device=dev)
+    dout = torch.empty_like(out)
+    part = _f32(NCU * (NO * 64 + NO), device=dev)
+    dhw, dhb = torch.empty_like(hw), _f32(NO, device=dev)
+    if g_logits is None:
+        lib.wm_headN_bwd_bce(_p(logits), _p(message), _p(gl), _p(gb), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb),
+                             message.shape[0], R, T, NO, 0, st)
+    else:
+        d = torch.empty_like(logits)
+        lib.wm_bce_bwd(_p(logits), _p(message), _p(gl), _p(gb), _p(d), message.shape[0], R, T, NO, st)
+        d += g_logits
+        lib.wm_headN_bwd(_p(d), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), R, T, NO, 0, st)
+    dmid, grads2, fout = _resblock_bwd_fused(s2_, True, dout, fold=(s1_[3], s1_[2]))
+    dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout, stem=stem)
+    return (dx, None) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (dhw, dhb)
 
 
 # ------------------------------------------------------------------------------------------ LSTM
@@ -1004,26 +1125,49 @@ class EncoderLSTMFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, *args):
-        p1, p2, (w_ih, w_hh, b_ih, b_hh) = args[:14], args[14:28], args[28:32]
-        want = wants_grad(ctx)
-        _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False)
-        mid, y2, cst = second[0], second[2], second[4]
-        mask = _tail_mask(mid, want)
-        h, lsaved = _lstm_fwd(None, w_ih, w_hh, b_ih, b_hh, want, tail=(mid, y2, cst[4], cst[5], mask))
-        if want:
-            ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
-            ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + lsaved))
-        return h
+        return _encoder_lstm_fwd(ctx, x, args, None)
 
     @staticmethod
     def backward(ctx, dh):
-        sv = ctx.saved_tensors
-        _single_backward(ctx, "EncoderLSTMFn")
-        s1_, s2_ = sv[:9], sv[9:18]
-        lgrads = _lstm_bwd(sv[18:], ctx.gdst, dh, dx_inside=_LSTM_DX["in_bwd"])
-        dmid, grads2, fout = _resblock_bwd_fused(s2_, True, lgrads[0], fold=(s1_[3], s1_[2]))
-        dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout)
-        return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + lgrads[1:]
+        return _encoder_lstm_bwd(ctx, dh, None)
+
+
+class StemEncoderLSTMFn(GradAwareFunction):
+    """encoder.0 in front of EncoderLSTMFn as one tape node where stem_in_conv1_applies(s, lstm=True): as StemResBlockPairFn.  Inputs
+    (s, stem w, stem b, ... EncoderLSTMFn's); backward = EncoderLSTMFn's, then StemFn's."""
+
+    @staticmethod
+    def forward(ctx, s, sw, sb, *args):
+        s = _frames(s, "clip batch", 1)
+        ctx.grad_rows = s.shape[0]
+        return _encoder_lstm_fwd(ctx, None, args, (s, sw, sb))
+
+    @staticmethod
+    def backward(ctx, dh):
+        return _behind_stem(ctx, _encoder_lstm_bwd(ctx, dh, _stem_of(ctx)))
+
+
+def _encoder_lstm_fwd(ctx, x, args, stem):
+    p1, p2, (w_ih, w_hh, b_ih, b_hh) = args[:14], args[14:28], args[28:32]
+    want = wants_grad(ctx)
+    _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False, stem=stem)
+    mid, y2, cst = second[0], second[2], second[4]
+    mask = _tail_mask(mid, want)
+    h, lsaved = _lstm_fwd(None, w_ih, w_hh, b_ih, b_hh, want, tail=(mid, y2, cst[4], cst[5], mask))
+    if want:
+        ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
+        ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + lsaved + (stem or ())))
+    return h
+
+
+def _encoder_lstm_bwd(ctx, dh, stem):
+    sv = ctx.saved_tensors
+    _single_backward(ctx, "EncoderLSTMFn")
+    s1_, s2_ = sv[:9], sv[9:18]
+    lgrads = _lstm_bwd(sv[18:24], ctx.gdst, dh, dx_inside=_LSTM_DX["in_bwd"])
+    dmid, grads2, fout = _resblock_bwd_fused(s2_, True, lgrads[0], fold=(s1_[3], s1_[2]))
+    dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout, stem=stem)
+    return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + lgrads[1:]
 
 
 # ------------------------------------------------------------------------------------------ embedding + convT

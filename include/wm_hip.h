@@ -78,6 +78,14 @@ int wm_conv64_bf(const float* x, const float* x2, const void* wpb, const float* 
 int wm_conv64_bf_tail(const float* x, const float* y2, const void* wpb_h, const float* sc2, const float* sh2, const float* bias,
                       float* out, void* mask, float* y, float* stats, int B, int T, wm_stream_t stream);
 
+/* The first training ResBlock's conv1 with the stem Conv1d(1, 64, 7, padding = 3) formed on load (py/main16.py:134-135, :177-178)
+ * instead of a wm_stem_fwd launch of its own: the clips s [B,1,T] are read in place of a frame, y0 [B,64,T] = the stem's output is
+ * written as a side product, bit for bit what wm_stem_fwd(s, stem_w, stem_b) writes; y and stats are bit for bit wm_conv64_bf(pro 0,
+ * epi 0, arith 1) on that y0.  stem_w [64,7], stem_b [64]; wpb_h from wm_pack_w64_h(mode 0); stats is required.  The pipelined f16
+ * build only: T % 128 != 0, schedule 0 or a null pointer is hipErrorInvalidValue, and nothing is written. */
+int wm_conv64_bf_stem(const float* s, const float* stem_w, const float* stem_b, const void* wpb_h, const float* bias, float* y0,
+                      float* y, float* stats, int B, int T, wm_stream_t stream);
+
 /* Inference ResBlock as ONE launch (py/main16.py:112-125 with both BatchNorm1d in eval mode):
  *   y = relu(x + (conv2(relu((conv1(x) + b1) * sc1 + sh1)) + b2) * sc2 + sh2)
  * sc / sh = the folded running statistics (wm_bn_eval_scale_shift); w1pb / w2pb = wm_pack_w64_bf_scaled images of
@@ -124,6 +132,15 @@ int wm_dwgrad64_bf_r1(const float* g, const float* g2, const float* ga, const fl
                       float* y, float* stats, float* partial, float* dw, float* dbias, int B, int T, int xpro, int epi, int accumulate,
                       const void* gmask, int arith, const float* gscale, float* dzmax, const float* g1, const float* hw,
                       wm_stream_t stream);
+/* wm_dwgrad64_bf's plain conv1 pair (xpro 0, epi 2, no gmask, arith 1) for the first ResBlock behind a stem.  Its weight-gradient
+ * operand x is the stem's output Conv1d(1, 64, 7, padding = 3)(s); it is formed on load from the clips s [B,1,T] and stem_w [64,7],
+ * stem_b [64] -- wm_stem_fwd's own fmaf chain -- and never read from memory.  e1 = the addend of the data gradient; the other
+ * arguments as wm_dwgrad64_bf's of the same names.  A null pointer (dbias and dzmax may be null) or T % 64 != 0:
+ * hipErrorInvalidValue, nothing is written.  Every output bit for bit what wm_dwgrad64_bf gives on the materialised x. */
+int wm_dwgrad64_bf_stem(const float* g, const float* g2, const float* ga, const float* gb, const float* gc, const void* wpb,
+                        const float* e1, float* y, float* partial, float* dw, float* dbias, int B, int T, int accumulate,
+                        const float* gscale, float* dzmax, const float* s, const float* stem_w, const float* stem_b,
+                        wm_stream_t stream);
 
 /* bf16x6 build of the 7-tap ConvTranspose1d(64,64,7,padding=3) (py/main16.py:144): wpb [3][7][64][64] uint16 from
  * wm_pack_w64_bf7 (mode 2 forward | 3 data gradient).  pro 0 x | 2 x + vec[b*64+c]; epi 0 + bias[c] | 3 none. */
