@@ -6,7 +6,7 @@ from .losses import (MultiScaleMelLoss, TFLoudnessLoss, clamp_peak, detection_lo
 from .step import LOSS_WEIGHTS, forward_losses, train_step, eval_forward
 from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
-from .attacks import (Convolved, Distortion, Lowpass, LpcCodec, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
+from .attacks import (Convolved, Distortion, Lowpass, LpcCodec, NoiseSuppress, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
                       evaluate_localization, evaluate_robustness, evaluate_robustness_by_class, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
 from . import attacks
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
@@ -15,6 +15,7 @@ from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_wa
                         save_audio_float)
 from .quality import stoi, nmr
 from .masking import masking, MaskingLoss
+from .suppress import noise_suppress
 from . import quality
 from .detection import (auc, calibrate_threshold, detection_report, eer, evaluate_detection, operating_point, roc_curve, tpr_at_fpr)
 from . import detection
@@ -37,4 +38,5 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "detection", "evaluate_detection", "detection_report", "roc_curve", "auc", "eer", "tpr_at_fpr", "calibrate_threshold", "operating_point",
            "curate", "clip_features", "classify_speech_noise", "is_silent", "prepare_recording", "curate_files", "butter_bandpass_sos", "slaney_mel", "dct_ortho",
            "lib", "LIB_PATH",
+           "NoiseSuppress", "noise_suppress",
            "masking", "MaskingLoss", "nmr"]

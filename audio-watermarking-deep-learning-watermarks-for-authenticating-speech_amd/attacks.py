@@ -16,6 +16,11 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
                open-loop quantiser on the prediction residual at a per-row SNR, all-pole synthesis that shapes the noise like the
                speech envelope -- one wm_lpc_codec launch (ops.LpcCodecFn); its "dead_zone" backward is the adjoint launch.  No LSP
                interpolation, no pitch predictor, no noise feedback, no entropy coder: parity with a real codec is unmeasured
+  NoiseSuppress   the REMOVAL attack, a STAND-IN for a single-channel noise suppressor: a short-time spectral Wiener gate with a
+               decision-directed a-priori SNR against one stationary noise estimate per row, at most reduce_db dB of attenuation per bin
+               drawn per row -- one wm_noise_suppress call (suppress.NoiseSuppressFn); with the gains held the map is self-adjoint, so
+               its backward is the same call on dy.  No voice-activity detector, no minimum statistics, no neural denoiser: parity with
+               WebRTC NS, RNNoise, `noisereduce` or any product's suppressor is unmeasured
   Convolved    a long convolutive channel: every row convolved with a given impulse response, or with one drawn per row from a bank of
                measured ones -- one wm_fir_rows launch (ops.FirRowsFn), its backward the same launch with reverse=True.  echo_ir
                makes the two-tap response of a plain echo
@@ -53,7 +58,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import dsp
+from . import dsp, suppress
 from ._host import _chk_int, _chk_positive
 from .codec import SAMPLE_RATE, _time_rows
 from .losses import postprocess
@@ -69,7 +74,7 @@ FAMILIES = {
     "param": (0xFFFFFFFF, 0xFFFFFFFF),          # o0..o2: Distortion's gain, SNR and noise coin; o3: TransformCodec's SNR
     "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry; o3: LpcCodec's SNR
     "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
-    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones
+    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones; o3: NoiseSuppress's reduce_db
     **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
     **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
 }
@@ -506,6 +511,63 @@ class LpcCodec(_RowDraws):
     def extra_repr(self):
         return (f"snr_db={self.snr_db}, frame={self.frame}, order={self.order}, sample_rate={self.sample_rate}, seed={self.seed}, "
                 f"grad={self.grad!r}")
+
+
+def row_reduce_db(seed, draw, rows, reduce_db):
+    """NoiseSuppress's per-row depth for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the "warp_phase"
+    counter -- TimeWarp, TimeStretch and PitchShift use its first three, so no two attacks share a number -- mapped onto the pair
+    reduce_db as fmaf(high - low, u, low)"""
+    return _affine(reduce_db, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[3]))
+
+
+class NoiseSuppress(_RowDraws):
+    """A STAND-IN for a single-channel noise suppressor on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,) at 16 kHz: the
+    signal path Ephraim-Malah / Scalart-Filho suppressors and WebRTC-style noise suppression share -- sine-windowed frames of 512 at hop
+    256, a noise PSD per bin, a Wiener gain from a decision-directed a-priori SNR (weight `alpha`, over-subtraction `over`) floored at
+    -reduce_db dB, synthesis with overlap-add (wm_noise_suppress in include/wm_hip.h has the definition).  It is the one attack here whose
+    PURPOSE is to remove a low-level noise-like signal, which is what the watermark is.
+    Its limits: it is a stand-in.  It uses one stationary noise estimate per row (the geometric mean of the row's own frame powers; or
+    `noise_psd`, a (257,) or (rows, 257) profile, which is what an attacker who knows delta's average spectrum would pass).  It has no
+    voice-activity detector, no minimum-statistics tracking and no neural denoiser.  A stationary tone counts as noise and is attenuated.
+    The gradient holds the gains constant (the backward is the same launch on dy: suppress.NoiseSuppressFn).  PARITY WITH WebRTC NS,
+    RNNoise, `noisereduce` OR ANY PRODUCT'S SUPPRESSOR IS UNMEASURED.  The output stays time-aligned, so STOI and NMR apply.
+    reduce_db: a number fixes the depth, a pair draws one value per row, reproducible from (seed, draw, row0 + r) (row_reduce_db); 0..60.
+    Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
+    pieces draws what the whole batch would.  `last_reduce_db`: the per-row values of the last call (a CPU tensor).
+    CUDA tensors run the kernels; CPU tensors a float64 numpy restatement of the definition, rounded once (forward only)."""
+
+    def __init__(self, reduce_db=(6, 24), over=1.0, alpha=0.98, noise_psd=None, seed=0):
+        super().__init__(seed)
+        self.reduce_db = _pair(reduce_db, "reduce_db")
+        if not 0.0 <= self.reduce_db[0] <= self.reduce_db[1] <= suppress.SUPPRESS_MAX_REDUCE_DB:
+            raise ValueError(f"reduce_db: expected values in [0, 60], got {reduce_db!r}")
+        self.alpha, self.over = suppress._chk_scalars(alpha, over)
+        if noise_psd is not None:
+            if not isinstance(noise_psd, torch.Tensor) or noise_psd.dim() not in (1, 2) or noise_psd.shape[-1] != suppress.SUPPRESS_BINS:
+                raise ValueError(f"noise_psd: expected None or a (257,) or (rows, 257) tensor, got "
+                                 f"{tuple(noise_psd.shape) if isinstance(noise_psd, torch.Tensor) else type(noise_psd).__name__}")
+            suppress._profile_rows(noise_psd, noise_psd.numel() // suppress.SUPPRESS_BINS, noise_psd.device)      # non-finite or negative values fail here
+            noise_psd = noise_psd.detach().to(torch.float32).contiguous()
+        self.register_buffer("noise_psd", noise_psd)
+        self.last_reduce_db = None
+
+    def forward(self, x, row0=0):
+        x, rows = self._rows(x, row0)
+        x32 = x.to(torch.float32)
+        x2 = x32.reshape(rows, x.shape[-1])
+        prof = suppress._profile_rows(self.noise_psd, rows, x.device)            # a profile for another number of rows fails here
+        rd = torch.from_numpy(row_reduce_db(self.seed, self.draw, row0 + np.arange(rows), self.reduce_db))
+        self._next_draw()
+        if x.is_cuda:
+            y = suppress.NoiseSuppressFn.apply(x2, rd.to(x.device), prof, self.alpha, self.over)
+        else:
+            y = suppress.suppress_rows_host(x2, rd, None, prof, self.alpha, self.over)
+        self.last_reduce_db = rd
+        return y.reshape(x.shape)
+
+    def extra_repr(self):
+        prof = None if self.noise_psd is None else tuple(self.noise_psd.shape)
+        return f"reduce_db={self.reduce_db}, over={self.over}, alpha={self.alpha}, noise_psd={prof}, seed={self.seed}"
 
 
 def row_reverb_params(seed, draw, rows, rt60, drr_db):

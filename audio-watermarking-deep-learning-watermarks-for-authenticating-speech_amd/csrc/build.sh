@@ -12,7 +12,7 @@ pids=()
 objs=()
 # the one list of translation units (= the stems of *.hip): compiled from it, linked from it.  obj/ may hold objects of units
 # that no longer exist (it is not under version control), so the link line never globs
-for f in conv64_fwd conv64_k7 conv64_wgrad conv64_fp32 conv64_eval conv64_dwgrad bn small_convs lstm_fwd lstm_bwd lstm_grad postproc stft_loss losses gconv_fwd gconv_wgrad gconv_small lstm_seq resample biquad distort mdct_codec fir_rows time_warp wsola lpc_codec stoi splice clip_scores clip_features masking; do
+for f in conv64_fwd conv64_k7 conv64_wgrad conv64_fp32 conv64_eval conv64_dwgrad bn small_convs lstm_fwd lstm_bwd lstm_grad postproc stft_loss losses gconv_fwd gconv_wgrad gconv_small lstm_seq resample biquad distort mdct_codec fir_rows time_warp wsola lpc_codec stoi splice clip_scores clip_features masking noise_suppress; do
   objs+=(obj/$f.o)
   if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ $newest_hpp -nt obj/$f.o ]; then
     $HIPCC $FLAGS -c $f.hip -o obj/$f.o &

@@ -922,6 +922,48 @@ int wm_clip_features_plan(long long rows, long long n, int sample_rate, int* fra
 int wm_clip_features(const float* x, const float* sos, const float* fb, const int* klo, const int* khi, const float* dct, float* feat,
                      int* counts, float* frames_out, long long rows, long long n, int sample_rate, int warm, wm_stream_t stream);
 
+/* ---- noise suppression: a short-time spectral Wiener gate with a decision-directed a-priori SNR, and its adjoint --------------------------
+ * The signal path that Ephraim-Malah / Scalart-Filho suppressors and WebRTC-style noise suppression share, as an attack on a watermark that
+ * is itself a low-level noise-like signal.  A STAND-IN: one stationary noise estimate per row, no voice-activity detector, no
+ * minimum-statistics tracking, no neural denoiser; a stationary tone counts as noise and is attenuated; parity with WebRTC NS, RNNoise,
+ * noisereduce or any product's suppressor is unmeasured.  Defined at 16 kHz.  The output stays time-aligned with the input.
+ * The gains come from a row x of n >= 1 samples and are applied to a second row src of n samples; in the forward src is x itself.
+ * x, src, y are (rows, n) fp32, rows >= 1, n <= 2^34, rows * n <= 2^46; every row on its own.
+ *   constants   L = 512, H = 256, K = 257 bins, M = ceil(n / H) + 1 frames; the sine window w[j] = sin(pi (j + 0.5) / L), whose square
+ *               sums to 1 at 50 % overlap; eps = 1e-10; gamma_E = 0.5772156649015329
+ *   framing     xp = H zeros, then the row, then zeros up to (M + 1) H samples; frame m = xp[m H : m H + L] w, so every sample lies in
+ *               exactly two frames
+ *   spectrum    X[m,k] = the 512-point real transform of frame m, k = 0..256;  P[m,k] = |X[m,k]|^2
+ *   noise PSD   stationary, and the row judges itself:  N[k] = e^gamma_E exp((1 / M) sum_m ln(P[m,k] + eps)), the geometric mean over ALL M
+ *               frames (frames of digital silence count); the factor e^gamma_E makes it unbiased on stationary Gaussian noise.  With
+ *               noise_in given, a per-row (K,) profile, that is N and this pass is skipped (an attacker who knows delta's average
+ *               spectrum would pass it)
+ *   gain        the recursion runs over m for every k:  g[m,k] = P[m,k] / (over N[k] + eps),
+ *               xi[m,k] = alpha q[m-1,k] + (1 - alpha) max(g[m,k] - 1, 0) with q[-1,k] = 1,  G[m,k] = max(xi / (1 + xi), Gmin),
+ *               q[m,k] = G[m,k]^2 g[m,k];  Gmin = 10^(-reduce_db / 20), reduce_db per row: NaN becomes 0, then it is clipped to [0, 60].
+ *               alpha: the decision-directed weight (0.98 is the usual one); over: the over-subtraction factor (1.0)
+ *   synthesis   S[m,k] = the transform of src's frames;  yf[m] = w irfft(G[m] S[m]);  the frames are overlap-added;  y = out[H : H + n]
+ * Properties: reduce_db = 0 gives Gmin = 1, so G = 1 and y = src to rounding.  With the gains held the map src -> y is self-adjoint (real
+ * gains, the same window on both sides, framing is the adjoint of overlap-add), so THE BACKWARD IS THE SAME CALL: gains from the saved x,
+ * src = dy.  The dependence of the gains on x is not differentiated.  An all-zero row gives exact zeros and finite gains.
+ * src: null means x.  noise_in: (rows, 257) or null.  gain_out (rows, M, 257) and noise_out (rows, 257): optional.  scratch: caller-
+ * allocated, contents unspecified before and after.  wm_noise_suppress_plan: host-only query (the two results are HOST pointers, stream
+ * unused): frames = M, scratch_bytes = what `scratch` must hold.
+ * Computed (csrc/noise_suppress.hip) in three launches: analysis in fp64 over (row, chunk of 16 frames), two frames per complex transform,
+ * P to scratch as fp32 with per-chunk, per-bin sums of ln(P + eps); one thread per (row, bin) adds those sums in chunk order, forms N and runs
+ * the recursion in fp64, G over P in place; synthesis in fp32 over (row, output hop), each workgroup forming the two frames that cover its
+ * 256 samples, every sample of y written once.  No atomics: a row's bits depend on its samples, its reduce_db (its noise_in, alpha, over)
+ * and n only, never on rows, its place in the batch or the grid; two launches give identical bits.
+ * A row of x with any non-finite sample comes back all NaN in y, gain_out and noise_out; its neighbours carry the bits of a launch without
+ * it.  Non-finite values in src just propagate through the arithmetic.
+ * Every pointer may start at any multiple of 4 bytes; inputs are borrowed and never written.  hipErrorInvalidValue before any launch:
+ * rows or n < 1, n > 2^34, rows * n > 2^46; a null x, reduce_db, y or scratch; a misaligned pointer; alpha outside [0, 1); over not finite
+ * and positive; any output (y, gain_out, noise_out, scratch) overlapping an input or another output (src == x is allowed). */
+int wm_noise_suppress_plan(long long rows, long long n, long long* frames, long long* scratch_bytes, wm_stream_t stream);
+int wm_noise_suppress(const float* x, const float* src, const float* noise_in, const float* reduce_db, float* y,
+                      float* gain_out, float* noise_out, void* scratch, long long rows, long long n,
+                      float alpha, float over, wm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
