@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void conv64_kernel(Conv64Args a) {
         Cs[tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pa[tid] : 0.f;
         Cs[64 + tid] = (PRO == PRO_BNRELU || PRO == PRO_BNBWD) ? a.pb[tid] : 0.f;
         Cs[128 + tid] = (PRO == PRO_BNBWD) ? a.pc[tid] : 0.f;
-        Cs[192 + tid] = (EPI == EPI_BIAS && a.bias) ? a.bias[tid] : 0.f;
+        // PRO_BNBWD never meets EPI_BIAS: the slot is the low word of its offset (pb is [2][64], hi + lo), else the bias
+        Cs[192 + tid] = (PRO == PRO_BNBWD) ? a.pb[64 + tid] : ((EPI == EPI_BIAS && a.bias) ? a.bias[tid] : 0.f);
         Cs[256 + tid] = (EPI == EPI_RELUMASK) ? a.ea[tid] : 0.f;
         Cs[320 + tid] = (EPI == EPI_RELUMASK) ? a.eb[tid] : 0.f;
     }

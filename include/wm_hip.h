@@ -42,7 +42,8 @@ int wm_pack_w64(const float* w, float* wp, int KW, int mode, wm_stream_t stream)
  *        | 2 x + pa[b*64+c] (message embedding add, py/main16.py:158-159) | 3 pa[c]*x + (pb[c] + pb[64+c]) + pc[c]*x2 (BN backward; pb is [2][64]: offset as hi + lo words)
  *   epi: 0 + bias[c] | 1 keep where e1*ea[c]+eb[c] > 0 (ReLU backward) | 2 + e1 (residual gradient) | 3 none
  *   stats (NULL or [256][2][64]): per-workgroup partial sums for BatchNorm (epi 0: sum y, sum y^2;
- *   epi 1: sum v, sum v*e1).  Supported (KW,pro,epi): (3,{0,1},0) (3,3,{1,2,3}) (7,{0,2},0) (7,0,3).          */
+ *   epi 1: sum v, sum v*e1); all 256 slots are written or zeroed.  Supported (KW,pro,epi): (3,{0,1},0) with or without stats,
+ *   (3,3,1) with stats only, (3,3,{2,3}) without; (7,{0,2},0) and (7,0,3) without stats.  Anything else: hipErrorInvalidValue. */
 int wm_conv64(const float* x, const float* x2, const float* wp, const float* pa, const float* pb, const float* pc,
               const float* bias, const float* e1, const float* ea, const float* eb, float* y, float* stats,
               int B, int T, int KW, int pro, int epi, wm_stream_t stream);
@@ -120,7 +121,8 @@ int wm_dwgrad64_bf(const float* g, const float* g2, const float* ga, const float
  * arith 1: f16 TWO-piece split (22 bits per operand), three products on v_mfma_f32_32x32x16_f16 -- half the matrix work of arith 0,
  *          wpb from wm_pack_w64_h (weights scaled by a
  *          power of two chosen from max |w|, stored behind the image); gscale = wm_bn_bwd_finalize's {gs, 1 / gs} for THIS launch's
- *          g; dzmax (optional, epi 1 / 2 / 8): 256 floats, max |y| per workgroup = the dzmax input of the next launch's finalize. */
+ *          g; dzmax (optional, epi 1 / 2 / 8; arith 1 only, arith 0 leaves it untouched): 256 floats, max |y| per workgroup (slots
+ *          beyond the grid zeroed) = the dzmax input of the next launch's finalize. */
 int wm_pack_w64_h(const float* w, void* wph, int mode, wm_stream_t stream);      /* 2 * 3 * 4096 f16 + 2 floats */
 /* wm_dwgrad64_bf for the ResBlock in front of the Conv1d(64,1,1) head.  The gradient that reaches its output is the rank-one frame
  * hw[c] g1[b][t] (wm_head1_bwd's dx); it is formed on load from g1 [B][T] and hw [64] -- the same single multiply -- and never read
@@ -161,20 +163,25 @@ int wm_gscale_from_max(const float* maxes, int n, float log2_target, float* gsca
 int wm_absmax_rows(const float* x, int rows, long long row_len, float* out, wm_stream_t stream);
 
 /* weight gradient of that ConvTranspose1d (= wm_wgrad64 with KW 7, gpro 0, layout 1): dw [in][out][7], dbias [64];
- * xpro 0 | 2 (x + vec[b*64+c]); partial: >= 256 * (7*4096 + 64) floats. */
+ * xpro 0 | 2 (x + vec[b*64+c]); partial: >= 256 * (7*4096 + 64) floats; accumulate: 0 overwrite | non-zero add (the whole value,
+ * not bit 0 alone as in wm_wgrad64_bf: there is no output-split build here). */
 int wm_wgrad64_bf7(const float* g, const float* x, const float* vec, float* partial, float* dw, float* dbias, int B, int T,
                    int xpro, int accumulate, int arith, const float* gscale, wm_stream_t stream);
 /* arith 1: f16 two-piece split; gscale = wm_gscale_absmax's {gs, 1 / gs} for g (required), x is split unscaled, dbias from the unscaled g */
 
-/* bf16x6 build of the k3 Conv1d weight gradient (contract of wm_wgrad64 with KW = 3, layout 0; gpro / xpro (3,1), (3,0), (0,0)).  accumulate: bit 0 = add to
+/* bf16x6 build of the k3 Conv1d weight gradient (contract of wm_wgrad64 with KW = 3, layout 0; gpro / xpro (3,1), (3,0), (0,0); partial:
+ * 256 x (3*4096+64) floats).  accumulate: bit 0 = add to
  * dw / dbias, bit 1 = the output-split build (a wave keeps one 32x32 block per tap: ~200 registers per lane, so the workgroup
- * can share a CU with the LSTM recurrence kernels when it is launched on a side stream; same results)                     */
+ * can share a CU with the LSTM recurrence kernels when it is launched on a side stream; same results; (0,0) has no such build and
+ * ignores the bit)                                                                                                          */
 int wm_wgrad64_bf(const float* g, const float* g2, const float* ga, const float* gb, const float* gc,
                   const float* x, const float* xa, const float* xb, float* partial, float* dw, float* dbias,
                   int B, int T, int gpro, int xpro, int accumulate, wm_stream_t stream);
 
-/* dW (+)= sum_{b,t} gpro(g)[out,t] * xpro(x)[in,t+tap-KW/2]; dbias (+)= sum gpro(g).  partial: [512][KW*4096+64].
- *   gpro 0|3, xpro 0|1|2 as above; layout 0: Conv1d weight [out][in][KW], 1: ConvTranspose1d weight [in][out][KW]. */
+/* dW (+)= sum_{b,t} gpro(g)[out,t] * xpro(x)[in,t+tap-KW/2]; dbias (+)= sum gpro(g).  partial: [256][KW*4096+64] (one slab per
+ *   workgroup, at most 256).  Supported (KW,gpro,xpro): (3,3,1) (3,3,0) (7,0,2) (7,0,0), anything else hipErrorInvalidValue; prologues
+ *   as above; layout 0: Conv1d weight [out][in][KW], 1: ConvTranspose1d weight [in][out][KW] (either with either KW); accumulate:
+ *   0 overwrite | non-zero add. */
 int wm_wgrad64(const float* g, const float* g2, const float* ga, const float* gb, const float* gc,
                const float* x, const float* xa, const float* xb, float* partial, float* dw, float* dbias,
                int B, int T, int KW, int gpro, int xpro, int layout, int accumulate, wm_stream_t stream);

@@ -57,6 +57,45 @@ def bits(t):
     return t.contiguous().view(torch.int32)
 
 
+CANARY = 8                         # untouched elements on either side of a Guarded buffer
+PATTERN = 0x5A5A5A5A
+INVALID = 1                        # hipErrorInvalidValue
+
+
+class Guarded:
+    """n elements with CANARY more on either side: NaN around floats, a bit pattern around integers.  `t` is the inner view (16-byte
+    aligned: CANARY * 4 bytes in); intact() is true while the surround, and with whole=True everything, holds what it was given.
+    Without `init` the inner elements hold the fill too: an output element the kernel never writes stays NaN."""
+
+    def __init__(self, dev, n, init=None, dtype=torch.float32):
+        fill = float("nan") if dtype == torch.float32 else (PATTERN if dtype == torch.int32 else PATTERN << 32 | PATTERN)
+        self.buf = torch.full((n + 2 * CANARY,), fill, dtype=dtype, device=dev)
+        self.t = self.buf[CANARY:CANARY + n]
+        if init is not None:
+            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init)).to(dev).reshape(-1))
+        self.before = self.buf.clone()
+
+    def intact(self, whole=False):
+        a, b = self.buf, self.before
+        if a.dtype == torch.float32:
+            a, b = bits(a), bits(b)
+        n, C = self.t.numel(), CANARY
+        return bool(torch.equal(a, b)) if whole else bool(torch.equal(a[:C], b[:C]) and torch.equal(a[C + n:], b[C + n:]))
+
+    def np(self, shape=None):
+        a = self.t.cpu().numpy()
+        return a if shape is None else a.reshape(shape)
+
+
+def invalid(call, *outputs):
+    """the call returns hipErrorInvalidValue and writes nothing"""
+    with pytest.raises(RuntimeError, match=f"hipError {INVALID}$"):
+        call()
+    torch.cuda.synchronize()
+    for g in outputs:
+        assert g.intact(whole=True), "an invalid call wrote to an output"
+
+
 def to_dev(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 

@@ -10,47 +10,12 @@ import pytest
 import torch
 
 import bn_yardstick as Y
-from gpu_support import awm, bits, dev, p, st, to_dev  # noqa: F401
+from gpu_support import CANARY, Guarded, awm, dev, invalid, p, st, to_dev  # noqa: F401
 from yardstick_common import assert_within, ulp32
 
 pytestmark = pytest.mark.gpu
 
-INVALID = 1                        # hipErrorInvalidValue
-C = Y.CANARY
-PATTERN = 0x5A5A5A5A
-
-
-class Guarded:
-    """n elements with CANARY more on either side: NaN around floats, a bit pattern around integers.  `t` is the inner view (16-byte
-    aligned: CANARY * 4 bytes in); intact() is true while the surround, and with whole=True everything, holds what it was given."""
-
-    def __init__(self, dev, n, init=None, dtype=torch.float32):
-        fill = float("nan") if dtype == torch.float32 else (PATTERN if dtype == torch.int32 else PATTERN << 32 | PATTERN)
-        self.buf = torch.full((n + 2 * C,), fill, dtype=dtype, device=dev)
-        self.t = self.buf[C:C + n]
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init)).to(dev).reshape(-1))
-        self.before = self.buf.clone()
-
-    def intact(self, whole=False):
-        a, b = self.buf, self.before
-        if a.dtype == torch.float32:
-            a, b = bits(a), bits(b)
-        n = self.t.numel()
-        return bool(torch.equal(a, b)) if whole else bool(torch.equal(a[:C], b[:C]) and torch.equal(a[C + n:], b[C + n:]))
-
-    def np(self, shape=None):
-        a = self.t.cpu().numpy()
-        return a if shape is None else a.reshape(shape)
-
-
-def invalid(call, *outputs):
-    """the call returns hipErrorInvalidValue and writes nothing"""
-    with pytest.raises(RuntimeError, match=f"hipError {INVALID}$"):
-        call()
-    torch.cuda.synchronize()
-    for g in outputs:
-        assert g.intact(whole=True), "an invalid call wrote to an output"
+assert CANARY == Y.CANARY            # the untouched elements on either side of every output (bn_yardstick.py, section C)
 
 
 # --------------------------------------------------------------------------------------------------------------- 1. wm_bn_finalize
