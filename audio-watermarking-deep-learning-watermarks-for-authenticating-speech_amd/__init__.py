@@ -8,7 +8,7 @@ from .optim import FlatAdam
 from .codec import PcmCodec, encode_pcm16, perceptual_postprocess
 from .attacks import (Convolved, Distortion, Lowpass, LpcCodec, NoiseSuppress, PitchShift, Resampled, Reverb, Splice, TimeStretch, TimeWarp, TransformCodec, echo_ir,
                       evaluate_localization, evaluate_robustness, evaluate_robustness_by_class, pack_labels, row_splice_spans, splice_rows_host, unpack_labels)
-from . import attacks
+from . import attacks, draws
 from .inference import (compute_si_snr, detect_prob, detect_watermark, detect_waveform, embed_waveform, evaluate_batches,
                         evaluate_unseen_file, generate_watermarked_audio, load_audio, locate_watermark, lowpass_biquad, pcm16, read_audio, resample, resample_add, Resample,
                         save_audio,
@@ -31,7 +31,7 @@ __all__ = ["Generator", "Detector", "ResBlock", "load_state_dict_strip_prefix", 
            "fir_lowpass", "clamp_peak", "limit_rms", "postprocess", "high_freq_penalty", "detection_losses", "l1_to_zero",
            "forward_losses", "train_step", "eval_forward", "LOSS_WEIGHTS", "FlatAdam", "distributed", "checkpoint", "main14b_2", "generate_watermarked_audio", "detect_watermark", "embed_waveform",
            "detect_waveform", "detect_prob", "evaluate_unseen_file", "evaluate_batches", "compute_si_snr", "load_audio", "save_audio", "save_audio_float", "lowpass_biquad", "pcm16", "resample", "Resample", "resample_add", "read_audio", "perceptual_postprocess", "PcmCodec", "encode_pcm16",
-           "attacks", "Distortion", "Lowpass", "Resampled", "TransformCodec", "LpcCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness", "evaluate_robustness_by_class",
+           "attacks", "draws", "Distortion", "Lowpass", "Resampled", "TransformCodec", "LpcCodec", "Convolved", "Reverb", "TimeWarp", "TimeStretch", "PitchShift", "echo_ir", "evaluate_robustness", "evaluate_robustness_by_class",
            "Splice", "evaluate_localization", "row_splice_spans", "splice_rows_host", "pack_labels", "unpack_labels", "detection_losses_masked",
            "locate_watermark",
            "stoi", "quality",

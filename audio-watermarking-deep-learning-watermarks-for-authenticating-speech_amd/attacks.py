@@ -5,16 +5,16 @@ additive noise; it ships no code for the last two, and no codec to train against
 that go wherever codec.PcmCodec goes -- the `codec=` argument of forward_losses / train_step / eval_forward / evaluate_batches takes any of them, and chains are plain
 torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already works as `codec=`:
 
-  Distortion   per-clip gain and white Gaussian noise at a set SNR: one wm_distort call (ops.DistortFn), differentiable
-  Lowpass      the biquad low-pass alone (no clamp, no 16-bit grid): ops.biquad, its backward the same launch with reverse=True
+  Distortion   per-clip gain and white Gaussian noise at a set SNR: one wm_distort call (dsp.DistortFn), differentiable
+  Lowpass      the biquad low-pass alone (no clamp, no 16-bit grid): dsp.biquad, its backward the same launch with reverse=True
   Resampled    down to another rate and back (8 kHz telephony, say), every row by itself: two wm_resample_rows launches
-               (ops.ResampleRowsFn), the backward of each the same launch with the transposed table
+               (dsp.ResampleRowsFn), the backward of each the same launch with the transposed table
   TransformCodec   a STAND-IN for lossy compression: lapped MDCT, per-band quantiser at a per-row SNR, bandwidth cut, synthesis -- one
-               wm_mdct_codec launch (ops.MdctCodecFn), its backward the same launch with the quantiser off.  The signal path MP3 / AAC
+               wm_mdct_codec launch (dsp.MdctCodecFn), its backward the same launch with the quantiser off.  The signal path MP3 / AAC
                share, not an encoder: parity with a real one is unmeasured
   LpcCodec     a STAND-IN for a predictive speech codec (ADPCM / CELP / AMR-WB / SILK are all linear-predictive): per-frame LPC, an
                open-loop quantiser on the prediction residual at a per-row SNR, all-pole synthesis that shapes the noise like the
-               speech envelope -- one wm_lpc_codec launch (ops.LpcCodecFn); its "dead_zone" backward is the adjoint launch.  No LSP
+               speech envelope -- one wm_lpc_codec launch (dsp.LpcCodecFn); its "dead_zone" backward is the adjoint launch.  No LSP
                interpolation, no pitch predictor, no noise feedback, no entropy coder: parity with a real codec is unmeasured
   NoiseSuppress   the REMOVAL attack, a STAND-IN for a single-channel noise suppressor: a short-time spectral Wiener gate with a
                decision-directed a-priori SNR against one stationary noise estimate per row, at most reduce_db dB of attenuation per bin
@@ -22,17 +22,17 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
                its backward is the same call on dy.  No voice-activity detector, no minimum statistics, no neural denoiser: parity with
                WebRTC NS, RNNoise, `noisereduce` or any product's suppressor is unmeasured
   Convolved    a long convolutive channel: every row convolved with a given impulse response, or with one drawn per row from a bank of
-               measured ones -- one wm_fir_rows launch (ops.FirRowsFn), its backward the same launch with reverse=True.  echo_ir
+               measured ones -- one wm_fir_rows launch (dsp.FirRowsFn), its backward the same launch with reverse=True.  echo_ir
                makes the two-tap response of a plain echo
   Reverb       the same launch with SYNTHETIC room responses drawn on the device per row (wm_rir_synth) at a per-row RT60 and
                direct-to-reverberant ratio: exponentially decaying Gaussian noise, not a room simulation -- survival in real rooms
                is unmeasured
   TimeWarp     the desynchronising channel: playback at another speed (tempo and pitch together), sinusoidal wow / flutter and a cut at
                the front, through a Hann-windowed sinc interpolator whose phase is computed per output sample -- one wm_time_warp launch
-               (ops.TimeWarpFn), its backward the same launch with adjoint=True.  Survival against real players and tapes is
+               (dsp.TimeWarpFn), its backward the same launch with adjoint=True.  Survival against real players and tapes is
                unmeasured
   TimeStretch  the pitch-preserving change of tempo: waveform-similarity overlap-add (WSOLA), frames copied from near their nominal
-               place to evenly spaced places of the output and cross-faded -- one wm_wsola launch (ops.WsolaFn), its backward the
+               place to evenly spaced places of the output and cross-faded -- one wm_wsola launch (dsp.WsolaFn), its backward the
                same launch as a gather with the chosen positions held constant.  A piecewise copy with cross-faded jumps, a
                rectangular search, no transient detection: parity with any real editor's stretch is unmeasured
   PitchShift   the change of pitch at constant tempo: TimeStretch by 1 / beta followed by wm_time_warp at speed beta, no kernel of
@@ -40,15 +40,16 @@ torch.nn.Sequential(Distortion(...), PcmCodec(...)), which therefore already wor
   evaluate_robustness   watermarked / clean probability, bit accuracy and delta RMS per attack, pooled as evaluate_batches pools them
   Splice       the EDITING attack, and the only module here with two inputs: spans of the watermarked signal are cut out and replaced by
                the clean signal, by silence, or by clean audio moved from elsewhere in the same row -- one wm_splice launch
-               (ops.SpliceFn) that also emits the per-sample labels "still watermarked" as a bit mask; its backward passes the
+               (dsp.SpliceFn) that also emits the per-sample labels "still watermarked" as a bit mask; its backward passes the
                gradient where the label is 1.  It is the `tamper=` argument of forward_losses / train_step / eval_forward /
                evaluate_batches, NOT a `codec=` and not a member of Sequential chains.  Rectangular cuts without a crossfade, "moved"
                audio from the same row only; whether a model trained with it localises real edits is unmeasured
   evaluate_localization   IoU, precision, recall and sample accuracy of the per-sample track against Splice's labels, from integer counts
 
-The noise is counter-based (Philox4x32-10 -> Box-Muller), so nothing is stored for the backward pass, a run is reproducible from `seed`,
-and philox4x32_10 / normal_noise below restate on the host exactly the numbers the kernel draws.  The counters (word 0, word 1, row, draw)
-of the families never meet: FAMILIES below is their one list, and a new attack takes a new row of it."""
+The modules are here, with their argument checks and the evaluation loops.  The random numbers they draw are counter-based, so nothing is
+stored for the backward pass and a run is reproducible from `seed`; draws.py restates on the host exactly the numbers the kernels draw
+and holds the table of which attack owns which output word (draws.WORDS: a new attack takes a free cell of it).  What a CPU tensor runs
+in place of a kernel is in attacks_host.py.  Both modules' names are bound here too: attacks.<name> is their public spelling."""
 from __future__ import annotations
 
 import math
@@ -56,91 +57,20 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from . import dsp, suppress
 from ._host import _chk_int, _chk_positive
+from .attacks_host import (  # noqa: F401  what a CPU tensor runs lives in attacks_host.py; attacks.<name> stays its spelling
+    _conv_rows_host, _gather_ext, _lpc_rows_host, _sinpi, _warp_rows_host, _wsola_rows_host, distort_rows_host, mdct_codec_rows_host,
+    pack_labels, splice_rows_host, unpack_labels)
 from .codec import SAMPLE_RATE, _time_rows
+from .draws import (  # noqa: F401  the host-side draws live in draws.py; attacks.<name> stays their public spelling
+    _M0, _M1, _W0, _W1, FAMILIES, SPLICE_KINDS, WORDS, _affine, _check_cut, _key, _normals, _unit, _words, normal_noise, philox4x32_10,
+    rir_taps, row_bank_index, row_lpc_snr_db, row_parameters, row_pitch_params, row_reduce_db, row_reverb_params, row_snr_db,
+    row_splice_spans, row_stretch_rates, row_warp_params)
 from .losses import postprocess
 
 NOISE_GRAD_MODES = ("through", "detached")
-_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-# The counter families: name -> (word 0, word 1) of the Philox counter (word 0, word 1, row, draw).  None is a word that counts: t >> 2 of
-# a row's samples (n <= 2^34, so below 2^32) and k >> 2 of a response's taps (below 2^12).  No two families share a counter, and
-# csrc/distort.hip and csrc/splice.hip spell the same words.
-FAMILIES = {
-    "sample": (None, 0),                        # Distortion's noise
-    "rir_tap": (None, 0xFFFFFFFE),              # the taps of Reverb's synthetic responses
-    "param": (0xFFFFFFFF, 0xFFFFFFFF),          # o0..o2: Distortion's gain, SNR and noise coin; o3: TransformCodec's SNR
-    "param2": (0xFFFFFFFE, 0xFFFFFFFF),         # o0, o1: Reverb's rt60 and drr_db; o2: Convolved's bank entry; o3: LpcCodec's SNR
-    "warp": (0xFFFFFFFD, 0xFFFFFFFF),           # TimeWarp's speed, shift, flutter rate and flutter depth
-    "warp_phase": (0xFFFFFFFC, 0xFFFFFFFF),     # o0: TimeWarp's flutter phase (all it uses); o1: TimeStretch's rate; o2: PitchShift's semitones; o3: NoiseSuppress's reduce_db
-    **{f"splice_span{j}": (0xFFFFFFFB - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},      # o0..o3: span j's coin, length, start, kind
-    **{f"splice_shift{j}": (0xFFFFFFFA - 2 * j, 0xFFFFFFFF) for j in range(dsp.SPLICE_MAX_SPANS)},     # o0: where span j's "moved" audio comes from
-}
-
-
-def philox4x32_10(counter, key):
-    """Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11).  counter: four uint32 values or arrays that
-    broadcast together, key: two uint32 values.  Returns a uint32 array of shape (4, ...): the four output words."""
-    c = [np.asarray(v, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for v in counter]
-    if len(c) != 4 or len(key) != 2:
-        raise ValueError("philox4x32_10: a counter of four words and a key of two")
-    c = list(np.broadcast_arrays(*c))
-    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
-    lo = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(_M0) * c[0], np.uint64(_M1) * c[2]                     # 32 x 32 bits: exact in 64
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & lo, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & lo]
-        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
-    return np.stack(c).astype(np.uint32)
-
-
-def _unit(o):
-    """u = ((o >> 9) + 0.5) * 2^-23: 24 bits, exact in float32 (and float64), never 0 or 1"""
-    return ((o >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
-
-
-def _key(seed):
-    seed = int(seed) & (2 ** 64 - 1)
-    return seed & 0xFFFFFFFF, seed >> 32
-
-
-def _words(family, seed, draw, rows, count=None):
-    """The four Philox output words of `family` for the rows `rows` (an int or an int array of row0 + r) of (seed, draw); count: the values
-    of the word that counts, for the families that have one"""
-    w0, w1 = FAMILIES[family]
-    return philox4x32_10((count if w0 is None else w0, w1, np.asarray(rows, dtype=np.uint64), int(draw)), _key(seed))
-
-
-def _affine(pair, u):
-    """fmaf(high - low, u, low) as the kernels form it: float32 bounds, the product exact in float64, one rounding to float32"""
-    lo, hi = (np.float32(v) for v in pair)
-    return (np.float64(hi - lo) * u + np.float64(lo)).astype(np.float32)
-
-
-def normal_noise(seed, draw, row, n):
-    """z(seed, draw, row, t) for t < n as a float64 array: counter (q, 0, row, draw) with q = t >> 2, key (seed low, seed high);
-    words (o0, o1) give sqrt(-2 ln u(o0)) * (cos, sin)(2 pi u(o1)) for samples 4q and 4q+1, (o2, o3) the same for 4q+2 and 4q+3."""
-    return _normals(seed, draw, row, n, "sample")
-
-
-def _normals(seed, draw, row, n, family):
-    """normal_noise from the counting family `family`: "sample" or "rir_tap" """
-    n = int(n)
-    q = np.arange((n + 3) // 4, dtype=np.uint64)
-    o = _words(family, seed, draw, int(row), q)
-    z = np.empty((len(q), 4), dtype=np.float64)
-    for p in (0, 1):
-        rad, th = np.sqrt(-2.0 * np.log(_unit(o[2 * p]))), 2.0 * math.pi * _unit(o[2 * p + 1])
-        z[:, 2 * p], z[:, 2 * p + 1] = rad * np.cos(th), rad * np.sin(th)
-    return z.reshape(-1)[:n]
-
-
-def row_parameters(seed, draw, rows, bounds):
-    """(gain_db, snr_db, noisy) of rows `rows` (an int array of row0 + r), as the kernel draws them: float32 arrays and a bool array"""
-    bounds, o = tuple(bounds), _words("param", seed, draw, rows)
-    return _affine(bounds[0:2], _unit(o[0])), _affine(bounds[2:4], _unit(o[1])), _unit(o[2]) < np.float64(np.float32(bounds[4]))
 
 
 def _pair(v, name):
@@ -167,11 +97,11 @@ class _RowDraws(torch.nn.Module):
         return self
 
     def _rows(self, x, row0):
-        """x as time rows and their number; row0 + rows must stay a row counter"""
+        """x as time rows, their number, and the row numbers row0 + r the draws take; row0 + rows must stay a row counter"""
         x = _time_rows(x, "x")
         rows = x.numel() // x.shape[-1]
         _chk_int(row0, "row0", 0, 2 ** 32 - rows, "an int with 0 <= row0 and row0 + rows <= 2^32")
-        return x, rows
+        return x, rows, row0 + np.arange(rows)
 
     def _next_draw(self):
         draw, self.draw = self.draw, (self.draw + 1) % 2 ** 32
@@ -205,7 +135,7 @@ class Distortion(_RowDraws):
         return (*self.gain_db, *(self.snr_db or (0.0, 0.0)), self.p_noise)
 
     def forward(self, x, row0=0):
-        x, _ = self._rows(x, row0)
+        x = self._rows(x, row0)[0]
         draw = self._next_draw()
         if x.is_cuda:
             y, stat = dsp.DistortFn.apply(x.to(torch.float32), self.bounds, self.seed, draw, row0, self.noise_grad == "through")
@@ -215,19 +145,7 @@ class Distortion(_RowDraws):
         return y
 
     def _host(self, x, draw, row0):
-        n = x.shape[-1]
-        x2 = x.reshape(-1, n)
-        gain_db, snr_db, noisy = row_parameters(self.seed, draw, row0 + np.arange(x2.shape[0]), self.bounds)
-        ms = x2.double().pow(2).mean(dim=1).numpy()
-        g = np.float32(10.0) ** (gain_db.astype(np.float64) / 20.0)
-        s = np.where(noisy, np.abs(g) * np.sqrt(ms) * 10.0 ** (-snr_db.astype(np.float64) / 20.0), 0.0)
-        g32, s32 = g.astype(np.float32), s.astype(np.float32)
-        y = x2 * torch.from_numpy(g32)[:, None]                                   # g = 1 hands x on bit for bit
-        for r in np.nonzero(s32)[0]:
-            z = torch.from_numpy(normal_noise(self.seed, draw, row0 + int(r), n))
-            y[r] = (float(g32[r]) * x2[r].double() + float(s32[r]) * z).float()
-        stat = np.stack([g32, s32, ms.astype(np.float32), np.where(noisy, snr_db, np.float32(np.inf))], axis=1)
-        return y.reshape(x.shape), torch.from_numpy(stat.astype(np.float32))
+        return distort_rows_host(x, draw, row0, self.seed, self.bounds)
 
     def extra_repr(self):
         return (f"gain_db={self.gain_db}, snr_db={self.snr_db}, p_noise={self.p_noise}, seed={self.seed}, "
@@ -272,10 +190,10 @@ class Lowpass(torch.nn.Module):
 
 class Resampled(torch.nn.Module):
     """y = up(down(x))[..., :T] along the last axis of (B, 1, T), (C, N) or (N,), every row by itself: down is sample_rate -> rate, up is
-    rate -> sample_rate, both the sinc resampler of ops.resample_table (torchaudio's default design) without mixdown.  The output has the
+    rate -> sample_rate, both the sinc resampler of dsp.resample_table (torchaudio's default design) without mixdown.  The output has the
     input's shape (ceil(sample_rate * ceil(rate * T / sample_rate) / rate) >= T: the cut is always possible); rate == sample_rate returns
     x.  CUDA: two launches of wm_resample_rows, differentiable through the same two launches with the transposed tables
-    (ops.ResampleRowsFn); CPU: the same float32 tables through F.conv1d, differentiable by autograd."""
+    (dsp.ResampleRowsFn); CPU: the same float32 tables through F.conv1d, differentiable by autograd."""
 
     def __init__(self, rate, sample_rate=SAMPLE_RATE):
         super().__init__()
@@ -298,13 +216,6 @@ class Resampled(torch.nn.Module):
 
     def extra_repr(self):
         return f"rate={self.rate}, sample_rate={self.sample_rate}"
-
-
-def row_snr_db(seed, draw, rows, snr_db):
-    """TransformCodec's per-row quality for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the counter
-    Distortion draws a row's parameters from -- the word Distortion leaves unused, so the two never share a number -- mapped onto the pair
-    snr_db as fmaf(high - low, u, low)"""
-    return _affine(snr_db, _unit(_words("param", seed, draw, rows)[3]))
 
 
 def code_entropy_kbps(codes, band, kcut, hop, sample_rate):
@@ -335,7 +246,7 @@ class TransformCodec(_RowDraws):
     Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
     pieces draws what the whole batch would.  `last_snr_db`: the per-row values of the last call (a CPU tensor).
     grad "straight_through": the quantiser passes the gradient unchanged, the cut is kept | "dead_zone": coefficients coded 0 pass none
-    (ops.MdctCodecFn; the step's dependence on x is not differentiated).  CUDA tensors run the kernel, one launch each way; CPU tensors a
+    (dsp.MdctCodecFn; the step's dependence on x is not differentiated).  CUDA tensors run the kernel, one launch each way; CPU tensors a
     float32 numpy restatement of the definition (forward only)."""
 
     def __init__(self, snr_db=(10, 30), bandwidth_hz=None, hop=256, band=8, sample_rate=SAMPLE_RATE, seed=0, grad="straight_through"):
@@ -353,8 +264,8 @@ class TransformCodec(_RowDraws):
 
     def _snr(self, x, row0):
         """x as time rows and the per-row quality of the CURRENT draw, which it does not advance"""
-        x, rows = self._rows(x, row0)
-        return x, torch.from_numpy(row_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
+        x, _, numbers = self._rows(x, row0)
+        return x, torch.from_numpy(row_snr_db(self.seed, self.draw, numbers, self.snr_db))
 
     def forward(self, x, row0=0):
         x, snr = self._snr(x, row0)
@@ -367,26 +278,8 @@ class TransformCodec(_RowDraws):
         return y
 
     def _host(self, x, snr):
-        """(y, int16 codes (rows, F, hop)) of a CPU tensor: the definition in float32 numpy, dense matrices"""
-        M, band, n, f32 = self.hop, self.band, x.shape[-1], np.float32
-        x2 = x.reshape(-1, n).numpy()
-        rows, F = x2.shape[0], dsp.mdct_frames(n, M)
-        j, k = np.arange(2 * M, dtype=np.float64), np.arange(M, dtype=np.float64)
-        w = np.sin(np.pi * (j + 0.5) / (2 * M)).astype(f32)
-        C = np.cos(np.pi / M * np.outer(k + 0.5, j + 0.5 + M / 2)).astype(f32)
-        xp = np.zeros((rows, (F + 1) * M), dtype=f32)
-        xp[:, M:M + n] = x2
-        X = (np.stack([xp[:, f * M:(f + 2) * M] for f in range(F)], axis=1) * w) @ C.T
-        X[:, :, self.kcut:] = 0
-        P = (X.reshape(rows, F, M // band, band) ** 2).mean(axis=3, dtype=f32)
-        scale = (f32(10) ** (-snr.numpy() / f32(20))).astype(f32).reshape(rows, 1, 1)
-        step = np.repeat(np.maximum(np.sqrt(f32(12) * P) * scale, f32(self.floor_step)), band, axis=2)
-        q = np.rint(X / step)
-        yf = f32(2.0 / M) * w * ((q * step) @ C)
-        out = np.zeros_like(xp)
-        for f in range(F):
-            out[:, f * M:(f + 2) * M] += yf[:, f]
-        return torch.from_numpy(np.ascontiguousarray(out[:, M:M + n])).reshape(x.shape), torch.from_numpy(q.astype(np.int16))
+        """(y, int16 codes (rows, F, hop)) of a CPU tensor"""
+        return mdct_codec_rows_host(x, snr, self.hop, self.band, self.kcut, self.floor_step)
 
     @torch.no_grad()
     def estimate_kbps(self, x, row0=0):
@@ -406,63 +299,6 @@ class TransformCodec(_RowDraws):
                 f"sample_rate={self.sample_rate}, seed={self.seed}, grad={self.grad!r}")
 
 
-def row_lpc_snr_db(seed, draw, rows, snr_db):
-    """LpcCodec's per-row quality for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the "param2"
-    counter -- Reverb and Convolved use its first three, so no two attacks share a number -- mapped onto the pair snr_db as
-    fmaf(high - low, u, low)"""
-    return _affine(snr_db, _unit(_words("param2", seed, draw, rows)[3]))
-
-
-def _lpc_rows_host(x2, snr, L, p, sample_rate, floor_step):
-    """wm_lpc_codec's forward on a (rows, n) float32 array in float32 numpy: (y, coefficients (rows, F, p), int16 codes (rows, n)).  The
-    definition of include/wm_hip.h with numpy's own summation order inside the autocorrelation and the frame energy."""
-    f32 = np.float32
-    rows, n = x2.shape
-    F = dsp.lpc_frames(n, L)
-    lag, expand = (t.numpy() for t in dsp.lpc_tables(p, sample_rate))
-    j = np.arange(2 * L, dtype=np.float64)
-    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * (j + 0.5) / (2 * L))).astype(f32)
-    xp = np.zeros((rows, L // 2 + F * L + L), dtype=f32)
-    xp[:, L // 2:L // 2 + n] = x2
-    s = np.stack([xp[:, f * L:f * L + 2 * L] for f in range(F)], axis=1) * w                       # (rows, F, 2L)
-    Rc = np.stack([(s[..., :2 * L - k] * s[..., k:]).sum(axis=-1, dtype=f32) for k in range(p + 1)], axis=-1) * lag
-    a = np.zeros((rows, F, p + 1), dtype=f32)                                                      # a[..., k] is tap k; entry 0 unused
-    E = Rc[..., 0].copy()
-    go = E > 0
-    E = np.where(go, E, f32(1))
-    for i in range(1, p + 1):
-        acc = Rc[..., i].copy()
-        for m in range(1, i):
-            acc = acc + a[..., m] * Rc[..., i - m]
-        k = -acc / E
-        go = go & (np.abs(k) < 1)
-        k = np.where(go, k, f32(0)).astype(f32)
-        a[..., 1:i] = a[..., 1:i] + k[..., None] * a[..., i - 1:0:-1]
-        a[..., i] = k
-        E = (E * (f32(1) - k * k)).astype(f32)
-    a = (a[..., 1:] * expand).astype(f32)
-    at = np.repeat(a, L, axis=1)[:, :n]                                                            # (rows, n, p): the set of sample t
-    hist = np.zeros((rows, n + p), dtype=f32)
-    hist[:, p:] = x2
-    e = x2.copy()
-    for k in range(1, p + 1):
-        e = e + at[:, :, k - 1] * hist[:, p - k:p - k + n]
-    ep = np.zeros((rows, F * L), dtype=f32)
-    ep[:, :n] = e
-    cnt = np.minimum(L, n - L * np.arange(F)).astype(f32)
-    P = (ep.reshape(rows, F, L) ** 2).sum(axis=2, dtype=f32) / cnt
-    snr = np.nan_to_num(np.asarray(snr, dtype=f32), nan=0.0).clip(0, 60)
-    g = (10.0 ** (-snr.astype(np.float64) / 20.0)).astype(f32).reshape(rows, 1)
-    step = np.repeat(np.maximum(np.sqrt(f32(12) * P) * g, f32(floor_step)), L, axis=1)[:, :n]
-    q = np.rint(e / step)
-    eq = (q * step).astype(f32)
-    y = np.zeros((rows, n + p), dtype=f32)                                                         # y[:, p + t]; the first p are the silence before
-    ar = at[:, :, ::-1]
-    for t in range(n):
-        y[:, p + t] = eq[:, t] - (ar[:, t] * y[:, t:t + p]).sum(axis=1, dtype=f32)
-    return np.ascontiguousarray(y[:, p:]), a, q.astype(np.int16)
-
-
 class LpcCodec(_RowDraws):
     """A STAND-IN for a predictive speech codec on every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): the signal path ADPCM, CELP,
     AMR-WB and SILK share -- per frame of `frame` samples an order-`order` linear predictor from the windowed autocorrelation, the
@@ -475,7 +311,7 @@ class LpcCodec(_RowDraws):
     Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
     pieces draws what the whole batch would.  `last_snr_db`: the per-row values of the last call (a CPU tensor).
     grad "straight_through": the gradient is dy itself (with the quantiser passed through, synthesis inverts the residual filter) |
-    "dead_zone": residual samples coded 0 pass none -- the adjoint launch at the forward's coefficients (ops.LpcCodecFn; the dependence of
+    "dead_zone": residual samples coded 0 pass none -- the adjoint launch at the forward's coefficients (dsp.LpcCodecFn; the dependence of
     the coefficients and steps on x is not differentiated).  CUDA tensors run the kernel; CPU tensors a float32 numpy restatement of the
     definition (forward only)."""
 
@@ -494,8 +330,8 @@ class LpcCodec(_RowDraws):
         self.last_snr_db = None
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
-        snr = torch.from_numpy(row_lpc_snr_db(self.seed, self.draw, row0 + np.arange(rows), self.snr_db))
+        x, rows, numbers = self._rows(x, row0)
+        snr = torch.from_numpy(row_lpc_snr_db(self.seed, self.draw, numbers, self.snr_db))
         self._next_draw()
         if x.is_cuda:
             y = dsp.LpcCodecFn.apply(x.to(torch.float32), snr.to(x.device), self.frame, self.order, self.sample_rate, self.floor_step,
@@ -511,13 +347,6 @@ class LpcCodec(_RowDraws):
     def extra_repr(self):
         return (f"snr_db={self.snr_db}, frame={self.frame}, order={self.order}, sample_rate={self.sample_rate}, seed={self.seed}, "
                 f"grad={self.grad!r}")
-
-
-def row_reduce_db(seed, draw, rows, reduce_db):
-    """NoiseSuppress's per-row depth for rows `rows` (an int array of row0 + r), a float32 array: the FOURTH output word of the "warp_phase"
-    counter -- TimeWarp, TimeStretch and PitchShift use its first three, so no two attacks share a number -- mapped onto the pair
-    reduce_db as fmaf(high - low, u, low)"""
-    return _affine(reduce_db, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[3]))
 
 
 class NoiseSuppress(_RowDraws):
@@ -552,11 +381,11 @@ class NoiseSuppress(_RowDraws):
         self.last_reduce_db = None
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         x32 = x.to(torch.float32)
         x2 = x32.reshape(rows, x.shape[-1])
         prof = suppress._profile_rows(self.noise_psd, rows, x.device)            # a profile for another number of rows fails here
-        rd = torch.from_numpy(row_reduce_db(self.seed, self.draw, row0 + np.arange(rows), self.reduce_db))
+        rd = torch.from_numpy(row_reduce_db(self.seed, self.draw, numbers, self.reduce_db))
         self._next_draw()
         if x.is_cuda:
             y = suppress.NoiseSuppressFn.apply(x2, rd.to(x.device), prof, self.alpha, self.over)
@@ -568,42 +397,6 @@ class NoiseSuppress(_RowDraws):
     def extra_repr(self):
         prof = None if self.noise_psd is None else tuple(self.noise_psd.shape)
         return f"reduce_db={self.reduce_db}, over={self.over}, alpha={self.alpha}, noise_psd={prof}, seed={self.seed}"
-
-
-def row_reverb_params(seed, draw, rows, rt60, drr_db):
-    """Reverb's (rt60, drr_db) of rows `rows` (an int array of row0 + r), two float32 arrays: words o0 and o1 of the counter
-    (0xFFFFFFFE, 0xFFFFFFFF, row, draw) -- next to Distortion's parameter counter, met by nothing else -- mapped onto the pairs as
-    fmaf(high - low, u, low) in float32"""
-    o = _words("param2", seed, draw, rows)
-    return _affine(rt60, _unit(o[0])), _affine(drr_db, _unit(o[1]))
-
-
-def row_bank_index(seed, draw, rows, entries):
-    """Convolved's choice among `entries` responses for rows `rows`: floor(u(o2) * entries) of the same counter, an int64 array"""
-    return np.floor(_unit(_words("param2", seed, draw, rows)[2]) * int(entries)).astype(np.int64)
-
-
-def rir_taps(seed, draw, row, rt60, drr_db, K, sample_rate):
-    """The synthetic response wm_rir_synth gives row `row` (= row0 + r), restated in float64: e[0] = 0, e[k] = z_k exp(-k c) with
-    c = 3 ln 10 / (rt60 * sample_rate) and z_k the normal of "sample" k of the counter (k >> 2, 0xFFFFFFFE, row, draw);
-    h[0] = 1 / sqrt(1 + w), h[k] = sqrt(w / sum e^2) e[k] / sqrt(1 + w), w = 10^(-drr_db / 10).  rt60 and drr_db enter as float32 values,
-    drr_db clamped to [-100, 100]; K = 1, sum e^2 = 0, rt60 not > 0 or a non-finite drr_db give {1, 0, ...}."""
-    K = int(K)
-    rt60, drr_db = float(np.float32(rt60)), float(np.float32(drr_db))
-    h = np.zeros(K, dtype=np.float64)
-    h[0] = 1.0
-    if K == 1 or not rt60 > 0.0 or not math.isfinite(drr_db):
-        return h
-    c = 3.0 * math.log(10.0) / (rt60 * float(np.float32(sample_rate)))
-    e = _normals(seed, draw, row, K, "rir_tap") * np.exp(-np.arange(K, dtype=np.float64) * c)
-    e[0] = 0.0
-    E = float(np.sum(e * e))
-    if not E > 0.0:
-        return h
-    w = 10.0 ** (-min(max(drr_db, -100.0), 100.0) / 10.0)
-    h = math.sqrt(w / E) * e / math.sqrt(1.0 + w)
-    h[0] = 1.0 / math.sqrt(1.0 + w)
-    return h
 
 
 def echo_ir(delay_s, gain_db, sample_rate=SAMPLE_RATE):
@@ -623,13 +416,6 @@ def echo_ir(delay_s, gain_db, sample_rate=SAMPLE_RATE):
     return h.to(torch.float32)
 
 
-def _conv_rows_host(rows2d, h):
-    """H x per row of a (rows, n) float32 CPU tensor, h (K,) or (rows, K): F.conv1d with one group per row, which autograd differentiates"""
-    rows, K = rows2d.shape[0], h.shape[-1]
-    w = (h.expand(rows, K) if h.dim() == 1 else h).flip(-1).reshape(rows, 1, K)
-    return F.conv1d(F.pad(rows2d.unsqueeze(0), (K - 1, 0)), w, groups=rows)[0]
-
-
 class Convolved(_RowDraws):
     """y = h * x, causal and cut to the input's length, for every row (clip or channel) of x, (B, 1, T), (C, N) or (N,): lag 0 stays at
     lag 0, so per-sample labels stay aligned.  h: a (K,) impulse response for all rows, or an (R, K) bank of (measured) responses, of which
@@ -637,7 +423,7 @@ class Convolved(_RowDraws):
     scaled to unit energy first (a response of zero energy is refused).  Every forward uses the next `draw`; reset(draw) rewinds; `row0`
     (forward's argument) numbers the first row, so that a batch cut into pieces draws what the whole batch would.  `last_index`: the bank
     entries of the last call (a CPU tensor; None without a bank).  h is a constant: no gradient flows to it.
-    CUDA tensors run wm_fir_rows, one launch each way (ops.FirRowsFn); CPU tensors F.conv1d in float32, differentiable by autograd."""
+    CUDA tensors run wm_fir_rows, one launch each way (dsp.FirRowsFn); CPU tensors F.conv1d in float32, differentiable by autograd."""
 
     def __init__(self, h, normalize=False, seed=0):
         if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2) or h.numel() == 0 or not 1 <= h.shape[-1] <= dsp.FIR_MAX_TAPS:
@@ -659,12 +445,12 @@ class Convolved(_RowDraws):
         self.last_index = None
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         draw = self._next_draw()
         h = self.h if self.h.device == x.device else self.h.to(x.device)
         self.last_index = None
         if h.dim() == 2:
-            self.last_index = torch.from_numpy(row_bank_index(self.seed, draw, row0 + np.arange(rows), h.shape[0]))
+            self.last_index = torch.from_numpy(row_bank_index(self.seed, draw, numbers, h.shape[0]))
             h = h[self.last_index.to(x.device)]                                   # gathered on the device: per-row taps
         x32 = x.to(torch.float32)
         if x.is_cuda:
@@ -685,7 +471,7 @@ class Reverb(_RowDraws):
     Every forward uses the next `draw` (fresh parameters and responses); reset(draw) rewinds; `row0` (forward's argument) numbers the
     first row, so that a batch cut into pieces draws what the whole batch would.  `last_params`: the (rows, 2) {rt60, drr_db} of the last
     call (a CPU tensor); `last_ir`: its (rows, taps) responses (on x's device).  The responses are constants of the graph.
-    CUDA tensors run wm_rir_synth and wm_fir_rows (ops.FirRowsFn, one launch each way); CPU tensors rir_taps and F.conv1d in float32,
+    CUDA tensors run wm_rir_synth and wm_fir_rows (dsp.FirRowsFn, one launch each way); CPU tensors rir_taps and F.conv1d in float32,
     differentiable by autograd."""
 
     def __init__(self, rt60=(0.1, 0.4), drr_db=(0, 12), taps=2048, sample_rate=SAMPLE_RATE, seed=0):
@@ -698,9 +484,9 @@ class Reverb(_RowDraws):
         self.last_params = self.last_ir = None
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         draw = self._next_draw()
-        rt60, drr = row_reverb_params(self.seed, draw, row0 + np.arange(rows), self.rt60, self.drr_db)
+        rt60, drr = row_reverb_params(self.seed, draw, numbers, self.rt60, self.drr_db)
         self.last_params = torch.from_numpy(np.stack([rt60, drr], axis=1))
         x32 = x.to(torch.float32)
         if x.is_cuda:
@@ -715,61 +501,6 @@ class Reverb(_RowDraws):
 
     def extra_repr(self):
         return f"rt60={self.rt60}, drr_db={self.drr_db}, taps={self.taps}, sample_rate={self.sample_rate}, seed={self.seed}"
-
-
-def row_warp_params(seed, draw, rows, speed, shift_s, flutter_hz, flutter_depth, sample_rate):
-    """TimeWarp's (len(rows), 6) float32 parameters {a, off, d, w, phi, c} of rows `rows` (an int array of row0 + r), the rows of
-    wm_time_warp's `params`.  speed, shift_s, flutter_hz, flutter_depth: (low, high) pairs (the last two None: no flutter).  Words o0..o3
-    of the counter (0xFFFFFFFD, 0xFFFFFFFF, row, draw) -- met by nothing else -- map onto speed, shift, flutter rate and flutter depth as
-    fmaf(high - low, u, low) in float32, word o0 of (0xFFFFFFFC, 0xFFFFFFFF, row, draw) is the phase u.  From these float32 draws, in
-    float64 and rounded to float32 once each: a = speed, off = shift * sample_rate, w = rate / sample_rate, d = depth a / (2 pi w) with the
-    rounded w (0 where w or depth is 0), phi = u, c = min(1, 1 / (a (1 + depth)))."""
-    rows = np.asarray(rows, dtype=np.uint64)
-    o = _words("warp", seed, draw, rows)
-    phase = _unit(_words("warp_phase", seed, draw, rows)[0])
-    flutter = flutter_hz is not None and flutter_depth is not None
-    a = _affine(speed, _unit(o[0])).astype(np.float64)
-    shift = _affine(shift_s, _unit(o[1])).astype(np.float64)
-    hz = _affine(flutter_hz, _unit(o[2])).astype(np.float64) if flutter else np.zeros(len(rows))
-    depth = _affine(flutter_depth, _unit(o[3])).astype(np.float64) if flutter else np.zeros(len(rows))
-    w = (hz / float(sample_rate)).astype(np.float32)
-    on = (w != 0) & (depth != 0)
-    d = np.where(on, depth * a / (2.0 * math.pi * np.where(on, w.astype(np.float64), 1.0)), 0.0)
-    c = np.minimum(1.0, 1.0 / (a * (1.0 + depth)))
-    return np.stack([a, shift * float(sample_rate), d, w.astype(np.float64), np.where(on, phase, 0.0), c], axis=1).astype(np.float32)
-
-
-def _sinpi(v):
-    """sin(pi v) of a float64 tensor, reduced to [-1/2, 1/2] first so that the argument of sin carries no rounding of pi v at large v"""
-    k = torch.round(v)
-    return torch.sin(math.pi * (v - k)) * (1.0 - 2.0 * torch.remainder(k, 2.0))
-
-
-def _warp_rows_host(x2, params, table, zeros, res):
-    """wm_time_warp's forward map on a (rows, n) float32 CPU tensor in torch ops, which autograd differentiates: positions and weights from
-    the definition (fp64 positions, float32 table, float32 weights), the taps gathered per output sample and summed in float32.  Row by
-    row, so that a row's bits do not depend on the rest of the batch."""
-    n = x2.shape[1]
-    t = torch.arange(n, dtype=torch.float64)
-    out = []
-    for xr, prm in zip(x2, params):
-        a, off, d, w, phi = (float(v) for v in prm[:5])
-        c32 = torch.tensor(1.0 if math.isnan(float(prm[5])) else min(max(float(prm[5]), 0.25), 1.0), dtype=torch.float32)
-        c = float(c32)
-        q = w * t + phi
-        p = a * t + off + d * _sinpi(2.0 * (q - torch.floor(q)))
-        H = int(math.ceil(zeros / c))
-        k = (torch.floor(p) - H)[:, None] + torch.arange(2 * H + 2, dtype=torch.float64)      # covers (p - H - 1, p + H + 1]
-        v = c * (p[:, None] - k).abs()
-        inside = (v < zeros) & (k >= 0) & (k < n)
-        s = v * res
-        i = torch.floor(s).clamp(0, zeros * res - 1)
-        f = (s - i).to(torch.float32)
-        i = i.to(torch.int64)
-        t0 = table[i]
-        W = torch.where(inside, c32 * (f * (table[i + 1] - t0) + t0), torch.zeros((), dtype=torch.float32))
-        out.append((W * xr[k.clamp(0, n - 1).to(torch.int64)]).sum(dim=-1))
-    return torch.stack(out)
 
 
 class TimeWarp(_RowDraws):
@@ -787,7 +518,7 @@ class TimeWarp(_RowDraws):
     Every forward uses the next `draw`; reset(draw) rewinds; `row0` (forward's argument) numbers the first row, so that a batch cut into
     pieces draws what the whole batch would.  `last_params`: the (rows, 6) {a, off, d, w, phi, c} of the last call (a CPU tensor).  The
     parameters are constants of the graph.  There is no shortcut for speed 1: the kernel hands a whole-sample shift on bit for bit.
-    CUDA tensors run wm_time_warp, one launch each way (ops.TimeWarpFn); CPU tensors the same definition in torch ops (gathered taps times
+    CUDA tensors run wm_time_warp, one launch each way (dsp.TimeWarpFn); CPU tensors the same definition in torch ops (gathered taps times
     float32 weights), differentiable by autograd."""
 
     RES = 512
@@ -812,9 +543,9 @@ class TimeWarp(_RowDraws):
         self.last_params = None
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         draw = self._next_draw()
-        self.last_params = torch.from_numpy(row_warp_params(self.seed, draw, row0 + np.arange(rows), self.speed, self.shift_s,
+        self.last_params = torch.from_numpy(row_warp_params(self.seed, draw, numbers, self.speed, self.shift_s,
                                                             self.flutter_hz, self.flutter_depth, self.sample_rate))
         x2 = x.to(torch.float32).reshape(rows, -1)
         if x.is_cuda:
@@ -827,67 +558,6 @@ class TimeWarp(_RowDraws):
     def extra_repr(self):
         return (f"speed={self.speed}, shift_s={self.shift_s}, flutter_hz={self.flutter_hz}, flutter_depth={self.flutter_depth}, "
                 f"zeros={self.zeros}, sample_rate={self.sample_rate}, seed={self.seed}")
-
-
-def row_stretch_rates(seed, draw, rows, rate):
-    """TimeStretch's float32 rate of rows `rows` (an int array of row0 + r): word o1 of the counter (0xFFFFFFFC, 0xFFFFFFFF, row, draw) --
-    TimeWarp's flutter phase is its word o0 -- onto the pair `rate` as fmaf(high - low, u, low) in float32"""
-    return _affine(rate, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[1]))
-
-
-def row_pitch_params(seed, draw, rows, semitones):
-    """PitchShift's (semitones, beta, rate) of rows `rows`, three float32 arrays: word o2 of the counter (0xFFFFFFFC, 0xFFFFFFFF, row,
-    draw) onto the pair `semitones` as fmaf(high - low, u, low) in float32; beta = float32(2^(st / 12)) and rate = float32(1 / beta), each
-    formed in float64 from the float32 value before it"""
-    st = _affine(semitones, _unit(_words("warp_phase", seed, draw, np.asarray(rows, dtype=np.uint64))[2]))
-    beta = np.exp2(st.astype(np.float64) / 12.0).astype(np.float32)
-    return st, beta, (1.0 / beta.astype(np.float64)).astype(np.float32)
-
-
-def _wsola_rows_host(x2, rates, n_out, L, S):
-    """wm_wsola's modes 0 and 1 on a (rows, n) float32 CPU tensor in torch ops: (y, delta).  The search runs on the values alone (the
-    float32 scores summed in torch's order, the tie order of the definition); the synthesis is a gather at the chosen positions --
-    constants -- and w u + (1 - w) v in float64 rounded to float32 once (u where u = v, bit for bit), which autograd differentiates
-    with the weights w and 1 - w of the adjoint's definition.  Row by row."""
-    rows, n = x2.shape
-    hs = L // 2
-    K = dsp.wsola_frames(n_out, L)
-    win = dsp.wsola_window(L)
-    cand = torch.arange(-S, S + 1)
-    order = torch.argsort(torch.where(cand == 0, 0, torch.where(cand < 0, -2 * cand - 1, 2 * cand)))     # 0, -1, +1, -2, +2, ...
-    j = torch.arange(hs)
-    delta = torch.zeros((rows, K), dtype=torch.int32)
-    out = []
-    for r in range(rows):
-        rate = float(np.float32(rates[r]))
-        if not (0.25 <= rate <= 4.0):
-            out.append(torch.zeros(n_out, dtype=torch.float32))
-            continue
-        xd = x2[r].detach()
-        a = np.floor(rate * ((np.arange(K, dtype=np.float64) - 1.0) * hs) + 0.5).astype(np.int64)
-        p = np.zeros(K, dtype=np.int64)
-        p[0] = a[0]
-        for k in range(1, K):
-            q, c0 = int(p[k - 1]) + hs, int(a[k]) - S
-            T, C = _gather_ext(xd, q + torch.arange(L), n), _gather_ext(xd, c0 + torch.arange(L + 2 * S), n)
-            d = T[None, :] - C.unfold(0, L, 1)
-            score = (d * d).sum(dim=1)[order]
-            score = torch.where(torch.isnan(score), torch.full_like(score, float("inf")), score)
-            dk = int(cand[order[int(torch.argmin(score))]])                      # the first of the smallest; all NaN: candidate 0
-            delta[r, k] = dk
-            p[k] = a[k] + dk
-        pt = torch.from_numpy(p)
-        u = _gather_ext(x2[r], (pt[1:, None] + j[None, :]).reshape(-1), n)
-        v = _gather_ext(x2[r], (pt[:-1, None] + hs + j[None, :]).reshape(-1), n)
-        w = win.double().repeat(K - 1)                                             # 1 - w is exact in float64
-        out.append((w * u.double() + (1.0 - w) * v.double()).to(torch.float32)[:n_out])
-    return torch.stack(out), delta
-
-
-def _gather_ext(xr, idx, n):
-    """xr[idx] with zeros where idx leaves [0, n)"""
-    inside = (idx >= 0) & (idx < n)
-    return torch.where(inside, xr[idx.clamp(0, n - 1)], torch.zeros((), dtype=xr.dtype))
 
 
 class _Wsola(_RowDraws):
@@ -923,7 +593,7 @@ class TimeStretch(_Wsola):
     numbers the first row, so that a batch cut into pieces draws what the whole batch would.  `last_params`: the (rows,) float32 rates of
     the last call (a CPU tensor); `last_delta`: its (rows, K) int32 offsets, where they were computed.  The chosen positions are constants
     of the graph: the gradient is that of the linear gather.  At rate 1 the output is the input bit for bit.
-    CUDA tensors run wm_wsola, one launch each way (ops.WsolaFn); CPU tensors the same definition in torch ops, differentiable by autograd."""
+    CUDA tensors run wm_wsola, one launch each way (dsp.WsolaFn); CPU tensors the same definition in torch ops, differentiable by autograd."""
 
     def __init__(self, rate=(0.9, 1.1), frame=512, search=128, seed=0):
         super().__init__(frame, search, seed)
@@ -932,9 +602,9 @@ class TimeStretch(_Wsola):
             raise ValueError(f"rate: expected values in [0.5, 2], got {rate!r}")
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         draw = self._next_draw()
-        rates = row_stretch_rates(self.seed, draw, row0 + np.arange(rows), self.rate)
+        rates = row_stretch_rates(self.seed, draw, numbers, self.rate)
         self.last_params = torch.from_numpy(rates)
         x2 = x.to(torch.float32).reshape(rows, -1)
         return self._stretch(x2, rates, x2.shape[1]).reshape(x.shape)
@@ -952,7 +622,7 @@ class PitchShift(_Wsola):
     PITCH SHIFT IS UNMEASURED -- and formants move with the pitch.  The output keeps the input's length and the labels are not moved.
     semitones in [-12, 12]: a number fixes it, a pair draws one per row from (seed, draw, row0 + r) (row_pitch_params).  `last_params`: the
     (rows, 3) float32 {semitones, beta, rate} of the last call (a CPU tensor); `last_delta`: the stretch's offsets.  seed, draw, reset and
-    row0 as in TimeStretch.  CUDA tensors run the two launches (ops.WsolaFn, ops.TimeWarpFn), CPU tensors the same definitions in torch
+    row0 as in TimeStretch.  CUDA tensors run the two launches (dsp.WsolaFn, dsp.TimeWarpFn), CPU tensors the same definitions in torch
     ops, differentiable by autograd."""
 
     RES = TimeWarp.RES
@@ -966,9 +636,9 @@ class PitchShift(_Wsola):
         self.zeros = zeros
 
     def forward(self, x, row0=0):
-        x, rows = self._rows(x, row0)
+        x, rows, numbers = self._rows(x, row0)
         draw = self._next_draw()
-        st, beta, rates = row_pitch_params(self.seed, draw, row0 + np.arange(rows), self.semitones)
+        st, beta, rates = row_pitch_params(self.seed, draw, numbers, self.semitones)
         self.last_params = torch.from_numpy(np.stack([st, beta, rates], axis=1))
         x2 = x.to(torch.float32).reshape(rows, -1)
         n = x2.shape[1]
@@ -989,92 +659,6 @@ class PitchShift(_Wsola):
         return f"semitones={self.semitones}, frame={self.frame}, search={self.search}, zeros={self.zeros}, seed={self.seed}"
 
 
-SPLICE_KINDS = ("original", "silence", "moved")           # the `kind` of a span: 0, 1, 2
-
-
-def _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence):
-    n = int(n)
-    if not 1 <= n <= dsp.SPLICE_MAX_N:
-        raise ValueError(f"n: expected 1 <= n <= 2^24 samples, got {n}")
-    if isinstance(max_spans, bool) or not isinstance(max_spans, (int, np.integer)) or not 1 <= max_spans <= dsp.SPLICE_MAX_SPANS:
-        raise ValueError(f"max_spans: expected an int in [1, {dsp.SPLICE_MAX_SPANS}], got {max_spans!r}")
-    if not 1 <= int(len_lo) <= int(len_hi) <= n:
-        raise ValueError(f"span lengths: expected 1 <= len_lo <= len_hi <= n = {n} samples, got {len_lo!r} and {len_hi!r}")
-    p = [np.float32(v) for v in (p_span, p_original, p_silence)]
-    if not all(0.0 <= float(v) <= 1.0 for v in p) or float(p[1]) + float(p[2]) > 1.0:
-        raise ValueError(f"probabilities: expected p_span, p_original, p_silence in [0, 1] with p_original + p_silence <= 1 (as float32 "
-                         f"values), got {p_span!r}, {p_original!r}, {p_silence!r}")
-    return n, int(max_spans), int(len_lo), int(len_hi), float(p[0]), float(p[1]), float(p[1]) + float(p[2])
-
-
-def row_splice_spans(seed, draw, rows, n, max_spans=2, p_span=0.5, len_lo=800, len_hi=6400, p_original=1 / 3, p_silence=1 / 3):
-    """The spans wm_splice draws for rows `rows` (an int array of row0 + r) of n samples: per row a list of max_spans tuples
-    (start, L, kind, shift, active), ints and a bool, kind an index into SPLICE_KINDS.  Span j takes the words o0..o3 of the counter
-    (0xFFFFFFFB - 2j, 0xFFFFFFFF, row, draw) and the first word o0' of (0xFFFFFFFA - 2j, 0xFFFFFFFF, row, draw): active iff u(o0) < p_span,
-    L = len_lo + ((v(o1) (len_hi - len_lo + 1)) >> 23), start = (v(o2) (n - L + 1)) >> 23, kind from u(o3) against p_original and
-    p_original + p_silence, shift = 1 + ((v(o0') (n - 1)) >> 23), with v(o) = o >> 9 and u = (v + 0.5) 2^-23.  The probabilities enter as
-    float32 values and are compared in float64, the products are integers: nothing is rounded.  n = 1: "moved" is reported, and acts, as
-    "original".  An inactive span keeps the geometry it drew."""
-    n, max_spans, len_lo, len_hi, p_span, t_original, t_silence = _check_cut(n, max_spans, p_span, len_lo, len_hi, p_original, p_silence)
-    rows = np.asarray(rows, dtype=np.uint64).reshape(-1)
-    out = [[] for _ in rows]
-    for j in range(max_spans):
-        o, o2 = _words(f"splice_span{j}", seed, draw, rows), _words(f"splice_shift{j}", seed, draw, rows)[0]
-        for i in range(len(rows)):
-            v = [int(o[k][i]) >> 9 for k in range(4)]
-            L = len_lo + ((v[1] * (len_hi - len_lo + 1)) >> 23)
-            start = (v[2] * (n - L + 1)) >> 23
-            u3 = (v[3] + 0.5) * 2.0 ** -23
-            kind = 0 if u3 < t_original else (1 if u3 < t_silence else 2)
-            if n == 1 and kind == 2:
-                kind = 0
-            shift = 1 + (((int(o2[i]) >> 9) * (n - 1)) >> 23)
-            out[i].append((start, L, kind, shift, bool((v[0] + 0.5) * 2.0 ** -23 < p_span)))
-    return out
-
-
-def splice_rows_host(a, b, seed, draw, row0=0, **cut):
-    """wm_splice restated in numpy: a (watermarked) and b (clean) float32 arrays (rows, n); `cut`: row_splice_spans's keywords.  Returns
-    (y float32 (rows, n), labels bool (rows, n)): spans applied in rising j, so the largest active j that holds a sample decides it;
-    y = b (original), +0 (silence) or b[(t + shift) mod n] (moved) there, and a elsewhere; samples are copied, never computed with."""
-    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-    if a.ndim != 2 or a.shape != b.shape or a.size == 0:
-        raise ValueError(f"a and b: expected two (rows, n) arrays of one shape, got {a.shape} and {b.shape}")
-    rows, n = a.shape
-    y, labels = a.copy(), np.ones((rows, n), dtype=bool)
-    for r, spans in enumerate(row_splice_spans(seed, draw, int(row0) + np.arange(rows), n, **cut)):
-        for start, L, kind, shift, active in spans:
-            if not active:
-                continue
-            t = np.arange(start, start + L)
-            labels[r, t] = False
-            y[r, t] = b[r, t] if kind == 0 else (np.float32(0.0) if kind == 1 else b[r, (t + shift) % n])
-    return y, labels
-
-
-def pack_labels(labels):
-    """bool (rows, n) -> the mask layout, a uint32 array (rows, ceil(n / 32)): bit j of word w is sample 32 w + j, tail bits zero"""
-    labels = np.asarray(labels, dtype=bool)
-    if labels.ndim != 2:
-        raise ValueError(f"labels: expected a (rows, n) array, got shape {labels.shape}")
-    rows, n = labels.shape
-    W = dsp.label_words(n)
-    padded = np.zeros((rows, W * 32), dtype=np.uint64)
-    padded[:, :n] = labels
-    return (padded.reshape(rows, W, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
-
-
-def unpack_labels(lab, n):
-    """the mask layout ((rows, ceil(n / 32)) uint32 / int32 array or tensor) -> bool array (rows, n)"""
-    if isinstance(lab, torch.Tensor):
-        lab = lab.detach().cpu().numpy()
-    lab = np.ascontiguousarray(lab)
-    if lab.ndim != 2 or lab.dtype not in (np.uint32, np.int32) or lab.shape[1] != dsp.label_words(n):
-        raise ValueError(f"lab: expected a (rows, {dsp.label_words(n)}) uint32 or int32 mask for n = {n}, got {lab.dtype} {lab.shape}")
-    words = lab.view(np.uint32)
-    return (((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)) != 0).reshape(lab.shape[0], -1)[:, :int(n)]
-
-
 class Splice(_RowDraws):
     """The editing attack on every row (clip or channel) of a watermarked signal, (B, 1, T), (C, N) or (N,): up to max_spans spans per row,
     each present with probability p_span, of a length drawn uniformly from length_s (seconds; a number fixes it) at a uniform position, are
@@ -1089,7 +673,7 @@ class Splice(_RowDraws):
     the row's length; WHETHER A MODEL TRAINED WITH IT LOCALISES REAL EDITS IS UNMEASURED.
     Every forward uses the next `draw`; reset(draw) rewinds; `row0` numbers the first row, so that a batch cut into pieces draws what the
     whole batch would (row_splice_spans restates the draw).  `last_labels`: the labels of the last call.  The gradient reaches
-    `watermarked` where the label is 1; `clean` is data.  CUDA tensors run wm_splice, one launch each way (ops.SpliceFn); CPU tensors
+    `watermarked` where the label is 1; `clean` is data.  CUDA tensors run wm_splice, one launch each way (dsp.SpliceFn); CPU tensors
     splice_rows_host (forward only)."""
 
     def __init__(self, max_spans=2, p_span=0.5, length_s=(0.05, 0.4), kinds=(1 / 3, 1 / 3, 1 / 3), seed=0, sample_rate=SAMPLE_RATE):
@@ -1124,7 +708,7 @@ class Splice(_RowDraws):
                     p_silence=self.p_silence)
 
     def forward(self, watermarked, clean, row0=0):
-        a, rows = self._rows(watermarked, row0)
+        a, rows, _ = self._rows(watermarked, row0)
         b = _time_rows(clean, "clean")
         if a.shape != b.shape or a.device != b.device:
             raise ValueError(f"watermarked and clean: expected equal shapes on one device, got {tuple(a.shape)} on {a.device} and "
@@ -1169,7 +753,7 @@ def localization_metrics(tampered_counts, clean_counts):
 def evaluate_localization(generator, detector, batches, tamper, device="cuda", message_bits=16, messages=None, threshold=0.5, codec=None):
     """Does the per-sample track localise?  Every batch s is watermarked (s_w = s + delta, or codec(s + delta)), tampered (s_t, labels =
     tamper(s_w, s), a Splice), and the Detector runs on cat([s_t, s]); its prediction sigmoid(logits[:, :, 0]) > threshold is scored against
-    the labels by ops.loc_counts -- integer counts per row on the device, pooled over all batches.  Eval mode, no_grad.  Returns
+    the labels by dsp.loc_counts -- integer counts per row on the device, pooled over all batches.  Eval mode, no_grad.  Returns
       iou = tp / (tp + fp + fn), precision, recall, sample_accuracy     over the tampered watermarked half ("positive" = still watermarked)
       clean_false_positive_rate = fp / (fp + tn)                         over the clean half, whose labels are all 0
       watermarked_fraction                                               the share of label 1 in the tampered half
@@ -1221,7 +805,7 @@ def evaluate_robustness(generator, detector, batches, attacks, device="cuda", me
     and the per-clip values of all batches are pooled and averaged once, as evaluate_batches does (a ragged last batch weighs by its
     clips).  `messages` (optional list, one tensor per batch) replaces the random draw.
     `quality=("stoi",)` adds what the attack does to the speech itself, three more keys in every row ("none" included), from ONE
-    ops.stoi call per attack on the same 2B rows against the clean s: "stoi" (the attacked watermarked half), "stoi_attack_only" (the
+    dsp.stoi call per attack on the same 2B rows against the clean s: "stoi" (the attacked watermarked half), "stoi_attack_only" (the
     attacked clean half: the gap between the two is what the watermark adds under that attack) and "stoi_rows", the clips pooled --
     clips with fewer than 30 spectral frames have no score and are left out, not averaged in as the sentinel 1e-5 (NaN when none is
     left).  STOI assumes time-aligned signals: under TimeWarp it is low by construction and says nothing.  The default, quality=(), is

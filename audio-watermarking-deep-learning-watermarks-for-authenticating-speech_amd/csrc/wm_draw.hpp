@@ -1,6 +1,7 @@
 // The attacks' counter-based draws on the device (distort.hip, splice.hip): Philox4x32-10 (Salmon et al., SC'11), the 24-bit unit map, and
 // the groups of 4 samples the apply kernels read and write, all in namespace wm.  The counter families are listed once, in
-// attacks.py's FAMILIES; attacks.py restates the generator on the host and tests/draw_yardstick.py checks both.
+// draws.py's FAMILIES, and the output words in use in its WORDS; draws.py restates the generator on the host and tests/draw_yardstick.py
+// checks both.
 #pragma once
 #include "wm_common.hpp"
 

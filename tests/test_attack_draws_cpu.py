@@ -1,7 +1,10 @@
-"""The attacks' draws, frozen: every public draw function of attacks.py at fixed arguments against tests/golden/attack_draws.npz, bit for
-bit.  The file is the package's own output, written by `python tests/test_attack_draws_cpu.py --write` at the last commit before the
+"""The attacks' draws, frozen: every public draw function of the attack layer (draws.py, reached as attacks.<name>) at fixed arguments
+against tests/golden/attack_draws.npz, bit for bit.  The file is the package's own output, written at the last commit before the
 generator, the unit map and the counter families were gathered into one place each -- so neither the package's restatement nor
-tests/draw_yardstick.py can move a draw without this test saying so.  Rewrite the file only for a change that is MEANT to move draws."""
+tests/draw_yardstick.py can move a draw without this test saying so.  It is never rewritten.
+tests/golden/attack_draws_2.npz holds the four draw functions that came after it (LpcCodec's, NoiseSuppress's, TimeStretch's and
+PitchShift's), written by `python tests/test_attack_draws_cpu.py --write` at the last commit before they moved into draws.py.  Rewrite
+it only for a change that is MEANT to move draws."""
 import os
 import sys
 
@@ -9,6 +12,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "attack_draws.npz")
+GOLDEN_2 = os.path.join(HERE, "golden", "attack_draws_2.npz")
 SEEDS = ((7 << 32) + 11, (1 << 63) + (3 << 32) + 5)       # the second: the key split and the signed conversion see bit 63
 DRAWS = (0, 2, 2 ** 32 - 1)
 ROWS = (5 + np.arange(8), np.array([2 ** 32 - 1]))
@@ -40,17 +44,40 @@ def _collect():
     return out
 
 
-def test_every_draw_is_what_it_was():
-    got = _collect()
-    with np.load(GOLDEN) as want:
+def _collect_2():
+    """the four draw functions that came after attack_draws.npz was written, at the same seeds, draws and rows"""
+    from awm_amd import attacks as A
+    out = {}
+    for si, seed in enumerate(SEEDS):
+        for draw in DRAWS:
+            for ri, rows in enumerate(ROWS):
+                k = f"s{si}_d{draw}_r{ri}"
+                out[k + "_lpc_snr_db"] = A.row_lpc_snr_db(seed, draw, rows, (10, 30))
+                out[k + "_reduce_db"] = A.row_reduce_db(seed, draw, rows, (6, 24))
+                out[k + "_rate"] = A.row_stretch_rates(seed, draw, rows, (0.9, 1.1))
+                out[k + "_semitones"], out[k + "_beta"], out[k + "_pitch_rate"] = A.row_pitch_params(seed, draw, rows, (-1, 1))
+    return out
+
+
+def _same(got, golden):
+    with np.load(golden) as want:
         assert sorted(got) == sorted(want.files)
         for k in want.files:
             assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
 
 
+def test_every_draw_is_what_it_was():
+    _same(_collect(), GOLDEN)
+
+
+def test_the_later_draws_are_what_they_were():
+    """attack_draws_2.npz: the package's own output at the last commit before the draws moved into draws.py"""
+    _same(_collect_2(), GOLDEN_2)
+
+
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(HERE))
     if sys.argv[1:] != ["--write"]:
-        sys.exit("usage: python tests/test_attack_draws_cpu.py --write")
-    np.savez_compressed(GOLDEN, **_collect())
-    print(f"wrote {GOLDEN}: {os.path.getsize(GOLDEN)} bytes")
+        sys.exit("usage: python tests/test_attack_draws_cpu.py --write      (writes attack_draws_2.npz alone; attack_draws.npz stays)")
+    np.savez_compressed(GOLDEN_2, **_collect_2())
+    print(f"wrote {GOLDEN_2}: {os.path.getsize(GOLDEN_2)} bytes")
