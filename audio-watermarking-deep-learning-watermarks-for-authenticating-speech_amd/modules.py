@@ -36,8 +36,8 @@ class ResBlock(nn.Module):
 
 def _rb_args(m):
     c1, n1, _, c2, n2 = m.block
-    return (c1.weight, c1.bias, n1.weight, n1.bias, c2.weight, c2.bias, n2.weight, n2.bias,
-            n1.running_mean, n1.running_var, n1.num_batches_tracked, n2.running_mean, n2.running_var, n2.num_batches_tracked)
+    return ops.BlockParams(c1.weight, c1.bias, n1.weight, n1.bias, c2.weight, c2.bias, n2.weight, n2.bias,
+                           n1.running_mean, n1.running_var, n1.num_batches_tracked, n2.running_mean, n2.running_var, n2.num_batches_tracked)
 
 
 def _hooked(*modules):

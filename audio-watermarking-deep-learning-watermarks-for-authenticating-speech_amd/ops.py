@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -511,20 +512,45 @@ def pack_w64(w: torch.Tensor, kw: int, mode: int) -> torch.Tensor:
     return wp
 
 
+# ----------------- the tape's state, by name: tuples still (save_for_backward(*saved), len(), slicing, a caller's plain tuple work as before)
+_T = Optional[torch.Tensor]
+_bn_consts = torch.Tensor.unbind                # (cst) -> sc1, sh1, mean1, is1, sc2, sh2, mean2, is2: the rows of a block's [8,64] cst
+# a ResBlock's parameters, then its BatchNorm buffers, in modules._rb_args order; its gradients come back in the same shape (_block_grads)
+BlockParams = NamedTuple("BlockParams", [(n, _T) for n in "w1 b1 g1 be1 w2 b2 g2 be2 rm1 rv1 nbt1 rm2 rv2 nbt2".split()])
+LstmSaved = NamedTuple("LstmSaved", [(n, _T) for n in "x h gates cst w_ih w_hh".split()])          # what _lstm_fwd keeps for _lstm_bwd
+
+
+class BlockSaved(NamedTuple):
+    """what _resblock_fwd keeps for a backward; mask = the sign bits of the output (None until a tail is formed), cst = _bn_consts"""
+    x: _T; y1: _T; y2: _T; mask: _T; cst: _T; w1: _T; w2: _T; g1: _T; g2: _T
+    sc2 = property(lambda self: self.cst[4])    # BN2's scale and shift: what a consumer needs to form the tail relu(x + y2 * sc2 + sh2)
+    sh2 = property(lambda self: self.cst[5])
+
+
+def _block_grads(grads):                        # (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2) at their BlockParams positions, None for the buffers
+    return BlockParams(*grads, None, None, None, None, None, None)
+
+
+def _cut(seq, *types):
+    """seq (a node's *args, its ctx.saved_tensors) by name: one tuple per type of `types`, in order, then the rest as a tuple"""
+    ends = [sum(len(t._fields) for t in types[:i + 1]) for i in range(len(types))]
+    return (*(t._make(seq[e - len(t._fields):e]) for t, e in zip(types, ends)), tuple(seq[ends[-1]:]))
+
+
 # ------------------------------------------------------------------------------------------ ResBlock
 def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None, stem=None):
-    """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for params = (w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2).
-    Returns (out, saved): saved = (x, y1, y2, mask, cst, w1, w2, g1, g2) for a backward, None from the inference launches.  No ctx.
+    """relu(x + BN2(conv2(relu(BN1(conv1(x)))))) for a BlockParams: (out, saved), a BlockSaved | None from the inference launches.  No ctx.
     tail=False (training mode only): stop in front of the tail -- (None, saved) with mask = None; the kernel that follows forms
-    out = relu(x + y2 * cst[4] + cst[5]) and the mask (ResBlockHead1Fn, DetectorTailFn, or the next block through `pending`).
+    out = relu(x + y2 * saved.sc2 + saved.sh2) and the mask (ResBlockHead1Fn, DetectorTailFn, or the next block through `pending`).
     pending (training mode, tail_in_consumer_applies): the `saved` of the block in front, run with tail=False; x is ignored.  This
     block's conv1 launch (wm_conv64_bf_tail) forms that block's tail on load and writes it -- this block's x -- and its mask; the
     return value is then (out, saved, that mask).
     stem = (s, w, b) of the Conv1d(1, 64, 7) in front (x is ignored): this block's x is that stem's output, formed and written by the
     conv1 launch itself (wm_conv64_bf_stem) where _stem_in_conv1_launches(s) in training mode, else by wm_stem_fwd first."""
-    w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = params
+    w1, b1, g1, be1, w2, b2, g2, be2, rm1, rv1, nbt1, rm2, rv2, nbt2 = BlockParams._make(params)
     if pending is not None:
-        px, py2, pcst = pending[0], pending[2], pending[4]
+        pending = BlockSaved._make(pending)
+        px, py2 = pending.x, pending.y2
         x, pmask = torch.empty_like(px), _tail_mask(px, want_grad)
     if stem is not None:
         ss, sw, sb = stem
@@ -537,12 +563,12 @@ def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None, stem=
     dev, st = x.device, _stream()
     out = torch.empty_like(x) if tail else None
     cst = _f32(8, 64, device=dev)       # sc1 sh1 mean1 is1 sc2 sh2 mean2 is2
-    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
+    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = _bn_consts(cst)
     if training:
         y1, y2 = torch.empty_like(x), torch.empty_like(x)
         stats = _f32(NCU * 128, device=dev)
         if pending is not None:
-            lib.wm_conv64_bf_tail(_p(px), _p(py2), _p(pack_w64_h(w1, 0)), _p(pcst[4]), _p(pcst[5]), _p(b1), _p(x), _p(pmask), _p(y1),
+            lib.wm_conv64_bf_tail(_p(px), _p(py2), _p(pack_w64_h(w1, 0)), _p(pending.sc2), _p(pending.sh2), _p(b1), _p(x), _p(pmask), _p(y1),
                                   _p(stats), B, T, st)
         elif stem is not None:
             lib.wm_conv64_bf_stem(_p(ss), _p(sw), _p(sb), _p(pack_w64_h(w1, 0)), _p(b1), _p(x), _p(y1), _p(stats), B, T, st)
@@ -579,7 +605,7 @@ def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None, stem=
         mu1.copy_(rm1); is1.copy_(torch.rsqrt(rv1 + BN_EPS)); mu2.copy_(rm2); is2.copy_(torch.rsqrt(rv2 + BN_EPS))
     more = () if pending is None else (pmask,)
     if not tail:
-        return (None, (x, y1, y2, None, cst, w1, w2, g1, g2)) + more
+        return (None, BlockSaved(x, y1, y2, None, cst, w1, w2, g1, g2)) + more
     if want_grad:
         # the backward needs only the SIGN of `out`: one bit per element, written beside it (a frame pass less in backward)
         mask = torch.empty(B * 64 * ((T + 31) // 32), dtype=torch.int32, device=dev)
@@ -587,7 +613,7 @@ def _resblock_fwd(x, params, training, want_grad, tail=True, pending=None, stem=
     else:
         mask = None
         lib.wm_bn_add_relu(_p(x), _p(y2), _p(sc2), _p(sh2), _p(out), B, T, st)
-    return (out, (x, y1, y2, mask, cst, w1, w2, g1, g2)) + more
+    return (out, BlockSaved(x, y1, y2, mask, cst, w1, w2, g1, g2)) + more
 
 
 class ResBlockFn(GradAwareFunction):
@@ -595,29 +621,28 @@ class ResBlockFn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, *args):
-        params, training = args[:14], args[14]
+        params, (training,) = _cut(args, BlockParams)
         out, saved = _resblock_fwd(x, params, training, wants_grad(ctx))
         if saved is not None:
             ctx.training = bool(training)
-            ctx.gdst = _gdst(params[0], params[1], params[4], params[5])      # w1, b1, w2, b2
+            ctx.gdst = _gdst(params.w1, params.b1, params.w2, params.b2)
             ctx.save_for_backward(*saved)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        return _resblock_bwd(ctx.saved_tensors, ctx.training, ctx.gdst, g_out) + (None,) * 7
+        dx, *grads = _resblock_bwd(ctx.saved_tensors, ctx.training, ctx.gdst, g_out)
+        return (dx,) + _block_grads(grads) + (None,)                          # (training: none)
 
 
 def _resblock_bwd(saved, training, gdst, g_out):
     """Backward of one ResBlock: (dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2).  The fused path where it applies, else one launch per
     product; gdst = the four weight-gradient destinations of _gdst (all None: fresh tensors, launched in line)."""
-    x, y1, y2, mask, cst, w1, w2, g1, g2 = saved
-    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
+    x, y1, y2, mask, cst, w1, w2, g1, g2 = saved = BlockSaved._make(saved)
+    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = _bn_consts(cst)
     g_out = g_out.contiguous()
     B, _, T = x.shape
-    dev, st = x.device, _stream()
-    ev = 0 if training else 1
-    n = float(B * T)
+    dev, st, ev, n = x.device, _stream(), 0 if training else 1, float(B * T)
     if _CONV["bf16x6"] and _CONV["fused_bwd"] and T % 64 == 0 and not all(g is not None for g in gdst):
         dx, grads, _ = _resblock_bwd_fused(saved, training, g_out)
         return (dx,) + grads
@@ -625,12 +650,10 @@ def _resblock_bwd(saved, training, gdst, g_out):
     part = _f32(max(B, 1) * 128, device=dev)
     dz2 = torch.empty_like(x)
     lib.wm_relu_bwd_reduce_mask(_p(g_out), _p(mask), _p(y2), _p(dz2), _p(part), None, B, T, st)
-    k2 = _f32(4, 64, device=dev)          # A, B (hi), B (lo), C  -- B is handed over as hi + lo words
-    dg2, dbe2 = _f32(64, device=dev), _f32(64, device=dev)
+    k2, dg2, dbe2 = _f32(4, 64, device=dev), _f32(64, device=dev), _f32(64, device=dev)     # k: A, B (hi), B (lo), C -- B as hi + lo words
     lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev, None, 0, None, st)
     # conv2: data gradient (+ ReLU mask + BN1-backward reductions in the epilogue) and weight gradient
-    dz1 = torch.empty_like(x)
-    stats = _f32(NCU * 128, device=dev)
+    dz1, stats = torch.empty_like(x), _f32(NCU * 128, device=dev)
     _conv3(dz2, y2, w2, 1, k2[0], k2[1], k2[3], None, y1, sc1, sh1, dz1, stats, B, T, 3, 1)
 
     def wgrad(dz, y, k, xin, sc, sh, xpro, dw, db):
@@ -642,8 +665,7 @@ def _resblock_bwd(saved, training, gdst, g_out):
             lib.wm_wgrad64(_p(dz), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(xin), _p(sc), _p(sh), _p(wpart), _p(dw), _p(db),
                            B, T, 3, 3, xpro, 0, 1 if acc else 0, _stream())
     launch((dz2, y2, k2, y1, cst), lambda: wgrad(dz2, y2, k2, y1, sc1, sh1, 1, dw2, db2))
-    k1 = _f32(4, 64, device=dev)
-    dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
+    k1, dg1, dbe1 = _f32(4, 64, device=dev), _f32(64, device=dev), _f32(64, device=dev)
     lib.wm_bn_bwd_finalize(_p(stats), NCU, n, _p(g1), _p(mu1), _p(is1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(dg1), _p(dbe1), 0, ev, None, 0, None, st)
     # conv1: data gradient + residual path, weight gradient
     dx = torch.empty_like(x)
@@ -659,84 +681,68 @@ def _resblock_bwd_fused(saved, training, g_out, pre=None, fold=None, rank1=None,
     dz2 = g (out > 0) and its two BatchNorm sums exist (made by the next block's folded conv1 launch): no reduction pass, no mask.
     `fold` = (mask, y2) of the block BEFORE this one: the conv1 launch then writes that block's dz2 instead of the plain input
     gradient and returns (its BatchNorm-sum partials, its max |dz| per workgroup) as the third value.
-    `rank1` = (g1 [B,1,T], hw [1,64,1]) with g_out None: the gradient w.r.t. the block output is hw[c] g1[b,t] and is formed on load
-    (head1_rank1_applies; neither `pre` nor `fold`).
+    `rank1` = (g1 [B,1,T], hw [1,64,1]), g_out None, neither `pre` nor `fold` (head1_rank1_applies): dout = hw[c] g1[b,t] is formed on load.
     `stem` = (s, w, b) of the Conv1d(1, 64, 7) whose output is this block's x (with `pre`): where _stem_in_dwgrad_launches, the conv1
     pair forms its weight-gradient operand from them instead of reading x (wm_dwgrad64_bf_stem).
     Returns (dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fold outputs | None)."""
-    x, y1, y2, mask, cst, w1, w2, g1, g2 = saved
-    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = cst.unbind(0)
+    if (rank1 is not None and (pre is not None or fold is not None)) or (stem is not None and pre is None):
+        raise ValueError("_resblock_bwd_fused: rank1 goes with neither pre nor fold, and stem needs pre")
+    x, y1, y2, mask, cst, w1, w2, g1, g2 = BlockSaved._make(saved)
+    sc1, sh1, mu1, is1, sc2, sh2, mu2, is2 = _bn_consts(cst)
     B, _, T = x.shape
-    dev, st = x.device, _stream()
-    ev = 0 if training else 1
-    n = float(B * T)
-    h = 1 if _CONV["bwd_f16x3"] else 0        # arithmetic of the two launches; the f16 split needs the gradient's scale (max |dz|)
-    pack = pack_w64_h if h else pack_w64_bf
-    k2 = _f32(4, 64, device=dev)          # A, B (hi), B (lo), C  -- B is handed over as hi + lo words
-    dg2, dbe2 = _f32(64, device=dev), _f32(64, device=dev)
+    dev, st, ev, n = x.device, _stream(), 0 if training else 1, float(B * T)
+    h, pack = (1, pack_w64_h) if _CONV["bwd_f16x3"] else (0, pack_w64_bf)      # the launches' arithmetic; the f16 split needs max |dz|
+    k2, dg2, dbe2 = _f32(4, 64, device=dev), _f32(64, device=dev), _f32(64, device=dev)     # k: A, B (hi), B (lo), C -- B as hi + lo words
     gs2 = _f32(2, device=dev) if h else None
     if rank1 is not None:
-        r1g, r1w = rank1
         part, dzm = _f32(max(B, 1) * 128, device=dev), _f32(B * 64, device=dev)
-        lib.wm_relu_bwd_reduce_mask_r1(_p(r1g), _p(r1w), _p(mask), _p(y2), _p(part), _p(dzm), B, T, st)
-        lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
-                               _p(dzm), B * 64, _p(gs2), st)
-        gsrc, gm = None, mask
+        lib.wm_relu_bwd_reduce_mask_r1(*map(_p, rank1), _p(mask), _p(y2), _p(part), _p(dzm), B, T, st)
+        gsrc, gm, sums = None, mask, (_p(part), B, _p(dzm), B * 64)
     elif pre is not None:
-        ppart, pmax = pre
-        gsrc, gm = g_out, None
-        lib.wm_bn_bwd_finalize(_p(ppart), NCU, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
-                               _p(pmax) if h else None, NCU, _p(gs2), st)
+        gsrc, gm, sums = g_out, None, (_p(pre[0]), NCU, _p(pre[1]) if h else None, NCU)
     else:
         # dz2 = g_out * (out > 0) is never written (default): the reduction pass only forms the two BatchNorm sums, and the two
         # convolution-backward launches mask g_out with the same bits while they load it (wm_dwgrad64_bf's gmask)
-        part = _f32(max(B, 1) * 128, device=dev)
-        dzm = _f32(B * 64, device=dev) if h else None
+        part, dzm = _f32(max(B, 1) * 128, device=dev), (_f32(B * 64, device=dev) if h else None)
         dz2 = None if _CONV["mask_on_load"] else torch.empty_like(x)
         lib.wm_relu_bwd_reduce_mask(_p(g_out), _p(mask), _p(y2), _p(dz2), _p(part), _p(dzm), B, T, st)
-        lib.wm_bn_bwd_finalize(_p(part), B, n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
-                               _p(dzm), B * 64, _p(gs2), st)
-        gsrc, gm = (g_out, mask) if dz2 is None else (dz2, None)
+        gsrc, gm, sums = *((g_out, mask) if dz2 is None else (dz2, None)), (_p(part), B, _p(dzm), B * 64)
+    lib.wm_bn_bwd_finalize(sums[0], sums[1], n, _p(g2), _p(mu2), _p(is2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(dg2), _p(dbe2), 0, ev,
+                           sums[2], sums[3], _p(gs2), st)         # sums: partials, their count, max |dz2| per slot, the slots
     # conv2: data gradient (+ ReLU mask + BN1-backward reductions in the epilogue) and weight gradient
-    dz1 = torch.empty_like(x)
-    stats = _f32(NCU * 128, device=dev)
+    dz1, stats = torch.empty_like(x), _f32(NCU * 128, device=dev)
     dzm1 = _f32(NCU, device=dev) if h else None          # max |dz1| per workgroup, written by the conv2-pair launch
     dw2, db2, dw1, db1 = torch.empty_like(w2), _f32(64, device=dev), torch.empty_like(w1), _f32(64, device=dev)
     wpart = _f32(NCU * (3 * 4096 + 64), device=dev)
-    if rank1 is not None:
-        lib.wm_dwgrad64_bf_r1(None, _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(pack(w2, 1)), _p(y1), _p(sc1), _p(sh1),
-                              _p(y1), _p(sc1), _p(sh1), _p(dz1), _p(stats), _p(wpart), _p(dw2), _p(db2), B, T, 1, 1, 0, _p(gm), h, _p(gs2), _p(dzm1),
-                              _p(r1g), _p(r1w), st)
-    else:
-        lib.wm_dwgrad64_bf(_p(gsrc), _p(y2), _p(k2[0]), _p(k2[1]), _p(k2[3]), _p(pack(w2, 1)), _p(y1), _p(sc1), _p(sh1),
-                           _p(y1), _p(sc1), _p(sh1), _p(dz1), _p(stats), _p(wpart), _p(dw2), _p(db2), B, T, 1, 1, 0, _p(gm), h, _p(gs2), _p(dzm1), st)
-    k1 = _f32(4, 64, device=dev)
-    dg1, dbe1 = _f32(64, device=dev), _f32(64, device=dev)
+
+    def pair(*, g, y, k, w, out, dw, db, gs, omax, xw=None, xa=None, xb=None, e1=None, ea=None, eb=None, stats=None, xpro=0, epi=2,
+             stem=None):    # one pair launch, argument names as in wm_dwgrad64_bf's prototype; its _r1 twin under rank1, _stem with `stem`
+        head = (_p(g), _p(y), _p(k[0]), _p(k[1]), _p(k[3]), _p(pack(w, 1)))
+        if stem is not None:
+            return lib.wm_dwgrad64_bf_stem(*head, _p(e1), _p(out), _p(wpart), _p(dw), _p(db), B, T, 0, _p(gs), _p(omax), *map(_p, stem), st)
+        entry = lib.wm_dwgrad64_bf if rank1 is None else lib.wm_dwgrad64_bf_r1
+        entry(*head, _p(xw), _p(xa), _p(xb), _p(e1), _p(ea), _p(eb), _p(out), _p(stats), _p(wpart), _p(dw), _p(db), B, T, xpro, epi, 0,
+              _p(gm), h, _p(gs), _p(omax), *map(_p, rank1 or ()), st)
+    pair(g=gsrc, y=y2, k=k2, w=w2, xw=y1, xa=sc1, xb=sh1, xpro=1, e1=y1, ea=sc1, eb=sh1, epi=1, out=dz1, stats=stats, omax=dzm1,
+         dw=dw2, db=db2, gs=gs2)
+    k1, dg1, dbe1 = _f32(4, 64, device=dev), _f32(64, device=dev), _f32(64, device=dev)
     gs1 = _f32(2, device=dev) if h else None
     lib.wm_bn_bwd_finalize(_p(stats), NCU, n, _p(g1), _p(mu1), _p(is1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(dg1), _p(dbe1), 0, ev,
                            _p(dzm1), NCU, _p(gs1), st)
-    dx = torch.empty_like(x)
-    fout = None
+    dx, fout = torch.empty_like(x), None
+    conv1 = dict(g=dz1, y=y1, k=k1, w=w1, out=dx, dw=dw1, db=db1, gs=gs1)
     if fold is not None and gm is not None:
         # conv1 pair that also does the PREVIOUS block's ReLU backward and BatchNorm sums (epi 8): dx leaves as that block's dz2
         pmask, py2 = fold
-        fpart = _f32(NCU * 128, device=dev)
-        fmax = _f32(NCU, device=dev) if h else None
-        lib.wm_dwgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
-                           _p(gsrc), _p(py2), _p(pmask), _p(dx), _p(fpart), _p(wpart), _p(dw1), _p(db1), B, T, 0, 8, 0, _p(gm), h, _p(gs1), _p(fmax), st)
+        fpart, fmax = _f32(NCU * 128, device=dev), (_f32(NCU, device=dev) if h else None)
+        pair(xw=x, e1=gsrc, ea=py2, eb=pmask, epi=8, stats=fpart, omax=fmax, **conv1)
         fout = (fpart, fmax)
     else:
         xmax = _f32(NCU, device=dev) if h else None          # max |dx| per workgroup: a consumer that splits dx into f16 pieces
-        if rank1 is not None:
-            lib.wm_dwgrad64_bf_r1(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
-                                  None, None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax),
-                                  _p(r1g), _p(r1w), st)
-        elif stem is not None and gm is None and _stem_in_dwgrad_launches(x):
-            lib.wm_dwgrad64_bf_stem(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(gsrc), _p(dx), _p(wpart),
-                                    _p(dw1), _p(db1), B, T, 0, _p(gs1), _p(xmax), _p(stem[0]), _p(stem[1]), _p(stem[2]), st)
+        if stem is not None and _stem_in_dwgrad_launches(x):
+            pair(e1=gsrc, omax=xmax, stem=stem, **conv1)
         else:
-            lib.wm_dwgrad64_bf(_p(dz1), _p(y1), _p(k1[0]), _p(k1[1]), _p(k1[3]), _p(pack(w1, 1)), _p(x), None, None,
-                               _p(gsrc), None, None, _p(dx), None, _p(wpart), _p(dw1), _p(db1), B, T, 0, 2, 0, _p(gm), h, _p(gs1), _p(xmax), st)
+            pair(xw=x, e1=gsrc, omax=xmax, **conv1)          # (rank1: gsrc is None, the addend is formed on load)
         if h:
             _note_gmax(dx, xmax)                             # (ConvT7Fn.backward) then needs no pass over it for its scale
     return dx, (dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2), fout
@@ -749,16 +755,22 @@ def pair_node_applies(x) -> bool:
 
 
 def _pair_fwd(x, p1, p2, training, want_grad, tail=True, stem=None):
-    """Two ResBlocks in a row, the second one up to `tail` (as _resblock_fwd's): (out | None, first, second), the two blocks' `saved`.
-    Where the tail-in-consumer launches apply, the first block's tail is formed by the second block's conv1 launch; same tensors
-    either way.  stem: _resblock_fwd's, for the first block (x is then ignored)."""
+    """Two ResBlocks in a row, the second up to `tail` (as _resblock_fwd's): (out | None, first, second), the two blocks' `saved`; stem
+    as _resblock_fwd's.  Where the tail-in-consumer launches apply, the second block's conv1 launch forms the first block's tail."""
     if training and _tail_in_consumer_launches(x if stem is None else stem[0]):
         _, first = _resblock_fwd(x, p1, True, want_grad, tail=False, stem=stem)
         out, second, pmask = _resblock_fwd(None, p2, True, want_grad, tail=tail, pending=first)
-        return out, first[:3] + (pmask,) + first[4:], second
+        return out, first._replace(mask=pmask), second
     mid, first = _resblock_fwd(x, p1, training, want_grad, stem=stem)
     out, second = _resblock_fwd(mid, p2, training, want_grad, tail=tail)
     return out, first, second
+
+
+def _pair_bwd(first, second, training, g_out, stem=None):
+    """ResBlockPairFn's backward on _pair_fwd's two `saved`: (dx, both blocks' _block_grads in a row).  stem: unused if nothing was folded"""
+    dmid, grads2, fout = _resblock_bwd_fused(second, training, g_out, fold=(first.mask, first.y2))
+    dx, grads1, _ = _resblock_bwd_fused(first, training, dmid, pre=fout, stem=stem if stem and fout else None)
+    return dx, _block_grads(grads1) + _block_grads(grads2)
 
 
 class ResBlockPairFn(GradAwareFunction):
@@ -774,36 +786,30 @@ class ResBlockPairFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, g_out):
-        return _pair_node_bwd(ctx, g_out, None)
+        return _behind_stem(ctx, *_pair_node_bwd(ctx, g_out))
 
 
 def _pair_node_fwd(ctx, x, args, stem):
-    p1, p2, training = args[:14], args[14:28], args[28]
+    p1, p2, (training,) = _cut(args, BlockParams, BlockParams)
     out, first, second = _pair_fwd(x, p1, p2, training, wants_grad(ctx), stem=stem)
-    ctx.save_for_backward(*(first + second + (stem or ())))
+    ctx.save_for_backward(*first, *second, *(stem or ()))
     ctx.training = bool(training)
     return out
 
 
-def _pair_node_bwd(ctx, g_out, stem):
-    sv = ctx.saved_tensors
-    s1_, s2_ = sv[:9], sv[9:18]
-    g_out = g_out.contiguous()
-    dmid, grads2, fout = _resblock_bwd_fused(s2_, ctx.training, g_out, fold=(s1_[3], s1_[2]))
-    dx, grads1, _ = _resblock_bwd_fused(s1_, ctx.training, dmid, pre=fout, stem=stem)
-    return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (None,)
+def _pair_node_bwd(ctx, g_out):
+    first, second, stem = _cut(ctx.saved_tensors, BlockSaved, BlockSaved)
+    dx, grads = _pair_bwd(first, second, ctx.training, g_out.contiguous(), stem)
+    return dx, grads + (None,), stem                                          # (training: none)
 
 
-def _stem_of(ctx):
-    """the (s, w, b) a Stem* node saved behind everything else"""
-    return tuple(ctx.saved_tensors[-3:])
-
-
-def _behind_stem(ctx, grads, extra=0):
-    """a Stem* node's backward from its plain twin's `grads` = (dx of the first block, ...): wm_stem_bwd on dx exactly as
-    StemFn.backward runs it -> (ds, dw, db) + `extra` Nones + the rest"""
-    s, w, _ = _stem_of(ctx)
-    return _stem_bwd(s, w, grads[0], ctx.grad_rows, ctx.needs_input_grad[0]) + (None,) * extra + grads[1:]
+def _behind_stem(ctx, dx, rest, stem, between=()):
+    """a node's return value: (dx,) -- behind a saved stem (ds, dw, db) from wm_stem_bwd on dx, exactly as StemFn.backward runs it --
+    then `between` (the arguments in front of the blocks' that get no gradient), then rest (the gradients of `args`)"""
+    if not stem:
+        return (dx,) + between + rest
+    s, w, _ = stem
+    return _stem_bwd(s, w, dx, ctx.grad_rows, ctx.needs_input_grad[0]) + between + rest
 
 
 class StemResBlockPairFn(GradAwareFunction):
@@ -820,7 +826,7 @@ class StemResBlockPairFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, g_out):
-        return _behind_stem(ctx, _pair_node_bwd(ctx, g_out, _stem_of(ctx)), extra=1)
+        return _behind_stem(ctx, *_pair_node_bwd(ctx, g_out), between=(None,))                  # (grad_rows: none)
 
 
 # ------------------------------------------------------------------------------------------ stem / heads
@@ -931,22 +937,21 @@ class ResBlockHead1Fn(GradAwareFunction):
 
     @staticmethod
     def forward(ctx, x, *args):
-        params, hw, hb = args[:14], args[14], args[15]
+        params, (hw, hb) = _cut(args, BlockParams)
         want = wants_grad(ctx)
         _, saved = _resblock_fwd(x, params, True, want, tail=False)
-        x, _, y2, _, cst = saved[:5]
+        x = saved.x
         B, _, T = x.shape
         out, mask = torch.empty_like(x), _tail_mask(x, want)
         y = _f32(B, 1, T, device=x.device)
-        lib.wm_head1_tail_fwd(_p(x), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(out), _p(mask), _p(y), B, T, _stream())
+        lib.wm_head1_tail_fwd(_p(x), _p(saved.y2), _p(saved.sc2), _p(saved.sh2), _p(hw), _p(hb), _p(out), _p(mask), _p(y), B, T, _stream())
         if want:
-            ctx.save_for_backward(*(saved[:3] + (mask,) + saved[4:] + (out, hw)))
+            ctx.save_for_backward(*saved._replace(mask=mask), out, hw)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        sv = ctx.saved_tensors
-        out, hw = sv[9], sv[10]
+        saved, (out, hw) = _cut(ctx.saved_tensors, BlockSaved)
         B, _, T = out.shape
         g = g.contiguous()
         part = _f32(1024 * 65, device=out.device)
@@ -954,11 +959,12 @@ class ResBlockHead1Fn(GradAwareFunction):
         if head1_rank1_applies(out):
             # dout[b,c,t] = hw[c] g[b,t] stays out of memory: the block's three readers of it form it on load
             lib.wm_head1_bwd(_p(g), _p(out), _p(hw), None, _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
-            dx, grads, _ = _resblock_bwd_fused(sv[:9], True, None, rank1=(g, hw))
-            return (dx,) + grads + (None,) * 6 + (dhw, dhb)
-        dout = torch.empty_like(out)
-        lib.wm_head1_bwd(_p(g), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
-        return _resblock_bwd(sv[:9], True, (None,) * 4, dout) + (None,) * 6 + (dhw, dhb)
+            dx, grads, _ = _resblock_bwd_fused(saved, True, None, rank1=(g, hw))
+        else:
+            dout = torch.empty_like(out)
+            lib.wm_head1_bwd(_p(g), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), B, T, 0, _stream())
+            dx, *grads = _resblock_bwd(saved, True, (None,) * 4, dout)
+        return (dx,) + _block_grads(grads) + (dhw, dhb)
 
 
 class DetectorTailFn(GradAwareFunction):
@@ -974,7 +980,7 @@ class DetectorTailFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, g_logits, g_loc, g_bce):
-        return _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, None)
+        return _behind_stem(ctx, *_detector_tail_bwd(ctx, g_logits, g_loc, g_bce), between=(None,))          # (message: none)
 
 
 class StemDetectorTailFn(GradAwareFunction):
@@ -989,32 +995,30 @@ class StemDetectorTailFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, g_logits, g_loc, g_bce):
-        grads = _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, _stem_of(ctx))
-        return _behind_stem(ctx, grads[:1] + grads[2:], extra=2)          # (grad_rows, message: none)
+        return _behind_stem(ctx, *_detector_tail_bwd(ctx, g_logits, g_loc, g_bce), between=(None, None))     # (grad_rows, message: none)
 
 
 def _detector_tail_fwd(ctx, x, message, args, stem):
-    p1, p2, hw, hb = args[:14], args[14:28], args[28], args[29]
+    p1, p2, (hw, hb) = _cut(args, BlockParams, BlockParams)
     want = wants_grad(ctx)
     _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False, stem=stem)
-    mid, y2, cst = second[0], second[2], second[4]
+    mid = second.x
     R, _, T = mid.shape
     NO, B, dev = hw.shape[0], message.shape[0], mid.device
     out, mask = torch.empty_like(mid), _tail_mask(mid, want)
     logits = _f32(R, T, NO, device=dev)
     part = _f32(2 * R * ((T + 255) // 256), device=dev)
     losses = torch.zeros(2, dtype=torch.float32, device=dev)
-    lib.wm_headN_tail_fwd(_p(mid), _p(y2), _p(cst[4]), _p(cst[5]), _p(hw), _p(hb), _p(message), B, _p(part), _p(losses[0]), _p(losses[1]),
-                          _p(out), _p(mask), _p(logits), R, T, NO, _stream())
+    lib.wm_headN_tail_fwd(_p(mid), _p(second.y2), _p(second.sc2), _p(second.sh2), _p(hw), _p(hb), _p(message), B, _p(part),
+                          _p(losses[0]), _p(losses[1]), _p(out), _p(mask), _p(logits), R, T, NO, _stream())
     ctx.set_materialize_grads(False)
     if want:
-        ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + (out, hw, logits, message) + (stem or ())))
+        ctx.save_for_backward(*first, *second._replace(mask=mask), out, hw, logits, message, *(stem or ()))
     return logits, losses[0], losses[1]
 
 
-def _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, stem):
-    sv = ctx.saved_tensors
-    s1_, s2_, (out, hw, logits, message) = sv[:9], sv[9:18], sv[18:22]
+def _detector_tail_bwd(ctx, g_logits, g_loc, g_bce):
+    first, second, (out, hw, logits, message, *stem) = _cut(ctx.saved_tensors, BlockSaved, BlockSaved)
     R, T, NO = logits.shape
     dev, st = logits.device, _stream()
     gl = g_loc.contiguous().float().reshape(1) if g_loc is not None else torch.zeros(1, device=dev)
@@ -1030,9 +1034,8 @@ def _detector_tail_bwd(ctx, g_logits, g_loc, g_bce, stem):
         lib.wm_bce_bwd(_p(logits), _p(message), _p(gl), _p(gb), _p(d), message.shape[0], R, T, NO, st)
         d += g_logits
         lib.wm_headN_bwd(_p(d), _p(out), _p(hw), _p(dout), _p(part), _p(dhw), _p(dhb), R, T, NO, 0, st)
-    dmid, grads2, fout = _resblock_bwd_fused(s2_, True, dout, fold=(s1_[3], s1_[2]))
-    dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout, stem=stem)
-    return (dx, None) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + (dhw, dhb)
+    dx, grads = _pair_bwd(first, second, True, dout, stem)
+    return dx, grads + (dhw, dhb), stem
 
 
 # ------------------------------------------------------------------------------------------ LSTM
@@ -1057,7 +1060,7 @@ class LSTMFn(GradAwareFunction):
 
 
 def _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, need_grad, tail=None):
-    """LSTMFn's forward: (h, saved) with saved = (x, h, gates, cst, w_ih, w_hh) for _lstm_bwd, None unless need_grad.  No ctx.
+    """LSTMFn's forward: (h, saved) with saved = an LstmSaved for _lstm_bwd, None unless need_grad.  No ctx.
     tail = (xres, y2, sc2, sh2, mask | None) of the ResBlock in front (tail_in_consumer_applies with lstm=True; x is ignored): the
     launch (wm_lstm_fwd_tail) forms that block's output on load and writes it -- the LSTM's x -- and the mask."""
     if tail is not None:
@@ -1081,14 +1084,14 @@ def _lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, need_grad, tail=None):
         lib.wm_lstm_xproj(_p(x), _p(w_ih), _p(b_ih), _p(b_hh), _p(xp), B, T, st)
         gates = xp if need_grad else None       # activations overwrite the projections in place
         lib.wm_lstm_fwd(_p(xp), _p(w_hh), _p(h), _p(gates), _p(cst), B, T, st)
-    return h, ((x, h, gates, cst, w_ih, w_hh) if need_grad else None)
+    return h, (LstmSaved(x, h, gates, cst, w_ih, w_hh) if need_grad else None)
 
 
 def _lstm_bwd(saved, gdst, dh, dx_inside=False):
     """LSTMFn's backward on _lstm_fwd's saved tensors: (dx, dw_ih, dw_hh, db_ih, db_hh); gdst = the four destinations of _gdst.
     dx_inside (EncoderLSTMFn, set_lstm_dx_in_bwd): dx comes out of the wave-specialised BPTT launch itself, unless the side-stream
     option is on.  (The library's own fp32 choice, wm_set_lstm_dx_bf16x6(0), is not visible here: the entry point honours it.)"""
-    x, h, gates, cst, w_ih, w_hh = saved
+    x, h, gates, cst, w_ih, w_hh = LstmSaved._make(saved)
     dh = dh.contiguous()
     B, _, T = x.shape
     dev, st = x.device, _stream()
@@ -1129,7 +1132,7 @@ class EncoderLSTMFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, dh):
-        return _encoder_lstm_bwd(ctx, dh, None)
+        return _behind_stem(ctx, *_encoder_lstm_bwd(ctx, dh))
 
 
 class StemEncoderLSTMFn(GradAwareFunction):
@@ -1144,30 +1147,27 @@ class StemEncoderLSTMFn(GradAwareFunction):
 
     @staticmethod
     def backward(ctx, dh):
-        return _behind_stem(ctx, _encoder_lstm_bwd(ctx, dh, _stem_of(ctx)))
+        return _behind_stem(ctx, *_encoder_lstm_bwd(ctx, dh))
 
 
 def _encoder_lstm_fwd(ctx, x, args, stem):
-    p1, p2, (w_ih, w_hh, b_ih, b_hh) = args[:14], args[14:28], args[28:32]
+    p1, p2, (w_ih, w_hh, b_ih, b_hh) = _cut(args, BlockParams, BlockParams)
     want = wants_grad(ctx)
     _, first, second = _pair_fwd(x, p1, p2, True, want, tail=False, stem=stem)
-    mid, y2, cst = second[0], second[2], second[4]
-    mask = _tail_mask(mid, want)
-    h, lsaved = _lstm_fwd(None, w_ih, w_hh, b_ih, b_hh, want, tail=(mid, y2, cst[4], cst[5], mask))
+    mask = _tail_mask(second.x, want)
+    h, lsaved = _lstm_fwd(None, w_ih, w_hh, b_ih, b_hh, want, tail=(second.x, second.y2, second.sc2, second.sh2, mask))
     if want:
         ctx.gdst = _gdst(w_ih, w_hh, b_ih, b_hh)
-        ctx.save_for_backward(*(first + second[:3] + (mask,) + second[4:] + lsaved + (stem or ())))
+        ctx.save_for_backward(*first, *second._replace(mask=mask), *lsaved, *(stem or ()))
     return h
 
 
-def _encoder_lstm_bwd(ctx, dh, stem):
-    sv = ctx.saved_tensors
+def _encoder_lstm_bwd(ctx, dh):
+    first, second, lsaved, stem = _cut(ctx.saved_tensors, BlockSaved, BlockSaved, LstmSaved)
     _single_backward(ctx, "EncoderLSTMFn")
-    s1_, s2_ = sv[:9], sv[9:18]
-    lgrads = _lstm_bwd(sv[18:24], ctx.gdst, dh, dx_inside=_LSTM_DX["in_bwd"])
-    dmid, grads2, fout = _resblock_bwd_fused(s2_, True, lgrads[0], fold=(s1_[3], s1_[2]))
-    dx, grads1, _ = _resblock_bwd_fused(s1_, True, dmid, pre=fout, stem=stem)
-    return (dx,) + grads1 + (None,) * 6 + grads2 + (None,) * 6 + lgrads[1:]
+    dmid, *lgrads = _lstm_bwd(lsaved, ctx.gdst, dh, dx_inside=_LSTM_DX["in_bwd"])
+    dx, grads = _pair_bwd(first, second, True, dmid, stem)
+    return dx, grads + tuple(lgrads), stem
 
 
 # ------------------------------------------------------------------------------------------ embedding + convT

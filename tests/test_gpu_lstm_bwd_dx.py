@@ -95,12 +95,6 @@ ROUTE_B, ROUTE_T = 2, 128
 SPIED = ("wm_lstm_bwd_wgrad_dx", "wm_lstm_bwd_wgrad", "wm_lstm_dx", "wm_lstm_bwd", "wm_lstm_bwd_fused", "wm_lstm_wgrad")
 
 
-def _rb_args(m):
-    c1, n1, _, c2, n2 = m.block
-    return (c1.weight, c1.bias, n1.weight, n1.bias, c2.weight, c2.bias, n2.weight, n2.bias,
-            n1.running_mean, n1.running_var, n1.num_batches_tracked, n2.running_mean, n2.running_var, n2.num_batches_tracked)
-
-
 @pytest.fixture(scope="module")
 def gen(awm, dev):
     G, _ = reference_models(awm, dev)
@@ -112,7 +106,7 @@ def _run(awm, gen, dev, on, monkeypatch, node="encoder", T=ROUTE_T, flat=False):
     node = "encoder": ops.EncoderLSTMFn | "lstm": the two blocks as their pair node, then plain ops.LSTMFn.  flat: the LSTM's parameters
     carry side-stream gradient destinations (the caller has switched the option on)."""
     from awm_amd import ops
-    from awm_amd.modules import resblock_pair
+    from awm_amd.modules import _rb_args, resblock_pair
     G = copy.deepcopy(gen)
     e1, e2 = G.encoder[1], G.encoder[2]
     lstm = (G.lstm.weight_ih_l0, G.lstm.weight_hh_l0, G.lstm.bias_ih_l0, G.lstm.bias_hh_l0)
